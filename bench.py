@@ -97,6 +97,41 @@ class MaskStream:
         return d["masks"], d["upperbound"]
 
 
+DUMP_SAMPLE = 1 << 20      # --dump-outputs: elements kept of a larger array (the same seeded subset on every run)
+DUMP_PARAM_SAMPLE = 2048   # elements kept per parameter tensor of the updated weights
+DUMP_LIMIT = 64 << 20      # bytes written in all
+
+
+def _sample(t, n, seed):
+    """t flattened; more than n elements: the n at fixed seeded positions (sorted), so two runs pick the same ones"""
+    flat = t.detach().reshape(-1)
+    if flat.numel() <= n:
+        return flat
+    idx = torch.randint(0, flat.numel(), (n,), generator=torch.Generator().manual_seed(seed)).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs DIR: writes DIR/<name>.npy for every array (float64 stays float64, everything else float32)"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = _sample(t, DUMP_SAMPLE, 0)
+        host[name] = t.double().cpu().numpy() if t.dtype == torch.float64 else t.float().cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs: {total} bytes > {DUMP_LIMIT}"
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    print(f"[bench] wrote {len(host)} arrays ({total / 1e6:.2f} MB) to {path}", file=sys.stderr, flush=True)
+
+
+def param_sample(model):
+    """the weights after the step: DUMP_PARAM_SAMPLE seeded elements of every floating-point state-dict tensor, in state-dict order"""
+    parts = [_sample(v, DUMP_PARAM_SAMPLE, i).float() for i, v in enumerate(model.state_dict().values()) if v.is_floating_point()]
+    return torch.cat(parts)
+
+
 def text_fwd_gflop(D, L, T):
     return (L * (2 * T * 12 * D * D + 4 * T * T * D) + 2 * D * D) / 1e9
 
@@ -254,6 +289,8 @@ def bench_forward(args, world, rank, dev):
         n_bf16 = max(2, args.steps // 2)
         model.enable_fp8_forward(img[: min(B, 16)])
         el, (lat_8, rec_8) = timed(args.steps, args.warmup)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"latents": lat_8, "reconstruction": rec_8})
         rec_same = model.get_latents_decoded_images(lat_b)
         rel = lambda a, b: float((a - b).norm() / b.norm())
         err = {"latents_rel": round(rel(lat_8, lat_b), 5), "decoder_rel_same_latents": round(rel(rec_same, rec_b), 5),
@@ -349,6 +386,10 @@ def main():
     ap.add_argument("--prototypes", type=int, default=65536, help="DINO head out_dim K (DINOv2 default 65536; unpinned)")
     ap.add_argument("--perceptual-weight", type=float, default=0.0,
                     help="> 0: add the LPIPS perceptual term (VGG16, seeded random weights: vgg.pth is a download) to the rec loss")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (rank 0; large arrays as a fixed "
+                         "seeded sample): train workloads the losses and a sample of the updated weights, forward workloads the "
+                         "latents and reconstructions")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -518,6 +559,14 @@ def main():
         return model, lp, trainer, txt, launch, elapsed, loss, closs
 
     model, lp, trainer, txt, launch, elapsed, loss, closs = measure(args.perceptual_weight, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:  # before the instrumented step below changes the weights again
+        outs = {"rec_loss": loss.reshape(-1), "clip_loss": closs.reshape(-1)}
+        if do_ssl:
+            outs["ssl_loss"] = trainer.ssl_loss_sum.reshape(-1)
+        if lp is not None:
+            outs["lpips"] = trainer.lpips_val
+        outs["params_sample"] = param_sample(model)
+        dump_outputs(args.dump_outputs, outs)
     state["host_ms_main"], state["host_split_main"] = state.get("host_ms_per_step"), state.get("host_split_ms")
     state["spread_main"] = state.get("step_ms_spread")
     state["per_step_main"] = state.get("per_step_ms")

@@ -57,6 +57,15 @@ def inputs():
 
 def generate():
     """the restatement's outputs on the real reference model, after checking every restated function against the real tool function"""
+    return _run()[0]
+
+
+def tool_outputs():
+    """what the real tool functions themselves returned on the real reference model (tests/golden/ref_pins.safetensors)"""
+    return _run()[1]
+
+
+def _run():
     ref = load_reference()
     zs, lp, rc = load_tool("test_zero_shot_hf"), load_tool("test_linear_probing_hf"), load_tool("test_reconstruction_hf")
     g = load_file(os.path.join(ROOT, "tests", "golden", "vtp_tiny.safetensors"))
@@ -73,10 +82,15 @@ def generate():
     clf = zs.build_zero_shot_classifier(model, tok, T.CLASSNAMES, T.TEMPLATES, num_classes_per_batch=3, device=dev, use_tqdm=False)
     assert torch.allclose(clf, mine["zs.classifier"], atol=1e-6), "build_zero_shot_classifier"
     t1, t5 = zs.evaluate(model, clf, [(images[:4], targets[:4]), (images[4:], targets[4:])], dev, precision="fp32")
+    tools = {"zs.classifier": clf, "zs.top": torch.tensor([t1, t5], dtype=torch.float64),
+             "zs.accuracy": torch.tensor(zs.accuracy(mine["zs.logits"], targets, topk=(1, 5)), dtype=torch.float64)}
     assert abs(t1 - float(mine["zs.top"][0])) < 1e-9 and abs(t5 - float(mine["zs.top"][1])) < 1e-9, (t1, t5, mine["zs.top"])
     assert zs.accuracy(mine["zs.logits"], targets, topk=(1, 5)) == T.accuracy(mine["zs.logits"], targets, topk=(1, 5))
     fe = lp.FeatureExtractor(model, 2, torch.float32)
     feats = fe(images)
+    for i, (p, c) in enumerate(feats):
+        tools[f"lp.patch{i}"], tools[f"lp.cls{i}"] = p, c
+    tools["lp.input_1_avg"], tools["lp.input_2"] = lp.create_linear_input(feats, 1, True), lp.create_linear_input(feats, 2, False)
     for i, (p, c) in enumerate(feats):
         assert torch.equal(p, mine[f"lp.patch{i}"]) and torch.equal(c, mine[f"lp.cls{i}"])
     assert torch.equal(lp.create_linear_input(feats, 1, True), mine["lp.input_1_avg"])
@@ -95,12 +109,17 @@ def generate():
     avg = lp.train_one_epoch(fe, clfs, opt, _NoSched(), torch.nn.CrossEntropyLoss(), batches, 0, 4, dev)
     assert abs(avg - float(mine["lp.losses"].mean())) < 1e-5, (avg, mine["lp.losses"])
     assert torch.allclose(clfs.classifiers_dict["blocks_1_avgpool_True"].linear.weight, mine["lp.w_after"], atol=1e-6)
+    tools["lp.avg_loss"] = torch.tensor([avg], dtype=torch.float64)
+    tools["lp.w_after"] = clfs.classifiers_dict["blocks_1_avgpool_True"].linear.weight.detach()
+    psnr = []
     for i in range(8):  # PSNR helper on the reconstruction block's outputs
         a = T.denormalize(images)[i].clamp(0, 1) * 255.0
+        psnr.append(float(rc.calculate_psnr(a, mine["rec.recon_denorm"][i] * 255.0)))
         assert abs(rc.calculate_psnr(a, mine["rec.recon_denorm"][i] * 255.0) - float(mine["rec.psnr"][i])) < 1e-4
+    tools["rec.psnr"] = torch.tensor(psnr, dtype=torch.float64)
     out = {"in.images": images, "in.targets": targets}
     out.update({"out." + k: v.contiguous() for k, v in mine.items()})
-    return out
+    return out, {k: v.detach().contiguous() for k, v in tools.items()}
 
 
 def main():
