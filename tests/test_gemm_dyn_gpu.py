@@ -61,7 +61,9 @@ SHAPES = [(8, 34144, 768, 768, "f32res"), (8, 34144, 2304, 768, "rope"), (8, 341
           (8, 34144, 768, 768, "bf16"), (8, 16448, 2304, 768, "bf16"), (8, 70001, 768, 256, "bf16"), (8, 33000, 1536, 320, "gelu"),
           # the half-size kernel (two workgroups per CU: 512 slots) and the one-wave-per-SIMD kernel, forced
           (9, 34144, 2304, 768, "rope"), (9, 34144, 2048, 768, "bf16"), (9, 34144, 4096, 768, "swiglu"), (9, 70001, 768, 768, "f32res"),
-          (9, 40000, 1024, 192, "bf16"), (10, 34144, 768, 4096, "bf16"), (10, 34144, 768, 2304, "bf16"), (10, 70001, 512, 2048, "bf16")]
+          (9, 40000, 1024, 192, "bf16"), (10, 34144, 768, 4096, "bf16"), (10, 34144, 768, 2304, "bf16"), (10, 70001, 512, 2048, "bf16"),
+          # the one-wave kernel below its look-ahead bound (2 k-tiles: the launch keeps the static lists) and at it (4 k-tiles: drawn)
+          (10, 34144, 768, 128, "bf16"), (10, 34144, 768, 256, "bf16")]
 
 
 @pytest.mark.parametrize("cfg,M,N,K,kind", SHAPES)
@@ -85,6 +87,28 @@ def test_dynamic_tiles_bit_identical_to_static(cfg, M, N, K, kind):
         if rep < 2:
             for t in outs:
                 t.fill_(float("nan"))
+
+
+def test_dynamic_tiles_with_a_grid_limit_below_8(monkeypatch):
+    """a vtp_gemm_debug grid limit of 4 workgroups would leave 4 of the 8 queues without a worker: the launch keeps the static lists"""
+    from vtp_amd import _lib
+    lib = _lib.load()
+    lib.vtp_set_gemm_tuning(8, 3)
+    g = torch.Generator(device=DEV).manual_seed(4)
+    run, outs = _launchers(4096, 768, 768, "bf16", g)
+    _dyn(False)
+    run()
+    ref = outs[0].clone()
+    outs[0].fill_(float("nan"))
+    monkeypatch.setenv("VTP_DIAG", "1")
+    _lib.check(lib.vtp_gemm_debug(None, 4, 0), "vtp_gemm_debug")
+    try:
+        _dyn(True)
+        run()
+        torch.cuda.synchronize()
+    finally:
+        lib.vtp_gemm_debug(None, 0, 0)
+    assert torch.equal(outs[0].view(torch.int16), ref.view(torch.int16)), f"{int((outs[0] != ref).sum())} elements differ from the static launch"
 
 
 def test_dynamic_tiles_two_streams_and_missing_cus():

@@ -37,31 +37,30 @@ def dma_piece(L, which, n, slot):
     L.append(f"v_add_u32 %[{ptr}], %[step{which}], %[{ptr}]")
 
 
-def ktile(L, slot, bc, bn, diag):
+def ktile(L, slot, bc, bn):
     o = 1 - slot
     # ---- S1
-    L += ["s_waitcnt lgkmcnt(0)"] + ([] if diag == 2 else ["s_barrier"])
+    L += ["s_waitcnt lgkmcnt(0)", "s_barrier"]
     # ---- X: rows 0..63
     reads = [(f"h{ks * 2 + b}", f"x{slot}{ks}", (2 + b) * 4096) for ks in range(4) for b in range(2)]
     for g in range(16):
         ks, q = g >> 2, g & 3
         j, i0 = q >> 1, (q & 1) * 2
-        if g in DMA_GROUPS and diag != 3:
+        if g in DMA_GROUPS:
             dma_m0(L, "b", DMA_GROUPS.index(g), slot)
         for i in (i0, i0 + 1):
             L.append(f"v_mfma_f32_32x32x16_bf16 %[c{i}{j}], %[{bc}{ks * 4 + i}], %[l{ks * 2 + j}], %[c{i}{j}]")
             if i == i0 and g < 8:  # (fragment reads in the first MFMA's shadow, the LDS-DMA piece in the second's)
                 d, a, off = reads[g]
                 L.append(f"ds_read_b128 %[{d}], %[{a}] offset:{off}")
-        if g in DMA_GROUPS and diag != 3:
+        if g in DMA_GROUPS:
             dma_piece(L, "b", DMA_GROUPS.index(g), slot)
         if g == 15:  # staging cursor: does it leave its output tile after this k-tile?  (cc = k-tiles left in the cursor's tile)
             L += ["s_sub_u32 %[cc], %[cc], 1", "s_cmp_eq_u32 %[cc], 0", "s_cselect_b32 %[sadvb], %[tadvb], %[kadvb]",
                   "s_cselect_b32 %[sadva], %[tadva], %[kadva]", "s_cselect_b32 %[cc], %[nkr], %[cc]",
                   "v_add_u32 %[peb], %[sadvb], %[peb]", "v_add_u32 %[pob], %[sadvb], %[pob]"]
     # ---- S2
-    L += [["s_waitcnt vmcnt(8) lgkmcnt(0)", "s_barrier"], ["s_waitcnt lgkmcnt(0)", "s_barrier"], ["s_waitcnt lgkmcnt(0)"],
-          ["s_waitcnt vmcnt(0) lgkmcnt(0)", "s_barrier"]][diag]
+    L += ["s_waitcnt vmcnt(8) lgkmcnt(0)", "s_barrier"]
     # ---- Y: rows 64..127; fetch A-lo + B of the next k-tile (other slot)
     reads = []
     for ks in range(4):
@@ -70,24 +69,23 @@ def ktile(L, slot, bc, bn, diag):
     for g in range(16):
         ks, q = g >> 2, g & 3
         j, i0 = q >> 1, (q & 1) * 2
-        if g in DMA_GROUPS and diag != 3:
+        if g in DMA_GROUPS:
             dma_m0(L, "a", DMA_GROUPS.index(g), slot)
         for i in (i0, i0 + 1):
             L.append(f"v_mfma_f32_32x32x16_bf16 %[c{i}{2 + j}], %[{bc}{ks * 4 + i}], %[h{ks * 2 + j}], %[c{i}{2 + j}]")
             if i == i0:
                 for d, a, off in reads[2 * g:2 * g + 2] if g < 12 else []:
                     L.append(f"ds_read_b128 %[{d}], %[{a}] offset:{off}")
-        if g in DMA_GROUPS and diag != 3:
+        if g in DMA_GROUPS:
             dma_piece(L, "a", DMA_GROUPS.index(g), slot)
         if g == 15:
             L += ["v_add_u32 %[pea], %[sadva], %[pea]", "v_add_u32 %[poa], %[sadva], %[poa]"]
 
 
-def body(diag=0):
-    """diag (timing experiments only, WRONG results): 1 = no vmcnt wait at S2 | 2 = no barriers either | 3 = no LDS-DMA"""
+def body():
     L = ["s_mov_b32 %[sm], m0", "1:"]
-    ktile(L, 0, "p", "q", diag)
-    ktile(L, 1, "q", "p", diag)
+    ktile(L, 0, "p", "q")
+    ktile(L, 1, "q", "p")
     L += ["s_sub_u32 %[cnt], %[cnt], 1", "s_cmp_lg_u32 %[cnt], 0", "s_cbranch_scc1 1b", "s_waitcnt lgkmcnt(0)", "s_mov_b32 m0, %[sm]"]
     return L
 
@@ -124,7 +122,7 @@ def tn_piece(L, which, n, slot):
           f"s_sub_u32 %[kr{which}], %[kr{which}], 8"]
 
 
-def tn_ktile(L, slot, bc, bn, csum, diag):
+def tn_ktile(L, slot, bc, bn, csum):
     o = 1 - slot
     L += ["s_waitcnt lgkmcnt(0)", "s_barrier"]
     # ---- X: rows 0..63 (A-lo x B); fetch A-hi of this k-tile; stage B of the k-tile after next
@@ -136,7 +134,7 @@ def tn_ktile(L, slot, bc, bn, csum, diag):
     for g in range(16):
         ks, q = g >> 2, g & 3
         j, i0 = q >> 1, (q & 1) * 2
-        if g in DMA_GROUPS and diag != 3:
+        if g in DMA_GROUPS:
             L.append(f"s_mov_b32 m0, %[db{slot}]" if g == 0 else "s_add_u32 m0, m0, 0x400")
             tn_piece_head(L, "b")
         for i in (i0, i0 + 1):
@@ -147,7 +145,7 @@ def tn_ktile(L, slot, bc, bn, csum, diag):
                 if csum:
                     for d, r in dots[2 * g:2 * g + 2]:
                         L.append(f"v_dot2_f32_bf16 %[{d}], v{r}, %[ones], %[{d}]")
-        if g in DMA_GROUPS and diag != 3:
+        if g in DMA_GROUPS:
             tn_piece(L, "b", DMA_GROUPS.index(g), slot)
     L += ["s_waitcnt vmcnt(8) lgkmcnt(0)", "s_barrier"]
     # ---- Y: rows 64..127 (A-hi x B); fetch A-lo + B of the next k-tile (other slot); stage A of the k-tile after next
@@ -161,7 +159,7 @@ def tn_ktile(L, slot, bc, bn, csum, diag):
     for g in range(16):
         ks, q = g >> 2, g & 3
         j, i0 = q >> 1, (q & 1) * 2
-        if g in DMA_GROUPS and diag != 3:
+        if g in DMA_GROUPS:
             L.append(f"s_mov_b32 m0, %[da{slot}]" if g == 0 else "s_add_u32 m0, m0, 0x400")
             tn_piece_head(L, "a")
         for i in (i0, i0 + 1):
@@ -171,11 +169,11 @@ def tn_ktile(L, slot, bc, bn, csum, diag):
             if csum and i == i0:
                 for d, r in dots[2 * g:2 * g + 2]:
                     L.append(f"v_dot2_f32_bf16 %[{d}], v{r}, %[ones], %[{d}]")
-        if g in DMA_GROUPS and diag != 3:
+        if g in DMA_GROUPS:
             tn_piece(L, "a", DMA_GROUPS.index(g), slot)
 
 
-def tn_body(csum, diag=0):
+def tn_body(csum):
     L = ["s_mov_b32 %[sm], m0"]
     for ks in range(4):  # the first fragments: A-lo and B (set p) of k-tile 0 in ring slot 0
         for b in range(2):
@@ -183,8 +181,8 @@ def tn_body(csum, diag=0):
         for i in range(4):
             L += tn_frag_reads("p", ks * 4 + i, f"b{'EO'[i & 1]}0", (i >> 1) * 8192 + ks * 2048)
     L.append("1:")
-    tn_ktile(L, 0, "p", "q", csum, diag)
-    tn_ktile(L, 1, "q", "p", csum, diag)
+    tn_ktile(L, 0, "p", "q", csum)
+    tn_ktile(L, 1, "q", "p", csum)
     L += ["s_sub_u32 %[cnt], %[cnt], 1", "s_cmp_lg_u32 %[cnt], 0", "s_cbranch_scc1 1b", "s_waitcnt lgkmcnt(0)", "s_mov_b32 m0, %[sm]"]
     return L
 
@@ -199,10 +197,7 @@ def emit(name, lines):
 
 def main():
     txt = "// GENERATED by tools/gen_gemm4w_ktile.py -- do not edit.  See that script for the schedule.\n"
-    txt += "#ifndef W4_DIAG\n" + emit("W4_TILE_ASM", body())
-    for d in (1, 2, 3):
-        txt += f"#elif W4_DIAG == {d}\n" + emit("W4_TILE_ASM", body(d))
-    txt += "#else\n" + emit("W4_TILE_ASM", body()) + "#endif\n"
+    txt += emit("W4_TILE_ASM", body())
     acc = ", ".join(f'[c{i}{j}] "+a"(acc[{i}][{j}])' for i in range(4) for j in range(4))
     lo = ", ".join(f'[l{r}] "+v"(fl[{r}])' for r in range(8))
     hi = ", ".join(f'[h{r}] "=&v"(fh[{r}])' for r in range(8))

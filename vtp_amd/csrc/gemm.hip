@@ -57,10 +57,7 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N) void gemm_nt_kernel(const Ge
   // walks a contiguous chunk of the tile list, n fastest: a chunk = a band of output rows x all weight panels.
   auto tile_origin = [&](int i, int& m0, int& n0) {
     int wg = blockIdx.x + i * G;
-    if (p.xcd_swizzle & 1) {  // bijective on [0, ntiles)
-      const int q = ntiles >> 3, r = ntiles & 7, x = wg & 7;
-      wg = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (wg >> 3);
-    }
+    if (p.xcd_swizzle & 1) wg = xcd_chunk_start(wg, ntiles) + (wg >> 3);  // bijective on [0, ntiles)
     n0 = (wg % tiles_n) * BN;
     m0 = (wg / tiles_n) * BM;
   };

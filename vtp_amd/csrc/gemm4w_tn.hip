@@ -240,8 +240,7 @@ __device__ __forceinline__ void w4t_segment(const GroupArgs& ga, int tile, int k
 
 // one workgroup per (tile, K slice): the launch geometry of gemm8p_grouped_tn_kernel (tiles x splits workgroups, split-major over the XCDs)
 __global__ __launch_bounds__(256, 1) void gemm4w_grouped_tn_kernel(const GroupArgs ga) {
-  const int W = gridDim.x, q = W >> 3, r = W & 7, x = blockIdx.x & 7;
-  const int c = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + ((int)blockIdx.x >> 3);
+  const int c = xcd_chunk_start(blockIdx.x, gridDim.x) + ((int)blockIdx.x >> 3);
   const int zslice = c / ga.ntiles, tile = c - zslice * ga.ntiles;
   const int kbeg = zslice * ga.k_split;
   w4t_segment(ga, tile, kbeg, min(ga.K, kbeg + ga.k_split) - kbeg, ga.splits, zslice);
@@ -251,8 +250,7 @@ __global__ __launch_bounds__(256, 1) void gemm4w_grouped_tn_kernel(const GroupAr
 // a launch need not be cut alike -- the tiles that also sum the columns of A (bias gradients: 64 v_dot2 per k-tile beside the 64 MFMAs,
 // measured 27 % slower per k-tile, tools/wgrad_timeline.py) get one slice more than the others and the launch ends level
 __global__ __launch_bounds__(256, 1) void gemm4w_grouped_tn_items_kernel(const GroupArgs ga) {
-  const int W = gridDim.x, q = W >> 3, r = W & 7, x = blockIdx.x & 7;
-  const int c = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + ((int)blockIdx.x >> 3);
+  const int c = xcd_chunk_start(blockIdx.x, gridDim.x) + ((int)blockIdx.x >> 3);
   const GroupItem& it = ga.items[c];
   w4t_segment(ga, w4t_uni(it.tile), w4t_uni(it.kbeg), w4t_uni(it.kcount), w4t_uni(it.nparts), w4t_uni(it.part));
 }

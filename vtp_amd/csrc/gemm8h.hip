@@ -36,8 +36,6 @@
 //   fragment reads (the reads complete under the previous quadrant's MFMAs, B-first double-buffered in registers) measured
 //   2-3 % SLOWER on every shape (fp32-residual epilogue: spills) and was dropped: LDS read latency is not what a lone workgroup waits for.
 #include "gemm_common.h"
-#include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 
 namespace vtp {
@@ -89,12 +87,9 @@ struct H8Frags {
   bf16x8 f[4];
 };
 
-int* gemm_tile_queue(hipStream_t s);  // gemm8p.hip: per-stream queue words of the dynamic tile assignment
-bool gemm_dyn_enabled();
-
-// DYN: tiles drawn from the per-XCD queues of p.tq instead of the static list bx, bx + G, ... -- the protocol of gemm8p_body<.., DYN>
-// (gemm8p.hip): two tiles from one blocking fetch_add(2), tile i + 2 drawn at the start of tile i's epilogue, LDS mailbox, read at
-// k-tile 1 of tile i + 1 (the cursor crosses into the next tile in k-tile nk - 2: nk >= 3)
+// DYN: tiles drawn from the queues of p.tq (TileQueue, gemm_common.h) instead of the static list bx, bx + G, ...; the tile after next,
+// posted at the end of the previous epilogue, is taken at k-tile 1 of a tile (the cursor crosses into the next tile in k-tile nk - 2:
+// nk >= 3)
 template <int EPI, int XMODE, bool DYN = false>
 __global__ __launch_bounds__(256, 2) void gemm8h_kernel(const GemmArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -108,46 +103,27 @@ __global__ __launch_bounds__(256, 2) void gemm8h_kernel(const GemmArgs p) {
   const int ntiles = tiles_m * tiles_n;
   const int G = gridDim.x, bx = blockIdx.x;
   const int n_my = DYN ? 0x10000 : (ntiles - bx + G - 1) / G;
-  int q_start = 0, q_n = 0, d_cur = -1, d_next = -1;  // DYN: my queue's chunk of the tile list; tile computed / tile the cursor moves to next
-  bool d_more = DYN, d_mail = false, s_stop = false;
-  int* const d_head = DYN ? p.tq + (bx & 7) * 16 : nullptr;
-  int* const mbox = (int*)(smem + H8_RING);  // (the epilogue staging area is idle during the k loops)
+  int d_cur = -1, d_next = -1;  // DYN: tile computed / tile the cursor moves to next
+  bool d_more = DYN, d_mail = false, s_stop = false;  // DYN: the last draw returned a tile: keep drawing
   auto pos_origin = [&](int wg, int& m0, int& n0) {
     n0 = (wg % tiles_n) << 8;
     m0 = (wg / tiles_n) << 7;
   };
   auto tile_origin = [&](int i, int& m0, int& n0) {
     int wg = bx + i * G;
-    if (p.xcd_swizzle & 1) {  // bijective on [0, ntiles): XCD x owns a contiguous chunk of the tile list
-      const int q = ntiles >> 3, r = ntiles & 7, x = wg & 7;
-      wg = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (wg >> 3);
-    }
+    if (p.xcd_swizzle & 1) wg = xcd_chunk_start(wg, ntiles) + (wg >> 3);  // bijective on [0, ntiles)
     pos_origin(wg, m0, n0);
   };
-  auto tq_exit = [&]() {
-    if (tid == 0) {
-      const int t = __hip_atomic_fetch_add(p.tq + 128, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (t == G - 1) {
-#pragma unroll
-        for (int x = 0; x < 8; ++x) __hip_atomic_store(p.tq + 16 * x, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(p.tq + 128, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-  };
-  if constexpr (DYN) {
-    const int q = ntiles >> 3, r = ntiles & 7, x = bx & 7;
-    q_n = q + (x < r ? 1 : 0);
-    q_start = x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-    if (tid == 0) *mbox = __hip_atomic_fetch_add(d_head, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    const int j = __builtin_amdgcn_readfirstlane(*(volatile int*)mbox);
-    __syncthreads();
-    if (j >= q_n) {
-      tq_exit();
+  // DYN: the queue of this workgroup (mailbox: the epilogue staging area is idle during the k loops)
+  const TileQueue tq = DYN ? TileQueue(p.tq, (int*)(smem + H8_RING), ntiles, bx) : TileQueue();
+  if constexpr (DYN) {  // the first two tiles
+    const int j = tq.first(tid);
+    if (j >= tq.n) {
+      tq.leave(tid, G);
       return;
     }
-    d_cur = q_start + j;
-    d_more = j + 1 < q_n;
+    d_cur = tq.start + j;
+    d_more = j + 1 < tq.n;
     d_next = d_more ? d_cur + 1 : -1;
   }
   const int nk = (p.K + 63) >> 6;
@@ -304,8 +280,8 @@ __global__ __launch_bounds__(256, 2) void gemm8h_kernel(const GemmArgs p) {
     else tile_origin(ti, m0, n0);
     for (int kt = 0; kt < nk; ++kt) {
       if constexpr (DYN) {
-        if (kt == 1 && d_mail) {  // left by thread 0 at the end of the previous epilogue: every wave is >= 4 barriers past that
-          d_next = __builtin_amdgcn_readfirstlane(*(volatile int*)mbox);
+        if (kt == 1 && d_mail) {  // posted by thread 0 at the end of the previous epilogue: every wave is >= 4 barriers past that
+          d_next = tq.take();
           d_more = d_next >= 0;
         }
       }
@@ -348,65 +324,24 @@ __global__ __launch_bounds__(256, 2) void gemm8h_kernel(const GemmArgs p) {
     }
     char* reg = gemm_epilogue_uses_lds<EPI, false, 64, H8_REGION>(p) ? smem + H8_RING + wave * H8_REGION : nullptr;
     // (all four ring slots hold operands of the next k-tiles here: no second staging region for the SwiGLU epilogue)
-    int d_t = 0;
-    if constexpr (DYN) {  // the tile after next
-      if (d_more && tid == 0) d_t = __hip_atomic_fetch_add(d_head, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    const int d_t = DYN ? tq.draw(d_more, tid) : 0;  // the tile after next
     gemm_epilogue<EPI, false, 128, 64, H8_REGION, XMODE>(p, acc, reg, m0, n0, 0, wave, lane, 0, nullptr);
     zero_acc();
     if constexpr (DYN) {
       d_mail = d_more;
-      if (d_more && tid == 0) *(volatile int*)mbox = d_t < q_n ? q_start + d_t : -1;
+      tq.post(d_more, tid, d_t);
       d_cur = d_next;
       d_next = -1;
       if (d_cur < 0) break;
     }
   }
-  if constexpr (DYN) tq_exit();
+  if constexpr (DYN) tq.leave(tid, G);
 }
 
 template <int EPI, int XMODE = 0>
-static int launch8h(const GemmArgs& a, hipStream_t s) {
-  auto kern = gemm8h_kernel<EPI, XMODE>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, H8_LDS);
-    attr_set = true;
-  }
-  static int slots = 0;
-  if (!slots) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    (void)hipGetDevice(&dev);
-    (void)hipGetDeviceProperties(&prop, dev);
-    int cus = prop.multiProcessorCount - prop.multiProcessorCount % 8;
-    if (cus < 8) cus = 8;
-    cus = gemm_cu_cap(cus);
-    slots = 2 * cus;  // two resident workgroups per CU
-    if (const char* e = getenv("VTP_GEMM8H_WG_PER_CU")) slots = atoi(e) > 0 ? atoi(e) * cus : slots;  // diagnostics
-    if (getenv("VTP_GEMM8H_DEBUG")) {
-      int nb = -1;
-      hipError_t rc = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)kern, 256, H8_LDS);
-      fprintf(stderr, "[gemm8h] occupancy query: %d workgroups / CU (rc %d), LDS %d B, grid slots %d\n", nb, (int)rc, H8_LDS, slots);
-    }
-  }
+static int launch8h(const GemmArgs& a, hipStream_t s) {  // two resident workgroups per CU; tiles drawn from the queues: >= 3 k-tiles
   const int ntiles = cdiv(a.M, 128) * cdiv(a.N, 256);
-  if (ntiles > slots && a.K >= 192 && (a.xcd_swizzle & 1) && gemm_dyn_enabled()) {  // persistent launch: tiles drawn from the queues
-    if (int* tq = gemm_tile_queue(s)) {
-      auto dk = gemm8h_kernel<EPI, XMODE, true>;
-      static bool dattr = false;
-      if (!dattr) {
-        (void)hipFuncSetAttribute((const void*)dk, hipFuncAttributeMaxDynamicSharedMemorySize, H8_LDS);
-        dattr = true;
-      }
-      GemmArgs b = a;
-      b.tq = tq;
-      hipLaunchKernelGGL(dk, dim3(slots), dim3(256), H8_LDS, s, b);
-      return check_launch("gemm8h_nt_dyn");
-    }
-  }
-  hipLaunchKernelGGL(kern, dim3(ntiles > slots ? slots : ntiles), dim3(256), H8_LDS, s, a);
-  return check_launch("gemm8h_nt");
+  return launch_persistent<gemm8h_kernel<EPI, XMODE>, gemm8h_kernel<EPI, XMODE, true>>(a, ntiles, 2, 256, H8_LDS, 3, s, "gemm8h_nt");
 }
 
 // entry point used by the dispatcher of gemm.hip (tile configuration 9); the caller has checked gemm8p_fits (32-bit staging offsets)

@@ -14,24 +14,19 @@
 //     with ds_read_b64_tr_b16.  Each wave issues 2 LDS-DMA pieces (global_load_lds_dwordx4, 1 KiB) per half-tile.
 //   * ring of 8 half-tile slots (2 k-tiles); the staging cursor runs 7 half-tiles ahead of the compute cursor, ACROSS output
 //     tiles (persistent workgroups: the next tile's operands stream in under the current tile's last k-tiles and epilogue).
-//   * one k-tile = 2 phases (round 4; -DVTP_P8_FOUR_PHASE builds the earlier four-phase schedule the file name comes from: 8 barrier
-//     intervals per k-tile); phase A = { reads of B-first, A-first, B-second | DMA issue | s_barrier | 16 MFMAs (rows 0..63 of the wave
-//     tile x k = 64) | s_barrier }, phase B = { reads of A-second | 3 DMA issues | s_barrier | 16 MFMAs | s_barrier }
-//     [four-phase: phase p = { fragment reads of p | LDS-DMA issue of half-tile g + 7 | s_barrier | 8 MFMAs (one 64 x 32 quadrant of
-//     the wave tile x k = 64) | s_barrier }].  The two wave groups run ONE barrier apart (group 1 executes
-//     one extra barrier in front of a tile's k loop, group 0 one behind it), so on every SIMD one wave is in its MFMA segment
-//     while its partner reads LDS / issues DMA: the matrix pipe is never shared and never idle for longer than a barrier.
-//   * `s_waitcnt vmcnt(6)` once per k-tile (phase 3): every half-tile of the next k-tile has landed, 3 stay in flight.
-//   Hazards (why the order j = B-first, A-first, B-second, A-second): the slot overwritten in phase p held the half-tile
-//   consumed >= 2 phases earlier, except B-first (consumed in phase 0, overwritten in phase 1): its four reads are issued
-//   first and retired by `lgkmcnt(8)` in front of phase 0's barrier.
+//   * one k-tile = 2 phases (round 4; the four-phase schedule of rounds 2-3 the file name comes from had 8 barrier intervals per
+//     k-tile); phase A = { reads of B-first, A-first, B-second | DMA issue | s_barrier | 16 MFMAs (rows 0..63 of the wave tile x
+//     k = 64) | s_barrier }, phase B = { reads of A-second | 3 DMA issues | s_barrier | 16 MFMAs | s_barrier }.  The two wave groups
+//     run ONE barrier apart (group 1 executes one extra barrier in front of a tile's k loop, group 0 one behind it), so on every SIMD
+//     one wave is in its MFMA segment while its partner reads LDS / issues DMA: the matrix pipe is never shared and never idle for
+//     longer than a barrier.
+//   * counted `s_waitcnt vmcnt` in front of each phase's first barrier: the half-tiles the next phase reads have landed, the younger
+//     ones stay in flight; `lgkmcnt(0)` there too: the DMA issued in the next phase overwrites the slots just read.
 //   * dedicated 32 KiB epilogue staging (4 KiB per wave) beside the 128 KiB ring: 160 KiB = all of a CU's LDS, 1 workgroup / CU.
 #include "gemm_common.h"
 #include "gemm_group.h"
 #include <cstdlib>
-#include <mutex>
 #include <type_traits>
-#include <unordered_map>
 
 namespace vtp {
 
@@ -90,18 +85,9 @@ struct GroupTile {
   int tile, splits;
 };
 
-// DYN (persistent NT launches, one K slice, >= 3 k-tiles per tile): the workgroup does not own tiles bx, bx + G, ... but DRAWS them
-// from per-XCD queues in device memory (p.tq: heads of 8 queues that hold the same contiguous chunks of the tile list as the static
-// XCD-aware order; the workgroup draws from queue bx & 7).  A launch that cannot get all of its CUs at once -- an RCCL kernel holds
-// 16 .. 32 of them for the whole backward, or another stream's GEMM is still running -- then ends when the TILES are done, not when
-// the statically-assigned tile list of a late-starting workgroup is (tools/cu_thief.py).  The staging cursor runs into the next tile
-// 1.75 k-tiles ahead of the MFMAs, so a workgroup holds TWO tiles beyond the one it computes: tiles 0 and 1 come from one blocking
-// fetch_add(2) at the start; tile i + 2 is drawn by thread 0 at the START of tile i's epilogue (an ordinary compiler-visible atomic:
-// the epilogue's own loads drain the vector-memory queue anyway), goes into an LDS mailbox at its END and is taken into an SGPR by
-// every wave at k-tile 1 of tile i + 1 -- before the cursor needs it (k-tile nk - 2).  (A returning atomic from inline asm inside the
-// k loop was tried first: its destination register is written when the result arrives, long after the statement, and the compiler
-// -- which cannot know -- had meanwhile given the register to something else: memory faults.)  The last workgroup to leave zeroes the
-// queue words.
+// DYN (persistent NT launches, one K slice, >= 4 k-tiles per tile): tiles drawn from the queues of p.tq (TileQueue, gemm_common.h)
+// instead of the static list bx, bx + G, ...  The staging cursor runs into the next tile 1.75 k-tiles ahead of the MFMAs; the tile after
+// next, posted at the end of the previous epilogue, is taken at k-tile 1 of a tile -- before the cursor needs it (k-tile nk - 2).
 template <int EPI, bool TRANS, int VAR = 0, int XMODE = 0, bool DYN = false>
 __device__ __forceinline__ void gemm8p_body(const GemmArgs& p, int bx, int zslice, const int G, const bool flat, const GroupTile gt) {
   // VAR bit 3: the operands are fp8 (e4m3, OCP) -- same bytes, same staging, same fragment reads (the launcher passes K and the
@@ -120,51 +106,29 @@ __device__ __forceinline__ void gemm8p_body(const GemmArgs& p, int bx, int zslic
   const int ntiles = tiles_m * tiles_n;
   // (bx, zslice, G): this workgroup computes tiles bx, bx + G, ... of K slice zslice (the kernels below derive them from the grid)
   const int n_my = DYN ? 0x10000 : (ntiles - bx + G - 1) / G;
-  // DYN: queue bx & 7 = positions [q_start, q_start + q_n) of the tile list; d_cur = position being computed, d_next = the one the
-  // staging cursor moves to next (-1: none), all wave-uniform
-  int q_start = 0, q_n = 0, d_cur = -1, d_next = -1;
-  bool d_more = DYN;      // the last draw returned a tile: keep drawing
-  bool d_mail = false;    // the previous tile's epilogue left a draw in the mailbox
-  int* const d_head = DYN ? p.tq + (bx & 7) * 16 : nullptr;
-  if constexpr (DYN) {
-    const int q = ntiles >> 3, r = ntiles & 7, x = bx & 7;
-    q_n = q + (x < r ? 1 : 0);
-    q_start = x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-  }
+  // DYN: d_cur = position being computed, d_next = the one the staging cursor moves to next (-1: none), all wave-uniform
+  int d_cur = -1, d_next = -1;
+  bool d_more = DYN;    // the last draw returned a tile: keep drawing
+  bool d_mail = false;  // the previous tile's epilogue left a draw in the mailbox
+  // DYN: the queue of this workgroup (mailbox: the epilogue staging area is idle during the k loops)
+  const TileQueue tq = DYN ? TileQueue(p.tq, (int*)(smem + P8_RING), ntiles, bx) : TileQueue();
   auto pos_origin = [&](int wg, int& m0, int& n0) {
     n0 = (wg % tiles_n) << 8;
     m0 = (wg / tiles_n) << 8;
   };
   auto tile_origin = [&](int i, int& m0, int& n0) {
     int wg = bx + i * G;
-    if ((p.xcd_swizzle & 1) && !flat) {  // bijective on [0, ntiles): XCD x owns a contiguous chunk of the tile list
-      const int q = ntiles >> 3, r = ntiles & 7, x = wg & 7;
-      wg = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (wg >> 3);
-    }
+    if ((p.xcd_swizzle & 1) && !flat) wg = xcd_chunk_start(wg, ntiles) + (wg >> 3);  // bijective on [0, ntiles)
     pos_origin(wg, m0, n0);
   };
-  auto tq_exit = [&]() {  // once per workgroup, behind its last draw: the last one to leave resets the queue words for the next launch
-    if (tid == 0) {
-      const int t = __hip_atomic_fetch_add(p.tq + 128, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (t == G - 1) {
-#pragma unroll
-        for (int x = 0; x < 8; ++x) __hip_atomic_store(p.tq + 16 * x, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(p.tq + 128, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-  };
-  int* const mbox = (int*)(smem + P8_RING);  // DYN: mailbox word (the epilogue staging area is idle during the k loops)
-  if constexpr (DYN) {  // the first two tiles: one blocking draw of two consecutive queue positions
-    if (tid == 0) *mbox = __hip_atomic_fetch_add(d_head, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    const int j = __builtin_amdgcn_readfirstlane(*(volatile int*)mbox);
-    __syncthreads();
-    if (j >= q_n) {
-      tq_exit();
+  if constexpr (DYN) {  // the first two tiles
+    const int j = tq.first(tid);
+    if (j >= tq.n) {
+      tq.leave(tid, G);
       return;
     }
-    d_cur = q_start + j;
-    d_more = j + 1 < q_n;
+    d_cur = tq.start + j;
+    d_more = j + 1 < tq.n;
     d_next = d_more ? d_cur + 1 : -1;
   }
   const int kbeg = zslice * p.k_split;
@@ -427,15 +391,13 @@ __device__ __forceinline__ void gemm8p_body(const GemmArgs& p, int bx, int zslic
       const char* kb = smem + (ktg & 1) * (4 * P8_SLOT);
       Frags b1, b2, a1[2], a2[2];
       if constexpr (DYN) {
-        if (kt == 1 && d_mail) {  // written by thread 0 at the end of the previous epilogue: every wave is >= 4 barriers past that
-          d_next = __builtin_amdgcn_readfirstlane(*(volatile int*)mbox);
+        if (kt == 1 && d_mail) {  // posted by thread 0 at the end of the previous epilogue: every wave is >= 4 barriers past that
+          d_next = tq.take();
           d_more = d_next >= 0;
         }
       }
-#ifndef VTP_P8_FOUR_PHASE
-      // Two phases of 16 MFMAs per k-tile (the schedule in use since round 4: half as many barrier intervals per k-tile as the four
-      // phases of 8 MFMAs below; measured 1-3 % per launch, +0.3 % on the step in three of three same-box repetitions,
-      // profiles/r04_2ph_step_ab.log).  The two wave groups still run one barrier apart.
+      // Two phases of 16 MFMAs per k-tile (since round 4: half as many barrier intervals per k-tile as the earlier four phases of 8
+      // MFMAs; measured 1-3 % per launch, +0.3 % on the step in three of three same-box repetitions, profiles/r04_2ph_step_ab.log).
       // ---- phase A: B-first, A-first, B-second -> quadrants (cols 0..63, rows 0..63); issues A-second of the next k-tile
       load_b(kb, b1);
       load_a(kb + P8_SLOT, a1);
@@ -469,49 +431,6 @@ __device__ __forceinline__ void gemm8p_body(const GemmArgs& p, int bx, int zslic
       }
       seg_barrier();
     }
-#else
-      static_assert(!DYN, "the tile queue is wired into the two-phase schedule only");
-      // ---- phase 0: B-first + A-first -> quadrant (cols 0..31, rows 0..63)
-      load_b(kb, b1);
-      __builtin_amdgcn_sched_barrier(0);
-      load_a(kb + P8_SLOT, a1);
-      __builtin_amdgcn_sched_barrier(0);
-      if (DYN ? !s_stop : s_h < H) issue(I3{});
-      __builtin_amdgcn_sched_barrier(0);
-      // the B-first reads (issued first) are done: phase 1 overwrites that slot (TN: 8 + 16 tr reads, the counter holds 15)
-      if constexpr (!TRANS) asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
-      else asm volatile("s_waitcnt lgkmcnt(15)" ::: "memory");
-      seg_barrier();
-      mma2(acc[0][0], acc[0][1], b1, a1[0], a1[1]);
-      if constexpr (TRANS) {
-        if (do_csum) add_csum(a1, 0);
-      }
-      seg_barrier();
-      // ---- phase 1: B-second -> quadrant (cols 32..63, rows 0..63)
-      load_b(kb + 2 * P8_SLOT, b2);
-      __builtin_amdgcn_sched_barrier(0);
-      if (DYN ? !s_stop : s_h < H) issue(I0{});
-      seg_barrier();
-      mma2(acc[1][0], acc[1][1], b2, a1[0], a1[1]);
-      seg_barrier();
-      // ---- phase 2: A-second -> quadrant (cols 32..63, rows 64..127)
-      load_a(kb + 3 * P8_SLOT, a2);
-      __builtin_amdgcn_sched_barrier(0);
-      if (DYN ? !s_stop : s_h < H) issue(I1{});
-      seg_barrier();
-      mma2(acc[1][2], acc[1][3], b2, a2[0], a2[1]);
-      if constexpr (TRANS) {
-        if (do_csum) add_csum(a2, 2);
-      }
-      seg_barrier();
-      // ---- phase 3: quadrant (cols 0..31, rows 64..127); the next k-tile's four half-tiles must have landed
-      if (DYN ? !s_stop : s_h < H) issue(I2{});
-      p8_wait_vm_halftiles(s_h - 4 * (ktg + 2));
-      seg_barrier();
-      mma2(acc[0][2], acc[0][3], b1, a2[0], a2[1]);
-      seg_barrier();
-    }
-#endif
     if (wr == 0) seg_barrier();  // re-align the groups: both run the epilogue together
     stamp(ti, 1);
     if constexpr (TRANS) {
@@ -594,22 +513,19 @@ __device__ __forceinline__ void gemm8p_body(const GemmArgs& p, int bx, int zslic
     // the ring slot under the staging cursor is free (its half-tile was consumed >= 2 phases ago, the next LDS-DMA into it is issued
     // after this epilogue): the wave's own 2 KiB of it are a second staging region
     char* reg2 = (EPI == EPI_SWIGLU && reg) ? smem + s_dst : nullptr;
-    int d_t = 0;
-    if constexpr (DYN) {  // the tile after next
-      if (d_more && tid == 0) d_t = __hip_atomic_fetch_add(d_head, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    const int d_t = DYN ? tq.draw(d_more, tid) : 0;  // the tile after next
     gemm_epilogue<EPI, TRANS, 128, 64, P8_REGION, XMODE>(p, acc, reg, m0, n0, wr, wc, lane, zslice, reg2);
     stamp(ti, 2);
     zero_acc();
     if constexpr (DYN) {
       d_mail = d_more;
-      if (d_more && tid == 0) *(volatile int*)mbox = d_t < q_n ? q_start + d_t : -1;
+      tq.post(d_more, tid, d_t);
       d_cur = d_next;
       d_next = -1;  // (known at k-tile 1 of the next tile, if a draw is in the mailbox)
       if (d_cur < 0) break;
     }
   }
-  if constexpr (DYN) tq_exit();
+  if constexpr (DYN) tq.leave(tid, G);
 }
 
 // the persistent NT launch with dynamic tile assignment (gemm8p_body<.., DYN = true>): grid = the CU count, one K slice
@@ -627,8 +543,7 @@ __global__ __launch_bounds__(512) void gemm8p_kernel(const GemmArgs p) {
   const bool flat = (p.xcd_swizzle & 4) != 0;
   int bx = blockIdx.x, zslice = blockIdx.z;
   if (flat) {
-    const int W = gridDim.x, q = W >> 3, r = W & 7, x = bx & 7;
-    const int c = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bx >> 3);
+    const int c = xcd_chunk_start(bx, gridDim.x) + (bx >> 3);
     zslice = c / ntiles;
     bx = c - zslice * ntiles;
   }
@@ -643,8 +558,7 @@ __global__ __launch_bounds__(512) void gemm8p_kernel(const GemmArgs p) {
 // (gemm8p_body), which also applies the epilogue (C = C + sum or C = sum, SwiGLU row de-interleave, fused bias-gradient column sums):
 // no slab buffers, no reduce launches, no separate column-sum launches.
 __global__ __launch_bounds__(512) void gemm8p_grouped_tn_kernel(const GroupArgs ga) {
-  const int W = gridDim.x, q = W >> 3, r = W & 7, x = blockIdx.x & 7;
-  const int c = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + ((int)blockIdx.x >> 3);
+  const int c = xcd_chunk_start(blockIdx.x, gridDim.x) + ((int)blockIdx.x >> 3);
   const int zslice = c / ga.ntiles, tile = c - zslice * ga.ntiles;
   int g = 0;
   for (int i = 1; i < ga.nprob; ++i)
@@ -664,86 +578,39 @@ __global__ __launch_bounds__(512) void gemm8p_grouped_tn_kernel(const GroupArgs 
 static unsigned long long* g_p8_timing = nullptr;
 static int g_p8_grid = 0, g_p8_delay = 0;
 
-// scratch of the in-launch split-K combine: launches on one stream are serialised and may share a buffer, concurrent streams (the
-// text tower beside the decoder) must not.  A pool of 8 slots (256 tile-slices x 256 KiB + tickets each) is allocated at the FIRST
-// combine launch of the process -- an eager one: the trainers warm up eagerly before any stream capture, and allocating under
-// capture is not possible -- and every stream handle is bound to a slot the first time it is seen (no allocation then, so a
-// capture stream that shows up later is fine).  No pool (allocation failed, first use under capture) or no free slot (more than 8
-// streams): the dispatcher (vtp_gemm_nt) launches the shape without the K split.
-struct CombineScratch {
-  float* part = nullptr;
-  int* ticket = nullptr;
-};
-static CombineScratch* combine_scratch(hipStream_t s) {
-  constexpr int SLOTS = 8;
-  static std::mutex mu;
-  static CombineScratch pool[SLOTS];
-  static std::unordered_map<hipStream_t, int> slot_of;
-  static bool ready = false, failed = false;
-  std::lock_guard<std::mutex> lock(mu);
-  if (!ready) {
-    if (failed) return nullptr;  // one attempt per process: callers fall back to the unsplit launch
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return nullptr;  // no allocation under capture
-    float* part = nullptr;
-    int* ticket = nullptr;
-    if (hipMalloc((void**)&part, (size_t)SLOTS * 256 * 65536 * sizeof(float)) != hipSuccess) {
-      failed = true;
-      return nullptr;
-    }
-    if (hipMalloc((void**)&ticket, (size_t)SLOTS * 1024 * sizeof(int)) != hipSuccess ||
-        hipMemset(ticket, 0, (size_t)SLOTS * 1024 * sizeof(int)) != hipSuccess) {
-      (void)hipFree(part);
-      if (ticket) (void)hipFree(ticket);
-      failed = true;
-      return nullptr;
-    }
-    for (int i = 0; i < SLOTS; ++i) pool[i] = CombineScratch{part + (size_t)i * 256 * 65536, ticket + i * 1024};
-    ready = true;
-  }
-  auto it = slot_of.find(s);
-  if (it == slot_of.end()) {
-    // a 9th distinct stream would have to share partial sums and tickets with a stream that may run concurrently: refuse
-    if ((int)slot_of.size() >= SLOTS) return nullptr;
-    it = slot_of.emplace(s, (int)slot_of.size()).first;
-  }
-  return &pool[it->second];
-}
-
-// queue words of the dynamic tile assignment (GemmArgs::tq): 256 ints per stream (heads of the 8 per-XCD queues 64 B apart, the exit
-// counter), zero between launches.  Launches on one stream are serialised and share a slot; every stream handle is bound to its own
-// slot the first time it is seen.  The pool (64 slots) is allocated at the first persistent launch outside stream capture (the trainers
-// warm up eagerly); no pool / no free slot: the launch keeps the static tile lists.
-int* gemm_tile_queue(hipStream_t s) {  // (shared with gemm8h.hip: launches on one stream are serialised, whatever the kernel)
-  constexpr int SLOTS = 64;
-  static std::mutex mu;
-  static int* pool = nullptr;
-  static std::unordered_map<hipStream_t, int> slot_of;
-  static bool failed = false;
-  std::lock_guard<std::mutex> lock(mu);
-  if (!pool) {
-    if (failed) return nullptr;
+void* StreamSlotPool::get(hipStream_t s) {
+  std::lock_guard<std::mutex> lock(mu_);
+  if (!base_) {
+    if (failed_) return nullptr;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return nullptr;
-    if (hipMalloc((void**)&pool, (size_t)SLOTS * 256 * sizeof(int)) != hipSuccess || hipMemset(pool, 0, (size_t)SLOTS * 256 * sizeof(int)) != hipSuccess) {
-      pool = nullptr;
-      failed = true;
+    if (hipMalloc((void**)&base_, slots_ * bytes_) != hipSuccess || hipMemset(base_, 0, slots_ * bytes_) != hipSuccess) {
+      if (base_) (void)hipFree(base_);
+      base_ = nullptr;
+      failed_ = true;
       return nullptr;
     }
   }
-  auto it = slot_of.find(s);
-  if (it == slot_of.end()) {
-    if ((int)slot_of.size() >= SLOTS) return nullptr;
-    it = slot_of.emplace(s, (int)slot_of.size()).first;
+  auto it = slot_of_.find(s);
+  if (it == slot_of_.end()) {
+    if ((int)slot_of_.size() >= slots_) return nullptr;  // 
+    it = slot_of_.emplace(s, (int)slot_of_.size()).first;
   }
-  return pool + it->second * 256;
+  return base_ + it->second * bytes_;
 }
+
+// scratch of the in-launch split-K combine, per stream: fp32 partial sums of 256 tile-slices x 256 KiB, then 1024 arrival tickets.  No
+// slot: the dispatcher (vtp_gemm_nt) launches the shape without the K split.
+constexpr size_t COMBINE_PART = (size_t)256 * 65536 * sizeof(float);
+static StreamSlotPool g_combine_pool(8, COMBINE_PART + 1024 * sizeof(int));
+// queue words of the dynamic tile assignment (TileQueue), per stream: 256 ints
+static StreamSlotPool g_tile_queue_pool(64, 256 * sizeof(int));
 
 // dynamic tile assignment of the persistent launches: VTP_GEMM_DYN=0 / 1 in the environment wins; otherwise what vtp_set_gemm_dynamic
 // asked for (the trainers turn it on when they run beside collectives); default off -- on a chip the step has to itself the static
 // lists are 0.4 % faster (no draw at the start of a workgroup, no exit count: 702 vs 699 images/s, profiles/r06_dyn_tiles.log)
 static int g_dyn_mode = 0;
-bool gemm_dyn_enabled() {
+static bool gemm_dyn_enabled() {
   static int env = -2;
   if (env == -2) {
     const char* e = getenv("VTP_GEMM_DYN");
@@ -751,69 +618,62 @@ bool gemm_dyn_enabled() {
   }
   return env >= 0 ? env == 1 : g_dyn_mode == 1;
 }
+
+int gemm_persistent_slots(int per_cu) {
+  static const int cus = [] {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    (void)hipGetDevice(&dev);
+    (void)hipGetDeviceProperties(&prop, dev);
+    const int n = prop.multiProcessorCount - prop.multiProcessorCount % 8;
+    const char* e = getenv("VTP_GEMM_CUS");
+    const int cap = e ? atoi(e) : 0;
+    if (cap >= 8 && cap < n) return cap - cap % 8;
+    return n < 8 ? 8 : n;
+  }();
+  return g_p8_grid > 0 ? g_p8_grid : per_cu * cus;
+}
+
+int* gemm_dyn_queue(const GemmArgs& a, int splits, int ntiles, int slots, int min_ktiles, hipStream_t s) {
+  if (splits != 1 || ntiles <= slots || !(a.xcd_swizzle & 1) || a.timing || slots < 8 || a.K < 64 * min_ktiles || !gemm_dyn_enabled())
+    return nullptr;
+  return (int*)g_tile_queue_pool.get(s);
+}
+
 // may this stream use the in-launch split-K combine?  (allocates the scratch pool at the first call outside stream capture; false:
 // the dispatcher launches the shape unsplit)
-bool gemm8p_combine_ready(hipStream_t s) { return combine_scratch(s) != nullptr; }
+bool gemm8p_combine_ready(hipStream_t s) { return g_combine_pool.get(s) != nullptr; }
 
 template <int EPI, bool TRANS, int VAR = 0, int XMODE = 0>
 static int launch8p(const GemmArgs& a0, int splits, hipStream_t s) {
   GemmArgs a = a0;
   a.timing = g_p8_timing;
   a.dbg_delay = g_p8_delay;
-  if constexpr (EPI != EPI_F32_SLAB && EPI != EPI_F32_ATOMIC) {
-    if (splits > 1) {  // in-launch combine: tiles x splits <= 256 (the caller's policy)
-      CombineScratch* c = combine_scratch(s);
-      if (!c || cdiv(a.M, 256) * cdiv(a.N, 256) * splits > 256) {
+  constexpr auto kern = gemm8p_kernel<EPI, TRANS, VAR, XMODE>;
+  const int ntiles = cdiv(a.M, 256) * cdiv(a.N, 256);
+  if (splits > 1) {
+    if constexpr (EPI != EPI_F32_SLAB && EPI != EPI_F32_ATOMIC) {  // in-launch combine: tiles x splits <= 256 (the caller's policy)
+      char* c = (char*)g_combine_pool.get(s);
+      if (!c || ntiles * splits > 256) {
         set_error("gemm8p: split-K combine scratch unavailable or too many tile slices");
         return VTP_ERR_ARG;
       }
-      a.part = c->part;
-      a.ticket = c->ticket;
+      a.part = (float*)c;
+      a.ticket = (int*)(c + COMBINE_PART);
     }
-  }
-  auto kern = gemm8p_kernel<EPI, TRANS, VAR, XMODE>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, P8_LDS);
-    attr_set = true;
-  }
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    (void)hipGetDevice(&dev);
-    (void)hipGetDeviceProperties(&prop, dev);
-    cus = prop.multiProcessorCount - prop.multiProcessorCount % 8;
-    if (cus < 8) cus = 8;
-  }
-  const int ntiles = cdiv(a.M, 256) * cdiv(a.N, 256);
-  if (splits > 1) {
-    GemmArgs f = a;
-    f.xcd_swizzle |= 4;
-    hipLaunchKernelGGL(kern, dim3(ntiles * splits), dim3(512), P8_LDS, s, f);
+    static bool attr_set = false;
+    if (!attr_set) {
+      hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, P8_LDS);
+      attr_set = true;
+    }
+    a.xcd_swizzle |= 4;
+    hipLaunchKernelGGL(kern, dim3(ntiles * splits), dim3(512), P8_LDS, s, a);
     return check_launch(TRANS ? "gemm8p_tn" : "gemm8p_nt");
   }
-  const int cap = g_p8_grid > 0 ? g_p8_grid : gemm_cu_cap(cus);
-  if constexpr (!TRANS && EPI != EPI_F32_SLAB && EPI != EPI_F32_ATOMIC) {
-    // persistent launch: tiles drawn from per-XCD queues (gemm8p_body DYN) when the shape allows the look-ahead (>= 4 k-tiles per tile)
-    if (splits == 1 && ntiles > cap && a.K >= 256 && (a.xcd_swizzle & 1) && !a.timing && gemm_dyn_enabled()) {
-      int* tq = gemm_tile_queue(s);
-      if (tq) {
-        auto dk = gemm8p_dyn_kernel<EPI, VAR, XMODE>;
-        static bool dattr = false;
-        if (!dattr) {
-          hipFuncSetAttribute((const void*)dk, hipFuncAttributeMaxDynamicSharedMemorySize, P8_LDS);
-          dattr = true;
-        }
-        a.tq = tq;
-        hipLaunchKernelGGL(dk, dim3(cap), dim3(512), P8_LDS, s, a);
-        return check_launch("gemm8p_nt_dyn");
-      }
-    }
-  }
-  dim3 grid(splits == 1 && ntiles > cap ? cap : ntiles, 1, splits);
-  hipLaunchKernelGGL(kern, grid, dim3(512), P8_LDS, s, a);
-  return check_launch(TRANS ? "gemm8p_tn" : "gemm8p_nt");
+  if constexpr (!TRANS && EPI != EPI_F32_SLAB && EPI != EPI_F32_ATOMIC)  // tiles drawn from the queues (gemm8p_body DYN): >= 4 k-tiles
+    return launch_persistent<kern, gemm8p_dyn_kernel<EPI, VAR, XMODE>>(a, ntiles, 1, 512, P8_LDS, 4, s, "gemm8p_nt");
+  else
+    return launch_persistent<kern, nullptr>(a, ntiles, 1, 512, P8_LDS, 4, s, TRANS ? "gemm8p_tn" : "gemm8p_nt");
 }
 
 // the staging addresses are 32-bit byte offsets from the operand bases

@@ -1,7 +1,11 @@
-// Shared pieces of the bf16 MFMA GEMM kernels (gemm.hip: ring / 2-barrier main loops; gemm8p.hip: 256x256 8-phase main loop):
-// the argument block, the row remaps and the fused epilogues.  Device code only.
+// Shared pieces of the bf16 MFMA GEMM kernels (gemm.hip: ring / 2-barrier main loops; gemm8p.hip, gemm8h.hip, gemm4w.hip: the persistent
+// 256x256 / 128x256 NT kernels): the argument block, the XCD-aware tile order, the tile queue and launch policy of the persistent
+// kernels, the row remaps and the fused epilogues.
 #pragma once
 #include <cstdlib>
+#include <mutex>
+#include <type_traits>
+#include <unordered_map>
 #include "common.h"
 #include "vtp_hip.h"
 
@@ -59,22 +63,127 @@ struct GemmArgs {
   int dbg_delay;  // diagnostics: > 0: every second workgroup (per XCD) starts this many 10-ns ticks late (lock-step experiments)
 };
 
-// VTP_GEMM_CUS=n (read once): the persistent kernels launch n workgroup slots instead of one per CU (rounded down to a multiple of 8)
-// -- leaves CUs to a kernel that holds them for the whole backward (RCCL channels at N > 1; INTEGRATION.md "Running beside RCCL")
-static inline int gemm_cu_cap(int cus) {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("VTP_GEMM_CUS");
-    v = e ? atoi(e) : 0;
-    if (v < 0) v = 0;
-  }
-  if (v >= 8 && v < cus) return v - v % 8;
-  return cus;
+// XCD-aware order of an n-entry list (the tiles of a persistent launch, the workgroups of a flat one): workgroups are dealt to the 8
+// XCDs round-robin, and XCD x = i % 8 takes the contiguous chunk of the list that starts here (n / 8 entries; the first n % 8 chunks
+// one more).  (Argument order i, n: with n first hipcc orders one addition the other way round in every caller.)
+__host__ __device__ __forceinline__ int xcd_chunk_start(int i, int n) {
+  const int q = n >> 3, r = n & 7, x = i & 7;
+  return x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q;
 }
 
-#ifndef VTP_EPI_F32_PF
-#define VTP_EPI_F32_PF 1  // residual rows requested this many LDS passes ahead in the staged fp32 epilogue (A/B builds: -DVTP_EPI_F32_PF=1)
-#endif
+// Dynamic tile assignment of the persistent NT kernels (gemm8p, gemm8h, gemm4w): a workgroup does not own the static tiles bx, bx + G,
+// ... but DRAWS them from per-XCD queues in device memory (GemmArgs::tq; queue bx & 7 holds the same contiguous chunk of the tile list
+// as the static XCD-aware order).  A launch that cannot get all of its CUs at once -- an RCCL kernel holds 16 .. 32 of them for the
+// whole backward, or another stream's GEMM is still running -- then ends when the TILES are done, not when the statically-assigned tile
+// list of a late-starting workgroup is (tools/cu_thief.py).  The staging cursors run into the next tile ahead of the MFMAs, so a
+// workgroup holds TWO tiles beyond the one it computes: tiles 0 and 1 come from one blocking fetch_add(2) at the start (first); tile
+// i + 2 is drawn by thread 0 at the START of tile i's epilogue (draw: an ordinary compiler-visible atomic -- the epilogue's own loads
+// drain the vector-memory queue anyway), goes into an LDS mailbox at its END (post) and is taken into an SGPR by every wave (take)
+// before the cursor needs it; where, follows from each kernel's k loop.  (A returning atomic from inline asm inside the k loop was
+// tried first: its destination register is written when the result arrives, long after the statement, and the compiler -- which
+// cannot know -- had meanwhile given the register to something else: memory faults.)  The last workgroup to leave zeroes the queue
+// words.  This is the only code that knows their layout: heads of the 8 queues 16 ints apart, the exit counter at word 128, all zero
+// between launches.
+struct TileQueue {
+  int* words;
+  int* head;     // the queue this workgroup draws from
+  int* mbox;     // LDS mailbox word (the caller's: idle where the protocol uses it)
+  int start, n;  // the queue holds positions [start, start + n) of the tile list
+
+  TileQueue() = default;  // (static-list kernels: unused)
+  __device__ __forceinline__ TileQueue(int* tq, int* mailbox, int ntiles, int bx) : words(tq), head(tq + (bx & 7) * 16), mbox(mailbox) {
+    const int x = bx & 7;
+    n = (ntiles >> 3) + (x < (ntiles & 7) ? 1 : 0);
+    start = xcd_chunk_start(bx, ntiles);
+  }
+  // once per workgroup, behind its last draw: the last one to leave resets the queue words for the next launch
+  __device__ __forceinline__ void leave(int tid, int G) const {
+    if (tid == 0) {
+      const int t = __hip_atomic_fetch_add(words + 128, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (t == G - 1) {
+#pragma unroll
+        for (int x = 0; x < 8; ++x) __hip_atomic_store(words + 16 * x, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(words + 128, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  }
+  // the first two tiles (all threads; two barriers): one draw of two consecutive queue indices j, j + 1 (positions start + j, ...; none at
+  // n or beyond); returns j
+  __device__ __forceinline__ int first(int tid) const {
+    if (tid == 0) *mbox = __hip_atomic_fetch_add(head, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    const int j = __builtin_amdgcn_readfirstlane(*(volatile int*)mbox);
+    __syncthreads();
+    return j;
+  }
+  // thread 0, while the last draw returned a tile (more): the ticket of the tile after next, for post()
+  __device__ __forceinline__ int draw(bool more, int tid) const {
+    int t = 0;
+    if (more && tid == 0) t = __hip_atomic_fetch_add(head, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return t;
+  }
+  __device__ __forceinline__ void post(bool more, int tid, int t) const {  // the drawn tile's position (-1: none) into the mailbox
+    if (more && tid == 0) *(volatile int*)mbox = t < n ? start + t : -1;
+  }
+  __device__ __forceinline__ int take() const { return __builtin_amdgcn_readfirstlane(*(volatile int*)mbox); }
+};
+
+// Per-stream slots of one device buffer: launches on one stream are serialised and may share scratch, concurrent streams (the text tower
+// beside the decoder) must not.  The buffer (zeroed) is allocated at the first call outside stream capture -- the trainers warm up
+// eagerly before any capture, and allocating under capture is not possible -- and every stream handle is bound to its own slot the
+// first time it is seen (no allocation then, so a capture stream that shows up later is fine).
+// Hazard (not handled): a captured kernel node keeps the slot of the stream it was captured on.  A graph replay holding nodes captured
+// on stream S that runs at the same time as an eager launch on S shares S's slot with it, and nothing serialises the two.  The trainers
+// never run eager GEMMs beside their own replays.
+class StreamSlotPool {
+ public:
+  StreamSlotPool(int slots, size_t slot_bytes) : slots_(slots), bytes_(slot_bytes) {}
+  // this stream's slot; null: no buffer (the allocation failed -- tried once per process -- or the first call is under capture) or
+  // every slot is taken (sharing one with a stream that may run concurrently would be wrong)
+  void* get(hipStream_t s);
+
+ private:
+  const int slots_;
+  const size_t bytes_;
+  std::mutex mu_;
+  std::unordered_map<hipStream_t, int> slot_of_;
+  char* base_ = nullptr;
+  bool failed_ = false;
+};
+
+// Launch policy of the persistent NT kernels (gemm8p.hip).  Workgroup slots of a launch with per_cu resident workgroups per CU: the CU
+// count rounded down to a multiple of 8 (at least 8), capped by VTP_GEMM_CUS=n (read once; rounded down to a multiple of 8 -- leaves
+// CUs to a kernel that holds them for the whole backward, RCCL channels at N > 1; INTEGRATION.md "Running beside RCCL"); a
+// vtp_gemm_debug grid limit replaces it.
+int gemm_persistent_slots(int per_cu);
+// May a persistent NT launch draw its tiles (TileQueue)?  Only with one K slice, more tiles than workgroup slots, the XCD-aware order, no
+// timing buffer, >= 8 slots (every queue has a worker), >= min_ktiles k-tiles per tile (the kernel's look-ahead into the next tile),
+// dynamic mode on (gemm_dyn_enabled) and a free queue slot.  Returns the stream's queue words; null: the static tile lists.
+int* gemm_dyn_queue(const GemmArgs& a, int splits, int ntiles, int slots, int min_ktiles, hipStream_t s);
+
+// one persistent NT launch of one K slice: KERN deals the tiles statically over min(ntiles, slots) workgroups, DKERN (nullptr: none)
+// draws them when gemm_dyn_queue allows
+template <auto KERN, auto DKERN>
+int launch_persistent(GemmArgs a, int ntiles, int per_cu, int threads, int lds, int min_ktiles, hipStream_t s, const char* name) {
+  constexpr bool HAS_DYN = !std::is_same_v<decltype(DKERN), std::nullptr_t>;
+  static const bool attr_set = [lds] {
+    (void)hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if constexpr (HAS_DYN) (void)hipFuncSetAttribute((const void*)DKERN, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    return true;
+  }();
+  (void)attr_set;
+  const int slots = gemm_persistent_slots(per_cu);
+  if constexpr (HAS_DYN) {
+    if (int* tq = gemm_dyn_queue(a, 1, ntiles, slots, min_ktiles, s)) {
+      a.tq = tq;
+      hipLaunchKernelGGL(DKERN, dim3(slots), dim3(threads), lds, s, a);
+      return check_launch(name);
+    }
+  }
+  hipLaunchKernelGGL(KERN, dim3(ntiles > slots ? slots : ntiles), dim3(threads), lds, s, a);
+  return check_launch(name);
+}
+
 enum { EPI_BF16 = 0, EPI_F32 = 1, EPI_SWIGLU = 2, EPI_GELU = 3, EPI_F32_ATOMIC = 4, EPI_F32_SLAB = 5, EPI_CONV_RELU = 6,
        EPI_CONV_MASK = 7 };
 
@@ -371,9 +480,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f32x16 (&acc)[W
       // the residual rows of pass k + 1 are requested before pass k goes through LDS (they are then OLDER than pass k's stores in the
       // in-order VMEM queue: waiting for them does not wait for those stores): one HBM round trip per tile is exposed instead of one
       // per pass (the dominant cost of this epilogue at K = 768: 8 dependent round trips per 256x256 tile)
-      // PF passes ahead (round 6: 1 -> 2; with one pass ahead a wave had 4 KiB of residual rows in flight and the tile's NPASS
-      // dependent round trips -- not bandwidth -- set the length of this epilogue: tools/wgrad_timeline.py, 38 us per 256 x 256 tile)
-      constexpr int PF = VTP_EPI_F32_PF;
+      // PF = 1 pass ahead (2 was measured: +-0 on the NT kernels, 3 us slower on the TN epilogue)
+      constexpr int PF = 1;
       f32x4 rv[PF + 1][T];
       auto coords = [&](int pass, int t, int& m, int& n) {
         const int j = pass / (TN / IG), ig = pass % (TN / IG);
