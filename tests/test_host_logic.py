@@ -633,13 +633,12 @@ def test_wgrad_group_item_list_partitions_every_tile():
             assert (slots2, len(items2)) == (2, 216)
 
 
-def test_overlap_defer_issues_in_order_behind_the_next_main_kernel(monkeypatch):
+def test_overlap_defer_queues_side_work_behind_the_next_main_kernel():
     """engine.Overlap.defer: forked side work is queued and issued -- in fork order, exactly once -- by the next run_deferred() (what
-    Stack.backward calls behind a block's first dgrad GEMM) or by a join; VTP_FORK_LATE=0 issues at the fork"""
+    Stack.backward calls behind a block's first dgrad GEMM) or by a join"""
     from vtp_amd import engine
     ov = engine.Overlap()
     log = []
-    monkeypatch.setattr(engine, "FORK_LATE", True)
     ov.defer(lambda: log.append("lane"))
     ov.defer(lambda: log.append("wgrad"))
     assert log == []
@@ -651,6 +650,3 @@ def test_overlap_defer_issues_in_order_behind_the_next_main_kernel(monkeypatch):
     ov.defer(lambda: log.append("late"))
     ov.join()                    # a join may not leave a fork un-issued (no side stream yet: nothing to wait for)
     assert log[-1] == "late" and ov._deferred == []
-    monkeypatch.setattr(engine, "FORK_LATE", False)
-    ov.defer(lambda: log.append("now"))
-    assert log[-1] == "now" and ov._deferred == []

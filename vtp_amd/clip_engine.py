@@ -49,7 +49,7 @@ class TextEngine:
         ops.embed_tokens(ids, st.p("token_embedding.weight"), st.p("positional_embedding"), x0, eot, B, T, D)
         if self.pool in ("first", "last"):  # the kernel wrote the arg-max position of every row; 'first' / 'last' pool a fixed position
             eot.fill_(0 if self.pool == "first" else T - 1)
-        xl = self.stack.forward(ws, x0, B, T, None, 0, train)
+        xl = self.stack.forward(ws, x0, [(B, T, None)], 0, train)
         if self.pool == "none":  # ln_final and the projection over all B * T rows
             xn = ws.get("all_n", (B * T, D), BF)
             stf = ws.get("all_stf", (B * T, 2), F32)
@@ -87,7 +87,7 @@ class TextEngine:
                          ops.NORM_LN)
             OVERLAP.join()
             yield "tail"
-            dx0, _ = yield from self.stack.backward(ws, dx, dx_b, B, T, None, 0)
+            dx0, _ = yield from self.stack.backward(ws, dx, dx_b, [(B, T, None)], 0)
             ops.embed_tokens_bwd(ids, dx0, st.g("token_embedding.weight"), st.g("positional_embedding"), B, T, D)
             OVERLAP.join()
             return
@@ -106,7 +106,7 @@ class TextEngine:
         ops.scatter_rows(d_pooled, eot, dx, dx_b, B, T, D)
         OVERLAP.join()
         yield "tail"
-        dx0, _ = yield from self.stack.backward(ws, dx, dx_b, B, T, None, 0)
+        dx0, _ = yield from self.stack.backward(ws, dx, dx_b, [(B, T, None)], 0)
         ops.embed_tokens_bwd(ids, dx0, st.g("token_embedding.weight"), st.g("positional_embedding"), B, T, D)
         OVERLAP.join()
 

@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -282,12 +282,9 @@ class Overlap:
     # chain's join nodes onto its own queue, and the main chain pays a cross-queue signal (10-20 us of idle chip) on the way in and
     # out of every such node.  Side work is therefore forked where its inputs are ready but ISSUED behind the main stream's next
     # kernel: defer(fn) queues the issue, run_deferred() -- called by Stack.backward behind the first dgrad GEMM of a block, and by
-    # whoever joins -- performs it.  (VTP_FORK_LATE=0: issue at the fork, the order of rounds 2-5.)
+    # whoever joins -- performs it.
     def defer(self, fn):
-        if FORK_LATE:
-            self._deferred.append(fn)
-        else:
-            fn()
+        self._deferred.append(fn)
 
     def run_deferred(self):
         while self._deferred:
@@ -307,23 +304,14 @@ class Overlap:
         return ctx()
 
 
-FORK_LATE = _env_flag("VTP_FORK_LATE")
-# VTP_PE_IN_GROUP=0: the patch-embed weight gradient as its own split-K launches (one set per list item) behind block 0's group
-PE_IN_GROUP = _env_flag("VTP_PE_IN_GROUP")
 OVERLAP = Overlap()
-# Decided by same-box A/B runs of rounds 1-3 and no longer switchable: apply_rope in the qkv GEMM's epilogue, the SwiGLU backward
-# in the w3 dgrad's epilogue, weight gradients as TN GEMMs straight from the activation layouts (no transposed copies, no fp32
-# atomics from the MFMA epilogue: 285 vs 572 images/s), bias-gradient column sums beside (not inside) the per-layer wgrad GEMMs.
-FUSE_SWIGLU_BWD = True
-FUSE_ROPE = True
-# the four weight gradients of a transformer block as ONE grouped launch with the split-K combine and the bias-gradient column
-# sums inside it (ops.WgradGroup), issued one block late so that it runs beside the NEXT block's dgrad / attention kernels
-# (the per-layer path -- one split-K GEMM + slab reduce + column-sum launch per linear layer, beside that layer's dgrad -- is what
-# LayerScale, stochastic depth and tiny token counts use)
-WGRAD_GROUPED = True
-# experiment switch (round 6): VTP_WGRAD_INLINE=1 issues the grouped launch on the main stream (no side stream) -- what the overlap of the
-# dominant kernel with the next block's dgrad chain is worth in the step (0.4 %: a kernel that holds every CU it runs on hides little)
-WGRAD_INLINE = _env_flag("VTP_WGRAD_INLINE", default="0")
+# Decided by same-box A/B runs of rounds 1-3: apply_rope in the qkv GEMM's epilogue, the SwiGLU backward in the w3 dgrad's epilogue,
+# weight gradients as TN GEMMs straight from the activation layouts (no transposed copies, no fp32 atomics from the MFMA epilogue:
+# 285 vs 572 images/s), bias-gradient column sums beside (not inside) the per-layer wgrad GEMMs.  The four weight gradients of a
+# transformer block are ONE grouped launch with the split-K combine and the bias-gradient column sums inside it (ops.WgradGroup),
+# issued one block late so that it runs beside the NEXT block's dgrad / attention kernels (Stack.backward); the per-layer path --
+# one split-K GEMM + slab reduce + column-sum launch per linear layer, beside that layer's dgrad -- is what LayerScale, stochastic
+# depth and tiny token counts use.
 
 
 def linear_bwd(ws: Workspace, tag: str, L, dy_b, x_b, M: int, d_in, *, need_dx: bool = True, dy_remap=(0, 0),
@@ -367,9 +355,6 @@ def linear_bwd(ws: Workspace, tag: str, L, dy_b, x_b, M: int, d_in, *, need_dx: 
         return
     if bias_grad_done:  # the kernel that produced dy_b already accumulated its column sums into the bias gradient
         gb = None
-    if defer is not None:  # grouped weight gradients: record the problem, the caller launches the block's group later
-        assert dy_remap == (0, 0) and x_remap == (0, 0)
-        defer.append(dict(dy=dy_b, x=x_b, gw=gw, gb=gb, N=N, K=K, swiglu_h=swiglu_h))
     c_remap = (-1, swiglu_h) if swiglu_h else (0, 0)
 
     def wgrad():
@@ -387,8 +372,9 @@ def linear_bwd(ws: Workspace, tag: str, L, dy_b, x_b, M: int, d_in, *, need_dx: 
             ops.gemm_tn(dy_b, x_b, slab, ldc2=n_el // 4, epi=EPI_F32_SLAB, splits=St, **kw)
             ops.reduce_slabs(slab, n_el, St, gw, n_el, accumulate=True)
 
-    if defer is not None:
-        pass
+    if defer is not None:  # grouped weight gradients: record the problem, the caller launches the block's group later
+        assert dy_remap == (0, 0) and x_remap == (0, 0)
+        defer.append(dict(dy=dy_b, x=x_b, gw=gw, gb=gb, N=N, K=K, swiglu_h=swiglu_h))
     elif OVERLAP.enabled and need_dx:
         OVERLAP.join()   # previous layer's dW branch is done with the shared T.* scratch (and with its inputs)
         OVERLAP.fork()   # the side stream sees dy_b / x_b complete
@@ -412,6 +398,25 @@ def linear_bwd(ws: Workspace, tag: str, L, dy_b, x_b, M: int, d_in, *, need_dx: 
 # =====================================================================================================================
 class BlockW:
     pass
+
+
+class BlockSaved(NamedTuple):
+    """What the backward of one block reads, kept by the training forward.  attn_in / ffn_in are the inputs of norm1 / norm2: the
+    block input x_in and x_mid in the plain pass, the gathered rows xs1 / xs2 of the kept images under stochastic depth."""
+    attn_in: torch.Tensor   # f32 [M, D]
+    xn1: torch.Tensor       # bf16 [M, D]
+    st1: torch.Tensor       # f32 [M, 2] (mean, rstd)
+    qkv: torch.Tensor       # bf16 [M, 3D] (RoPE applied)
+    o: torch.Tensor         # bf16 [M, D]
+    lse: torch.Tensor       # f32 [M * heads]
+    ffn_in: torch.Tensor    # f32 [M, D]
+    xn2: torch.Tensor       # bf16 [M, D]
+    st2: torch.Tensor       # f32 [M, 2]
+    pre: torch.Tensor       # bf16 [M, 2H] (SwiGLU, 8|8 interleaved) or [M, H] (GELU): the FFN pre-activations
+    hid: torch.Tensor       # bf16 [M, H]
+
+
+ATTN_SCALE = 1.0 / math.sqrt(64.0)  # head_dim 64
 
 
 # parameter names per block style (reference module trees: block.py:159-187 SelfAttentionBlock, block.py:382-399
@@ -607,62 +612,11 @@ class Stack:
         o = (i * 2 + branch) * p["per"] + sum(p["keeps"][:s])
         return p["idx_dev"][o:o + p["keeps"][s]]
 
-    def forward_drop(self, ws: Workspace, x, segs, prefix_tokens: int):
-        """training forward with stochastic depth; `x` (f32 [M, D]) is updated IN PLACE block after block (the branch inputs that
-        backward needs are the gathered compact copies).  segs = [(B_i, N_i, rope_i)]."""
-        D, H, heads = self.D, self.H, self.heads
-        p = self.drop_plan
-        keeps, scales = p["keeps"], p["scales"]
-        self._check_drop_plan(p, segs)
-        csegs = [(k, N, rp) for (B, N, rp), k in zip(segs, keeps)]  # the compact (gathered) list
-        Mc = sum(k * N for k, N, _ in csegs)
-        scale = 1.0 / math.sqrt(64.0)
-        rope_plan = self._rope_plan(ws, csegs, prefix_tokens, Mc) if FUSE_ROPE else None
-        saved_all = []
-        for i, b in enumerate(self.blocks):
-            t = f"{i}.d."
-            xs1, xs2 = ws.get(t + "xs1", (Mc, D), F32), ws.get(t + "xs2", (Mc, D), F32)
-            xn1, st1 = ws.get(t + "xn1", (Mc, D), BF), ws.get(t + "st1", (Mc, 2), F32)
-            qkv, o = ws.get(t + "qkv", (Mc, 3 * D), BF), ws.get(t + "o", (Mc, D), BF)
-            lse = ws.get(t + "lse", (Mc * heads,), F32)
-            xn2, st2 = ws.get(t + "xn2", (Mc, D), BF), ws.get(t + "st2", (Mc, 2), F32)
-            pre, hid = ws.get(t + "x12", (Mc, 2 * H if self.swiglu else H), BF), ws.get(t + "hid", (Mc, H), BF)
-            delta = ws.get("d.delta", (Mc, D), F32)
-            # ---- attention branch on the kept images
-            self._gather(x, segs, csegs, i, 0, xs1, None, 1.0)
-            ops.norm_fwd(xs1, b.n1w, b.n1b, xn1, st1, Mc, D, self.eps, self.kind)
-            if rope_plan is not None:
-                ps, pc = self._plan_tabs(rope_plan, i)
-                ops.gemm_qkv_rope(xn1, b.qkv.w, b.qkv.bias, qkv, Mc, 3 * D, D, rope_plan[0], ps, pc, 2 * D)
-            elif b.qn_w is not None:  # QK normalisation (attention.py:67-68,119-120) on the kept images: projection -> norm -> RoPE below
-                qkv_pre = ws.get(t + "qkv_pre", (Mc, 3 * D), BF)
-                qinv = ws.get(t + "qinv", (Mc, 2 * heads), F32)
-                ops.gemm_nt(xn1, b.qkv.w, qkv_pre, M=Mc, N=3 * D, K=D, bias=b.qkv.bias, epi=EPI_BF16)
-                ops.qk_norm_fwd(qkv_pre, b.qn_w, b.kn_w, qkv, qinv, Mc, D)
-            else:
-                ops.gemm_nt(xn1, b.qkv.w, qkv, M=Mc, N=3 * D, K=D, bias=b.qkv.bias, epi=EPI_BF16)
-            for r0, Bs, Ns, rp in self._rows(csegs):
-                q_s = qkv[r0:r0 + Bs * Ns]
-                if rp is not None and rope_plan is None:
-                    rs, rc = rope_at(rp, i)
-                    ops.rope_qk(q_s, rs, rc, Bs, Ns, heads, prefix_tokens)
-                ops.attn_fwd(q_s, q_s[:, D:], q_s[:, 2 * D:], o[r0:r0 + Bs * Ns], lse[r0 * heads:], Bs, Ns, heads, Ns * 3 * D, 3 * D,
-                             Ns * D, D, scale, self.causal)
-            ops.gemm_nt(o, b.proj.w, delta, M=Mc, N=D, K=D, bias=b.proj.bias, gamma=b.ls1, epi=EPI_F32)
-            self._scatter(delta, x, segs, csegs, i, 0, scales, accumulate=True)  # x_attn = index_add(x, residual, alpha)
-            # ---- FFN branch on an independent subset
-            self._gather(x, segs, csegs, i, 1, xs2, None, 1.0)
-            ops.norm_fwd(xs2, b.n2w, b.n2b, xn2, st2, Mc, D, self.eps, self.kind)
-            if self.swiglu:
-                ops.gemm_nt(xn2, b.w12.w12, hid, M=Mc, N=2 * H, K=D, c2=pre, ldc2=2 * H, bias=b.w12.b12, epi=EPI_SWIGLU)
-            else:  # Mlp FFN (ffn_layer = "mlp", ffn.py:21-48): fc1 -> GELU -> fc2 on the kept images
-                ops.gemm_nt(xn2, b.fc.w, hid, M=Mc, N=H, K=D, c2=pre, ldc2=H, bias=b.fc.bias,
-                            epi=ops.EPI_QUICK_GELU if self.quick_gelu else EPI_GELU)
-            ops.gemm_nt(hid, b.w3.w, delta, M=Mc, N=D, K=H, bias=b.w3.bias, gamma=b.ls2, epi=EPI_F32)
-            self._scatter(delta, x, segs, csegs, i, 1, scales, accumulate=True)
-            saved_all.append((xs1, xn1, st1, qkv, o, lse, xs2, xn2, st2, pre, hid))
-        self.last_saved = saved_all
-        return x
+    def _drop_segs(self, segs):
+        """(the compact list [(kept images, N_i, rope_i)], its row count) of the active plan for a pass over `segs`"""
+        self._check_drop_plan(self.drop_plan, segs)
+        csegs = [(k, N, rp) for (_, N, rp), k in zip(segs, self.drop_plan["keeps"])]
+        return csegs, sum(k * N for k, N, _ in csegs)
 
     def _gather(self, x, segs, csegs, i, branch, dst, dst_b, scale_by_seg):
         D = self.D
@@ -682,58 +636,6 @@ class Stack:
             ops.scatter_image_rows(src[r_c:], self._drop_idx(i, branch, s), x[r_full:], k, N, D, al, accumulate)
             r_full += B * N
             r_c += k * N
-
-    def backward_drop(self, ws: Workspace, dy, segs, prefix_tokens: int, saved):
-        """backward of forward_drop; `dy` (f32 [M, D], gradient of the stack output) is updated IN PLACE into the gradient of the
-        stack input.  Generator (see backward)."""
-        D, H, heads = self.D, self.H, self.heads
-        p = self.drop_plan
-        keeps, scales = p["keeps"], p["scales"]
-        self._check_drop_plan(p, segs)
-        csegs = [(k, N, rp) for (B, N, rp), k in zip(segs, keeps)]
-        Mc = sum(k * N for k, N, _ in csegs)
-        scale = 1.0 / math.sqrt(64.0)
-        dh = ws.get("b.d.dh", (Mc, H), BF)
-        dpre = ws.get("b.d.dx12", (Mc, 2 * H if self.swiglu else H), BF)
-        dxn = ws.get("b.d.dxn", (Mc, D), BF)
-        d_o = ws.get("b.d.do", (Mc, D), BF)
-        dqkv = ws.get("b.d.dqkv", (Mc, 3 * D), BF)
-        delta = ws.get("b.d.delta", (Mc * heads,), F32)
-        gdy_b = ws.get("b.d.gdy_b", (Mc, D), BF)
-        gdy = ws.get("b.d.gdy", (Mc, D), F32)
-        dxc = ws.get("b.d.dxc", (Mc, D), F32)
-        for i in range(self.depth - 1, -1, -1):
-            b = self.blocks[i]
-            xs1, xn1, st1, qkv, o, lse, xs2, xn2, st2, pre, hid = saved[i]
-            # ---- FFN branch: d(delta2) = alpha * dy[kept rows]; the branch-input gradient lands on the same rows
-            self._gather(dy, segs, csegs, i, 1, gdy, gdy_b, scales)
-            linear_bwd(ws, "w3", b.w3, gdy_b, hid, Mc, dh, ls=(b.ls2, b.gls2) if b.ls2 is not None else None)
-            if self.swiglu:
-                ops.swiglu_bwd(dh, pre, dpre, Mc, H)
-                linear_bwd(ws, "w12", None, dpre, xn2, Mc, dxn, N=2 * H, K=D, gw=b.w12.gw1, gb=b.w12.gb1, wT=b.w12.w12T, swiglu_h=H)
-            else:
-                ops.gelu_bwd(dh, pre, dpre, Mc * H, quick=self.quick_gelu)
-                linear_bwd(ws, "fc", b.fc, dpre, xn2, Mc, dxn)
-            ops.norm_bwd(dxn, xs2, b.n2w, st2, gdy, dxc, None, b.gn2w, b.gn2b, Mc, D, self.kind)   # dxc = dy[kept] + norm bwd
-            self._scatter(dxc, dy, segs, csegs, i, 1, 1.0, accumulate=False)
-            # ---- attention branch
-            self._gather(dy, segs, csegs, i, 0, gdy, gdy_b, scales)
-            linear_bwd(ws, "proj", b.proj, gdy_b, o, Mc, d_o, ls=(b.ls1, b.gls1) if b.ls1 is not None else None)
-            for r0, Bs, Ns, rp in self._rows(csegs):
-                r1 = r0 + Bs * Ns
-                q_s, dq_s = qkv[r0:r1], dqkv[r0:r1]
-                ops.attn_bwd(q_s, q_s[:, D:], q_s[:, 2 * D:], o[r0:r1], d_o[r0:r1], lse[r0 * heads:], delta[r0 * heads:], dq_s,
-                             dq_s[:, D:], dq_s[:, 2 * D:], Bs, Ns, heads, Ns * 3 * D, 3 * D, Ns * D, D, scale, self.causal,
-                             rope=None if rp is None else rope_at(rp, i), rope_prefix=prefix_tokens)
-            if b.qn_w is not None:
-                ops.qk_norm_bwd(dqkv, ws.get(f"{i}.d.qkv_pre", (Mc, 3 * D), BF), ws.get(f"{i}.d.qinv", (Mc, 2 * heads), F32), b.qn_w, b.kn_w,
-                                b.g_qn, b.g_kn, Mc, D)
-            linear_bwd(ws, "qkv", b.qkv, dqkv, xn1, Mc, dxn)
-            ops.norm_bwd(dxn, xs1, b.n1w, st1, gdy, dxc, None, b.gn1w, b.gn1b, Mc, D, self.kind)
-            self._scatter(dxc, dy, segs, csegs, i, 0, 1.0, accumulate=False)
-            OVERLAP.join()
-            yield ("block", i)
-        return dy
 
     @staticmethod
     def _rows(segs):
@@ -757,69 +659,143 @@ class Stack:
                 out.append((r0, B, N, rope))
         return out
 
+    # ------------------------------------------------------------------------------------------------ the two half-blocks
+    # Every pass runs them over a branch input of M rows: the full residual in the plain pass (the output then adds back through the
+    # fused resid= epilogue), the gathered rows of the kept images under stochastic depth (the output goes to `delta`, which the
+    # caller scatters back with alpha).  `t` prefixes the workspace keys of what the branch keeps for the backward.
+    def _attention(self, qkv, o, lse, rows, i: int, prefix_tokens: int, rope_qk: bool):
+        """per-segment RoPE (unless the qkv projection applied it: rope_qk False) + attention over qkv [M, 3D] -> o [M, D]"""
+        D, heads = self.D, self.heads
+        for r0, Bs, Ns, rp in rows:
+            q_s, o_s = qkv[r0:r0 + Bs * Ns], o[r0:r0 + Bs * Ns]
+            if rp is not None and rope_qk:
+                rs, rc = rope_at(rp, i)
+                ops.rope_qk(q_s, rs, rc, Bs, Ns, heads, prefix_tokens)
+            ops.attn_fwd(q_s, q_s[:, D:], q_s[:, 2 * D:], o_s, lse[r0 * heads:], Bs, Ns, heads, Ns * 3 * D, 3 * D, Ns * D, D,
+                         ATTN_SCALE, self.causal)
+
+    def _attn_fwd(self, ws: Workspace, t: str, i: int, x, out, resid, M: int, rows, prefix_tokens: int, rope_plan):
+        """out = (resid +) proj(attn(rope(qkv(norm1(x)))));  returns (xn1, st1, qkv, o, lse)"""
+        D, heads, b = self.D, self.heads, self.blocks[i]
+        xn1, st1 = ws.get(t + "xn1", (M, D), BF), ws.get(t + "st1", (M, 2), F32)
+        qkv, o = ws.get(t + "qkv", (M, 3 * D), BF), ws.get(t + "o", (M, D), BF)
+        lse = ws.get(t + "lse", (M * heads,), F32)  # per segment [B_i, heads, N_i]
+        ops.norm_fwd(x, b.n1w, b.n1b, xn1, st1, M, D, self.eps, self.kind)
+        if rope_plan is not None:  # apply_rope rides in the epilogue of the qkv projection (all segments, one launch)
+            ps, pc = self._plan_tabs(rope_plan, i)
+            ops.gemm_qkv_rope(xn1, b.qkv.w, b.qkv.bias, qkv, M, 3 * D, D, rope_plan[0], ps, pc, 2 * D)
+        elif b.qn_w is not None:  # projection -> QK norm (attention.py:67-68,119-120; pre-norm values and 1/rms kept) -> RoPE below
+            qkv_pre = ws.get(t + "qkv_pre", (M, 3 * D), BF)
+            qinv = ws.get(t + "qinv", (M, 2 * heads), F32)
+            ops.gemm_nt(xn1, b.qkv.w, qkv_pre, M=M, N=3 * D, K=D, bias=b.qkv.bias, epi=EPI_BF16)
+            ops.qk_norm_fwd(qkv_pre, b.qn_w, b.kn_w, qkv, qinv, M, D)
+        else:
+            ops.gemm_nt(xn1, b.qkv.w, qkv, M=M, N=3 * D, K=D, bias=b.qkv.bias, epi=EPI_BF16)
+        self._attention(qkv, o, lse, rows, i, prefix_tokens, rope_plan is None)
+        ops.gemm_nt(o, b.proj.w, out, M=M, N=D, K=D, bias=b.proj.bias, gamma=b.ls1, resid=resid, epi=EPI_F32)
+        return xn1, st1, qkv, o, lse
+
+    def _ffn_fwd(self, ws: Workspace, t: str, i: int, x, out, resid, M: int, train: bool):
+        """out = (resid +) w3(act(w12 / fc(norm2(x))));  returns (xn2, st2, pre, hid) -- pre (the FFN pre-activations) only in training"""
+        D, H, b = self.D, self.H, self.blocks[i]
+        xn2, st2 = ws.get(t + "xn2", (M, D), BF), ws.get(t + "st2", (M, 2), F32)
+        pre = ws.get(t + "x12", (M, 2 * H if self.swiglu else H), BF) if train else None
+        hid = ws.get(t + "hid", (M, H), BF)
+        ops.norm_fwd(x, b.n2w, b.n2b, xn2, st2, M, D, self.eps, self.kind)
+        if self.swiglu:
+            ops.gemm_nt(xn2, b.w12.w12, hid, M=M, N=2 * H, K=D, c2=pre, ldc2=2 * H, bias=b.w12.b12, epi=EPI_SWIGLU)
+        else:  # Mlp FFN (ffn_layer = "mlp", ffn.py:21-48; the text tower's c_fc / c_proj): fc1 -> GELU -> fc2
+            ops.gemm_nt(xn2, b.fc.w, hid, M=M, N=H, K=D, c2=pre, ldc2=H, bias=b.fc.bias,
+                        epi=ops.EPI_QUICK_GELU if self.quick_gelu else EPI_GELU)
+        ops.gemm_nt(hid, b.w3.w, out, M=M, N=D, K=H, bias=b.w3.bias, gamma=b.ls2, resid=resid, epi=EPI_F32)
+        return xn2, st2, pre, hid
+
+    def _ffn_bwd(self, ws: Workspace, i: int, s: BlockSaved, dy, dy_b, dx, dx_b, M: int, bt: str, dpre, *, fused: bool,
+                 bias_done: bool = False, probs=None, dx_colsum=None):
+        """dy / dy_b: gradient of the FFN branch output (f32 / bf16 copy); dx (+ dx_b) = dy + the gradient through the branch into its
+        input.  fused: the SwiGLU backward rides in the w3 dgrad's epilogue.  probs: collects the grouped weight-gradient problems."""
+        D, H, b = self.D, self.H, self.blocks[i]
+        dh, dxn = ws.get(bt + "dh", (M, H), BF), ws.get(bt + "dxn", (M, D), BF)
+        linear_bwd(ws, "w3", b.w3, dy_b, s.hid, M, dpre if fused else dh, bias_grad_done=bias_done,
+                   ls=(b.ls2, b.gls2) if b.ls2 is not None else None, dgrad_swiglu=s.pre if fused else None, defer=probs)
+        OVERLAP.run_deferred()  # side work forked at the block boundary: behind the block's first main-stream kernel
+        if self.swiglu:
+            if not fused:
+                ops.swiglu_bwd(dh, s.pre, dpre, M, H)
+            linear_bwd(ws, "w12", None, dpre, s.xn2, M, dxn, N=2 * H, K=D, gw=b.w12.gw1, gb=b.w12.gb1, wT=b.w12.w12T, swiglu_h=H,
+                       defer=probs)
+        else:
+            ops.gelu_bwd(dh, s.pre, dpre, M * H, quick=self.quick_gelu)
+            linear_bwd(ws, "fc", b.fc, dpre, s.xn2, M, dxn, defer=probs)
+        ops.norm_bwd(dxn, s.ffn_in, b.n2w, s.st2, dy, dx, dx_b, b.gn2w, b.gn2b, M, D, self.kind, dx_colsum=dx_colsum)
+
+    def _attn_bwd(self, ws: Workspace, t: str, i: int, s: BlockSaved, dy, dy_b, dx, dx_b, M: int, bt: str, dqkv, rows,
+                  prefix_tokens: int, *, bias_done: bool = False, probs=None, join: bool = False, dx_colsum=None):
+        """_ffn_bwd of the attention branch.  join: wait for the side stream before norm1's backward (which overwrites the dy
+        operand of the previous block's grouped weight gradients)"""
+        D, heads, b = self.D, self.heads, self.blocks[i]
+        d_o, dxn = ws.get(bt + "do", (M, D), BF), ws.get(bt + "dxn", (M, D), BF)
+        delta = ws.get(bt + "delta", (M * heads,), F32)
+        linear_bwd(ws, "proj", b.proj, dy_b, s.o, M, d_o, bias_grad_done=bias_done, ls=(b.ls1, b.gls1) if b.ls1 is not None else None,
+                   defer=probs)
+        for r0, Bs, Ns, rp in rows:
+            r1 = r0 + Bs * Ns
+            q_s, dq_s = s.qkv[r0:r1], dqkv[r0:r1]
+            # dq / dk come back as gradients w.r.t. the un-rotated q, k (inverse RoPE fused into the attention backward)
+            ops.attn_bwd(q_s, q_s[:, D:], q_s[:, 2 * D:], s.o[r0:r1], d_o[r0:r1], s.lse[r0 * heads:], delta[r0 * heads:], dq_s,
+                         dq_s[:, D:], dq_s[:, 2 * D:], Bs, Ns, heads, Ns * 3 * D, 3 * D, Ns * D, D, ATTN_SCALE, self.causal,
+                         rope=None if rp is None else rope_at(rp, i), rope_prefix=prefix_tokens)
+        if b.qn_w is not None:  # gradient w.r.t. the normalised q, k -> w.r.t. the projection output (in place), + dw
+            ops.qk_norm_bwd(dqkv, ws.get(t + "qkv_pre", (M, 3 * D), BF), ws.get(t + "qinv", (M, 2 * heads), F32), b.qn_w, b.kn_w,
+                            b.g_qn, b.g_kn, M, D)
+        linear_bwd(ws, "qkv", b.qkv, dqkv, s.xn1, M, dxn, defer=probs)
+        if join:
+            OVERLAP.join()
+        ops.norm_bwd(dxn, s.attn_in, b.n1w, s.st1, dy, dx, dx_b, b.gn1w, b.gn1b, M, D, self.kind, dx_colsum=dx_colsum)
+
     # x: f32 [M, D] input residual.  Returns the output residual (f32 [M, D]).
-    def forward(self, ws: Workspace, x, B: int, N: int, rope, prefix_tokens: int, train: bool, segs=None):
+    def forward(self, ws: Workspace, x, segs, prefix_tokens: int, train: bool):
         """`segs` = [(B_i, N_i, rope_i)]: several batches of different sequence length concatenated along the token-row
         axis (the reference's list path, block.py:235-298 / utils.py:14-25 cat_keep_shapes): every linear / norm runs once
-        over all rows, RoPE and attention run per segment on its row range."""
-        D, H, heads = self.D, self.H, self.heads
-        segs = [(B, N, rope)] if segs is None else segs
+        over all rows, RoPE and attention run per segment on its row range.  In training with a drop plan set (stochastic depth)
+        `x` is updated IN PLACE block after block and each branch runs on the gathered rows of its kept images."""
+        D = self.D
         M = sum(b * n for b, n, _ in segs)
-        scale = 1.0 / math.sqrt(64.0)
-        vit = self.swiglu  # (FFN kind; RoPE / naming follow self.style)
         fp8 = getattr(self, "fp8", None)
         if fp8 is not None and fp8["ready"] and not train:
-            return self.forward_fp8(ws, x, segs, prefix_tokens, M)
+            return self._forward_fp8(ws, x, segs, prefix_tokens, M)
         calib = fp8["amax"] if (fp8 is not None and not fp8["ready"] and not train) else None
+        drop = train and self.drop_plan is not None
+        if drop:
+            csegs, Mb = self._drop_segs(segs)
+            rows, scales = list(self._rows(csegs)), self.drop_plan["scales"]
+        else:
+            csegs, Mb, rows = segs, M, self._attn_rows(segs)
+        rope_plan = self._rope_plan(ws, csegs, prefix_tokens, Mb)
         saved_all = []
-        rope_plan = self._rope_plan(ws, segs, prefix_tokens, M) if FUSE_ROPE else None
-        for i, b in enumerate(self.blocks):
-            t = f"{i}." if train else ""
-            xn1 = ws.get(t + "xn1", (M, D), BF)
-            st1 = ws.get(t + "st1", (M, 2), F32)
-            qkv = ws.get(t + "qkv", (M, 3 * D), BF)
-            o = ws.get(t + "o", (M, D), BF)
-            lse = ws.get(t + "lse", (M * heads,), F32)  # per segment [B_i, heads, N_i]
-            xmid = ws.get(t + "xmid", (M, D), F32)
-            xn2 = ws.get(t + "xn2", (M, D), BF)
-            st2 = ws.get(t + "st2", (M, 2), F32)
-            pre = ws.get(t + "x12", (M, 2 * H if vit else H), BF) if train else None  # FFN pre-activations
-            hid = ws.get(t + "hid", (M, H), BF)
-            xout = ws.get((f"{i}.xout" if train else f"xout{i & 1}"), (M, D), F32)
-            x_in = x  # block input (previous block's xout buffer) is kept for norm1 backward
-
-            ops.norm_fwd(x, b.n1w, b.n1b, xn1, st1, M, D, self.eps, self.kind)
-            if rope_plan is not None:  # apply_rope rides in the epilogue of the qkv projection (all segments, one launch)
-                ps, pc = self._plan_tabs(rope_plan, i)
-                ops.gemm_qkv_rope(xn1, b.qkv.w, b.qkv.bias, qkv, M, 3 * D, D, rope_plan[0], ps, pc, 2 * D)
-            elif b.qn_w is not None:  # projection -> QK norm (pre-norm values and 1/rms kept for the backward) -> RoPE below
-                qkv_pre = ws.get(t + "qkv_pre", (M, 3 * D), BF)
-                qinv = ws.get(t + "qinv", (M, 2 * heads), F32)
-                ops.gemm_nt(xn1, b.qkv.w, qkv_pre, M=M, N=3 * D, K=D, bias=b.qkv.bias, epi=EPI_BF16)
-                ops.qk_norm_fwd(qkv_pre, b.qn_w, b.kn_w, qkv, qinv, M, D)
+        for i in range(self.depth):
+            if drop:
+                t = f"{i}.d."
+                x1, x2 = ws.get(t + "xs1", (Mb, D), F32), ws.get(t + "xs2", (Mb, D), F32)
+                delta = ws.get("d.delta", (Mb, D), F32)
+                self._gather(x, segs, csegs, i, 0, x1, None, 1.0)
+                a = self._attn_fwd(ws, t, i, x1, delta, None, Mb, rows, prefix_tokens, rope_plan)
+                self._scatter(delta, x, segs, csegs, i, 0, scales, accumulate=True)  # x_attn = index_add(x, residual, alpha)
+                self._gather(x, segs, csegs, i, 1, x2, None, 1.0)  # the FFN branch on an independent subset
+                f = self._ffn_fwd(ws, t, i, x2, delta, None, Mb, True)
+                self._scatter(delta, x, segs, csegs, i, 1, scales, accumulate=True)
             else:
-                ops.gemm_nt(xn1, b.qkv.w, qkv, M=M, N=3 * D, K=D, bias=b.qkv.bias, epi=EPI_BF16)
-            for r0, Bs, Ns, rp in self._attn_rows(segs):
-                q_s, o_s = qkv[r0:r0 + Bs * Ns], o[r0:r0 + Bs * Ns]
-                if rp is not None and rope_plan is None:
-                    rs, rc = rope_at(rp, i)
-                    ops.rope_qk(q_s, rs, rc, Bs, Ns, heads, prefix_tokens)
-                ops.attn_fwd(q_s, q_s[:, D:], q_s[:, 2 * D:], o_s, lse[r0 * heads:], Bs, Ns, heads, Ns * 3 * D, 3 * D, Ns * D, D,
-                             scale, self.causal)
-            ops.gemm_nt(o, b.proj.w, xmid, M=M, N=D, K=D, bias=b.proj.bias, gamma=b.ls1, resid=x, epi=EPI_F32)
-            ops.norm_fwd(xmid, b.n2w, b.n2b, xn2, st2, M, D, self.eps, self.kind)
-            if vit:
-                ops.gemm_nt(xn2, b.w12.w12, hid, M=M, N=2 * H, K=D, c2=pre, ldc2=2 * H, bias=b.w12.b12, epi=EPI_SWIGLU)
-            else:
-                ops.gemm_nt(xn2, b.fc.w, hid, M=M, N=H, K=D, c2=pre, ldc2=H, bias=b.fc.bias,
-                            epi=ops.EPI_QUICK_GELU if self.quick_gelu else EPI_GELU)
-            ops.gemm_nt(hid, b.w3.w, xout, M=M, N=D, K=H, bias=b.w3.bias, gamma=b.ls2, resid=xmid, epi=EPI_F32)
-            if calib is not None:  # fp8 calibration pass: amax of the four GEMM inputs of this block
-                for j, tns in enumerate((xn1, o, xn2, hid)):
-                    ops.amax(tns, calib[i, j:j + 1])
+                t = f"{i}." if train else ""
+                x1, x2 = x, ws.get(t + "xmid", (M, D), F32)  # the block input (previous block's xout) is kept for norm1 backward
+                xout = ws.get((f"{i}.xout" if train else f"xout{i & 1}"), (M, D), F32)
+                a = self._attn_fwd(ws, t, i, x1, x2, x1, M, rows, prefix_tokens, rope_plan)
+                f = self._ffn_fwd(ws, t, i, x2, xout, x2, M, train)
+                if calib is not None:  # fp8 calibration pass: amax of the four GEMM inputs of this block
+                    for j, tns in enumerate((a[0], a[3], f[0], f[3])):
+                        ops.amax(tns, calib[i, j:j + 1])
+                x = xout
             if train:
-                saved_all.append((x_in, xn1, st1, qkv, o, lse, xmid, xn2, st2, pre, hid))
-            x = xout
+                saved_all.append(BlockSaved(x1, *a, x2, *f))
         self.last_saved = saved_all  # per-call context: several forward passes may be in flight before their backward
         return x
 
@@ -850,36 +826,31 @@ class Stack:
             f["alpha"].append(al)
         f["ready"] = True
 
-    def forward_fp8(self, ws: Workspace, x, segs, prefix_tokens: int, M: int):
+    def _forward_fp8(self, ws: Workspace, x, segs, prefix_tokens: int, M: int):
         """Stack.forward(train=False) with the four linear maps of every block on the fp8 MFMA path: norm / attention / SwiGLU
         outputs are quantised (one extra row pass each) and multiplied against e4m3 weights; accumulation, bias, residual and
         the attention itself are unchanged (fp32 / bf16)."""
         D, H, heads, f = self.D, self.H, self.heads, self.fp8
-        scale = 1.0 / math.sqrt(64.0)
         a8 = ws.get("f8.a", (M, max(D, H)), torch.uint8)
         qkv = ws.get("qkv", (M, 3 * D), BF)
         o = ws.get("o", (M, D), BF)
         lse = ws.get("lse", (M * heads,), F32)
         xmid = ws.get("xmid", (M, D), F32)
         hid = ws.get("hid", (M, H), BF)
-        rope_plan = self._rope_plan(ws, segs, prefix_tokens, M) if FUSE_ROPE else None
+        rope_plan = self._rope_plan(ws, segs, prefix_tokens, M)
         rope_arg = None if rope_plan is None else (rope_plan[0], rope_plan[1], rope_plan[2], 2 * D)
+        rows = self._attn_rows(segs)
         for i, b in enumerate(self.blocks):
             w8, al, sc = f["w"][i], f["alpha"][i], f["act_scale"][i]
             xout = ws.get(f"xout{i & 1}", (M, D), F32)
             ops.norm_fwd_e4m3(x, b.n1w, b.n1b, a8, sc[0:1], None, M, D, self.eps, self.kind)  # norm + quantise in one pass
-            if b.qn_w is not None:  # QK normalisation (round 5): e4m3 projection -> bf16 pre-norm q, k -> RMSNorm(head_dim) -> RoPE below
+            if b.qn_w is not None:  # QK normalisation: e4m3 projection -> bf16 pre-norm q, k -> RMSNorm(head_dim) -> RoPE below
                 qkv_pre = ws.get("f8.qkv_pre", (M, 3 * D), BF)
                 ops.gemm_nt_fp8(a8, w8[0], qkv_pre, M=M, N=3 * D, K=D, alpha=al[0], bias=b.qkv.bias, epi=EPI_BF16)
                 ops.qk_norm_fwd(qkv_pre, b.qn_w, b.kn_w, qkv, ws.get("f8.qinv", (M, 2 * heads), F32), M, D)
             else:
                 ops.gemm_nt_fp8(a8, w8[0], qkv, M=M, N=3 * D, K=D, alpha=al[0], bias=b.qkv.bias, epi=EPI_BF16, rope=rope_arg)
-            for r0, Bs, Ns, rp in self._attn_rows(segs):
-                q_s, o_s = qkv[r0:r0 + Bs * Ns], o[r0:r0 + Bs * Ns]
-                if rp is not None and rope_arg is None:
-                    ops.rope_qk(q_s, rp[0], rp[1], Bs, Ns, heads, prefix_tokens)
-                ops.attn_fwd(q_s, q_s[:, D:], q_s[:, 2 * D:], o_s, lse[r0 * heads:], Bs, Ns, heads, Ns * 3 * D, 3 * D, Ns * D, D,
-                             scale, self.causal)
+            self._attention(qkv, o, lse, rows, i, prefix_tokens, rope_arg is None)
             ops.quantize_e4m3(o, a8, sc[1:2])
             ops.gemm_nt_fp8(a8, w8[1], xmid, M=M, N=D, K=D, alpha=al[1], bias=b.proj.bias, resid=x, epi=EPI_F32)
             ops.norm_fwd_e4m3(xmid, b.n2w, b.n2b, a8, sc[2:3], None, M, D, self.eps, self.kind)
@@ -897,36 +868,36 @@ class Stack:
         return b.w3.gb if (b.ls2 is None and self.drop_plan is None) else None
 
     # dy: f32 [M,D] grad of the stack output, dy_b: its bf16 copy.  Returns (dx f32, dx bf16) for the stack input.
-    def dx_buffers(self, ws: Workspace, M: int):
-        """(f32, bf16) buffers backward() returns the stack-input gradient in (block 0's outputs; static like every workspace buffer)"""
-        return ws.get("b.dx0", (M, self.D), F32), ws.get("b.dx_b0", (M, self.D), BF)
-
-    def backward(self, ws: Workspace, dy, dy_b, B: int, N: int, rope, prefix_tokens: int, saved=None, segs=None,
-                 dy_colsum_done: bool = False, hold_last: bool = False, extra_last=None):
-        """hold_last (grouped weight gradients only): block 0's group is neither launched nor announced here but left in self.held =
-        (0, group) -- the caller launches it and yields ("block", 0) -- and extra_last, a list of linear_bwd-style problem records over the
-        same token rows (TrunkEngine: the patch-embed weight gradient, whose dy is this stack's input gradient), rides in that launch.
-        Generator: yields ("block", i) each time all parameter gradients of block i have been enqueued (a
-        gradient-bucket / graph-segment boundary for the trainer); returns (dx f32, dx bf16) of the stack input.
+    def backward(self, ws: Workspace, dy, dy_b, segs, prefix_tokens: int, saved=None, dy_colsum_done: bool = False,
+                 hold_last: bool = False, extra_last=None):
+        """Generator: yields ("block", i) each time all parameter gradients of block i have been enqueued (a gradient-bucket /
+        graph-segment boundary for the trainer); returns (dx f32, dx bf16) of the stack input.  With a drop plan set (the forward
+        ran with stochastic depth) `dy` is updated IN PLACE into that gradient and dy_b receives its bf16 copy.
         dy_colsum_done: the caller's norm backward already summed dy_b's columns into the last block's w3 bias gradient
-        (self.blocks[-1].w3.gb as its dx_colsum)."""
-        D, H, heads = self.D, self.H, self.heads
-        segs = [(B, N, rope)] if segs is None else segs
+        (self.blocks[-1].w3.gb as its dx_colsum).
+        hold_last (grouped weight gradients only): block 0's group is neither launched nor announced here but left in self.held =
+        (0, group) -- the caller launches it and yields ("block", 0) -- and extra_last, a list of problem records {x, gw, gb, N, K,
+        swiglu_h} over the same token rows whose dy is this stack's input gradient (TrunkEngine: the patch-embed weight gradient),
+        rides in that launch."""
+        D, H = self.D, self.H
         M = sum(b * n for b, n, _ in segs)
-        scale = 1.0 / math.sqrt(64.0)
-        vit = self.swiglu  # (FFN kind)
+        saved = self.last_saved if saved is None else saved
+        drop = self.drop_plan is not None
+        if drop:
+            csegs, Mb = self._drop_segs(segs)
+            rows, scales, bt = list(self._rows(csegs)), self.drop_plan["scales"], "b.d."
+            gdy, gdy_b = ws.get(bt + "gdy", (Mb, D), F32), ws.get(bt + "gdy_b", (Mb, D), BF)
+            dxc = ws.get(bt + "dxc", (Mb, D), F32)
+        else:
+            Mb, rows, bt = M, self._attn_rows(segs), "b."
+            dmid = ws.get("b.dmid", (M, D), F32)
         # grouped weight gradients: the four dW of block i are ONE launch (split-K combine and bias-gradient column sums inside
         # it), issued at the start of block i - 1's backward so that it overlaps that block's dgrad / attention kernels; the dy
-        # operands it reads (dpre, dmid_b, dqkv; dy_b already alternates) are therefore double-buffered by block parity
-        grouped = WGRAD_GROUPED and M >= 256 and all(b.ls1 is None and b.ls2 is None for b in self.blocks) \
-            and ops.wgrad_group_fits(M, max(3 * D, 2 * H if vit else H)) and D % 8 == 0 and H % 8 == 0  # else: per-layer launches (ring-kernel fallback inside)
+        # operands it reads (dpre, dmid_b, dqkv; dy_b already alternates) are therefore double-buffered by block parity.  LayerScale,
+        # stochastic depth and small token counts take the per-layer launches (ring-kernel fallback inside).
+        grouped = not drop and M >= 256 and all(b.ls1 is None and b.ls2 is None for b in self.blocks) \
+            and ops.wgrad_group_fits(M, max(3 * D, 2 * H if self.swiglu else H)) and D % 8 == 0 and H % 8 == 0
         par = (lambda i: f".{i & 1}") if grouped else (lambda i: "")
-        dh = ws.get("b.dh", (M, H), BF)
-        d_o = ws.get("b.do", (M, D), BF)
-        dxn = ws.get("b.dxn", (M, D), BF)
-        delta = ws.get("b.delta", (M * heads,), F32)
-        dmid = ws.get("b.dmid", (M, D), F32)
-        saved = self.last_saved if saved is None else saved
         groups = ws.__dict__.setdefault("_wgrad_groups", {})
         scratch = self.__dict__.setdefault("_wgrad_scratch", {})
         pending = None  # (block index, ops.WgradGroup) whose launch is due
@@ -936,7 +907,7 @@ class Stack:
             issued behind this block's first main-stream kernel (Overlap.defer)"""
             if pending is None:
                 return
-            if OVERLAP.enabled and not WGRAD_INLINE:
+            if OVERLAP.enabled:
                 OVERLAP.fork()
                 side, grp = OVERLAP.side, pending[1]
 
@@ -948,70 +919,55 @@ class Stack:
                 pending[1].launch()
 
         for i in range(self.depth - 1, -1, -1):
-            b = self.blocks[i]
-            x_in, xn1, st1, qkv, o, lse, xmid, xn2, st2, pre, hid = saved[i]
+            b, s = self.blocks[i], saved[i]
+            t = f"{i}.d." if drop else f"{i}."
+            dpre = ws.get(bt + "dx12" + par(i), (Mb, 2 * H if self.swiglu else H), BF)
+            dqkv = ws.get(bt + "dqkv" + par(i), (Mb, 3 * D), BF)
+            if drop:
+                # each branch: d(delta) = alpha * dy[kept rows]; the branch-input gradient lands on the same rows
+                self._gather(dy, segs, csegs, i, 1, gdy, gdy_b, scales)
+                self._ffn_bwd(ws, i, s, gdy, gdy_b, dxc, None, Mb, bt, dpre, fused=False)
+                self._scatter(dxc, dy, segs, csegs, i, 1, 1.0, accumulate=False)
+                self._gather(dy, segs, csegs, i, 0, gdy, gdy_b, scales)
+                self._attn_bwd(ws, t, i, s, gdy, gdy_b, dxc, None, Mb, bt, dqkv, rows, prefix_tokens)
+                self._scatter(dxc, dy, segs, csegs, i, 0, 1.0, accumulate=False)
+                OVERLAP.join()
+                yield ("block", i)
+                continue
             dxo = ws.get(f"b.dx{i & 1}", (M, D), F32)
             dxo_b = ws.get(f"b.dx_b{i & 1}", (M, D), BF)
-            dpre = ws.get("b.dx12" + par(i), (M, 2 * H if vit else H), BF)
             dmid_b = ws.get("b.dmid_b" + par(i), (M, D), BF)
-            dqkv = ws.get("b.dqkv" + par(i), (M, 3 * D), BF)
             probs = [] if grouped else None
             if grouped:
                 launch_pending()  # dW of block i + 1, beside this block's kernels
-            # ---- FFN: x_out = x_mid + w3(act(...))
-            fused_act = vit and FUSE_SWIGLU_BWD and b.ls2 is None
-            linear_bwd(ws, "w3", b.w3, dy_b, hid, M, dpre if fused_act else dh,
-                       bias_grad_done=dy_colsum_done if i == self.depth - 1 else self.w3_colsum_target(i) is not None,
-                       ls=(b.ls2, b.gls2) if b.ls2 is not None else None, dgrad_swiglu=pre if fused_act else None, defer=probs)
-            OVERLAP.run_deferred()  # side work forked at the block boundary: behind the block's first main-stream kernel
-            if vit:
-                if not fused_act:
-                    ops.swiglu_bwd(dh, pre, dpre, M, H)
-                linear_bwd(ws, "w12", None, dpre, xn2, M, dxn, N=2 * H, K=D, gw=b.w12.gw1, gb=b.w12.gb1, wT=b.w12.w12T,
-                           swiglu_h=H, defer=probs)
-            else:
-                ops.gelu_bwd(dh, pre, dpre, M * H, quick=self.quick_gelu)
-                linear_bwd(ws, "fc", b.fc, dpre, xn2, M, dxn, defer=probs)
             # the norm backward kernels also sum the columns of their bf16 output = the bias gradient of the linear layer that
-            # takes it as dy (proj here; the previous block's w3 below)
-            ops.norm_bwd(dxn, xmid, b.n2w, st2, dy, dmid, dmid_b, b.gn2w, b.gn2b, M, D, self.kind,
-                         dx_colsum=b.proj.gb if b.ls1 is None else None)
-            # ---- attention: x_mid = x_in + proj(attn(rope(qkv(xn1))))
-            linear_bwd(ws, "proj", b.proj, dmid_b, o, M, d_o, bias_grad_done=b.proj.gb is not None,
-                       ls=(b.ls1, b.gls1) if b.ls1 is not None else None, defer=probs)
-            for r0, Bs, Ns, rp in self._attn_rows(segs):
-                r1 = r0 + Bs * Ns
-                q_s, dq_s = qkv[r0:r1], dqkv[r0:r1]
-                # dq / dk come back as gradients w.r.t. the un-rotated q, k (inverse RoPE fused into the attention backward)
-                ops.attn_bwd(q_s, q_s[:, D:], q_s[:, 2 * D:], o[r0:r1], d_o[r0:r1], lse[r0 * heads:], delta[r0 * heads:], dq_s,
-                             dq_s[:, D:], dq_s[:, 2 * D:], Bs, Ns, heads, Ns * 3 * D, 3 * D, Ns * D, D, scale, self.causal,
-                             rope=None if rp is None else rope_at(rp, i), rope_prefix=prefix_tokens)
-            if b.qn_w is not None:  # gradient w.r.t. the normalised q, k -> w.r.t. the projection output (in place), + dw
-                ops.qk_norm_bwd(dqkv, ws.get(f"{i}.qkv_pre", (M, 3 * D), BF), ws.get(f"{i}.qinv", (M, 2 * heads), F32), b.qn_w, b.kn_w,
-                                b.g_qn, b.g_kn, M, D)
-            linear_bwd(ws, "qkv", b.qkv, dqkv, xn1, M, dxn, defer=probs)
-            if grouped:  # dW of block i + 1 is done: the norm backward below overwrites the dy operand it read (b.dx_b, same parity)
-                OVERLAP.join()
-            ops.norm_bwd(dxn, x_in, b.n1w, st1, dmid, dxo, dxo_b, b.gn1w, b.gn1b, M, D, self.kind,
-                         dx_colsum=self.w3_colsum_target(i - 1) if i > 0 else None)
+            # takes it as dy (proj after the FFN branch; the previous block's w3 after the attention branch)
+            self._ffn_bwd(ws, i, s, dy, dy_b, dmid, dmid_b, M, bt, dpre, fused=self.swiglu and b.ls2 is None,
+                          bias_done=dy_colsum_done if i == self.depth - 1 else self.w3_colsum_target(i) is not None, probs=probs,
+                          dx_colsum=b.proj.gb if b.ls1 is None else None)
+            # grouped: dW of block i + 1 is done before norm1's backward overwrites the dy operand it read (b.dx_b, same parity)
+            self._attn_bwd(ws, t, i, s, dmid, dmid_b, dxo, dxo_b, M, bt, dqkv, rows, prefix_tokens, bias_done=b.proj.gb is not None,
+                           probs=probs, join=grouped, dx_colsum=self.w3_colsum_target(i - 1) if i > 0 else None)
             dy, dy_b = dxo, dxo_b
             if not grouped:
                 OVERLAP.join()
                 yield ("block", i)
                 continue
-            extra = extra_last if (i == 0 and hold_last and extra_last) else []
+            extra = [dict(pr, dy=dy_b) for pr in extra_last] if (i == 0 and hold_last and extra_last) else []
             gkey = (i, bool(self.wgrad_overwrite), len(extra))
             grp = groups.get(gkey)
             if grp is None:
                 grp = ops.WgradGroup(M)
-                for pr in probs + list(extra):
+                for pr in probs + extra:
                     grp.add(pr["dy"], pr["x"], pr["gw"], pr["gb"], pr["N"], pr["K"], pr["swiglu_h"], accumulate=not self.wgrad_overwrite)
                 groups[gkey] = grp.finalize(self.store.device, scratch)
             if pending is not None:
                 yield ("block", pending[0])  # its weight gradients are complete (joined above)
             pending = (i, grp)
         self.held = None
-        if pending is not None and hold_last:
+        if drop:
+            ops.cast_f32_bf16(dy, dy_b, M * D)
+        elif pending is not None and hold_last:
             OVERLAP.run_deferred()
             self.held = pending
         elif pending is not None:  # block 0's group: nothing of this stack is left to run beside it
@@ -1258,11 +1214,7 @@ class TrunkEngine:
             ops.gemm_nt(pt, self.pe.w, xs, M=g.B * g.hw, N=D, K=768, bias=self.pe.bias, epi=EPI_F32, a_remap=(g.hw, 1), c_remap=(g.hw, 1))
             ops.assemble_tokens(xs, st.p(self.prefix + "cls_token"), st.p(self.prefix + "mask_token"), g.masks, g.B, g.N, D)
         stack_segs = [(g.B, g.N, g.rope) for g in segs]
-        dropped = train and self.stack.drop_plan is not None
-        if dropped:  # stochastic depth (block.py:207-289): residual branches on random image subsets, x0 updated in place
-            xl = self.stack.forward_drop(ws, x0, stack_segs, 1)
-        else:
-            xl = self.stack.forward(ws, x0, 0, 0, None, 1, train, segs=stack_segs)
+        xl = self.stack.forward(ws, x0, stack_segs, 1, train)
         xnf = ws.get("xnf", (M, D), BF)
         stf = ws.get("stf", (M, 2), F32)
         ops.norm_fwd(xl, st.p(self.prefix + "norm.weight"), st.p(self.prefix + "norm.bias") if self.kind == ops.NORM_LN else None, xnf, stf,
@@ -1270,7 +1222,6 @@ class TrunkEngine:
         c = TrunkCtx()
         c.ws, c.segs, c.M, c.xl, c.xnf, c.stf, c.patches, c.stack_saved, c.x0, c.stack_segs = \
             ws, segs, M, xl, xnf, stf, patches, self.stack.last_saved, x0, stack_segs
-        c.dropped = dropped
         self._ctx = c
         return xnf
 
@@ -1318,28 +1269,21 @@ class TrunkEngine:
         OVERLAP.join()
         yield "tail"
         g_cls, g_mask = st.g(self.prefix + "cls_token"), st.g(self.prefix + "mask_token")
-        if getattr(c, "dropped", False):
-            dx0 = yield from self.stack.backward_drop(ws, dx, c.stack_segs, 1, c.stack_saved)
-            dx0_b = dx_b
-            ops.cast_f32_bf16(dx0, dx0_b, M * D)
-            self.stack.held = None
-        else:
-            # the patch-embed weight (and bias) gradient as a fifth problem of block 0's grouped launch: dy = the stack's input gradient
-            # (cls and masked rows zeroed by token_rows_bwd below, before the launch), x = the im2col rows in the token layout
-            extra = None
-            if PE_IN_GROUP and not want_dimg and D % 8 == 0:
-                extra = [dict(dy=self.stack.dx_buffers(ws, M)[1], x=c.patches, gw=self.pe.gw, gb=self.pe.gb, N=self.pe.N, K=self.pe.K, swiglu_h=0)]
-            dx0, dx0_b = yield from self.stack.backward(ws, dx, dx_b, 0, 0, None, 1, c.stack_saved, segs=c.stack_segs,
-                                                        dy_colsum_done=self.stack.w3_colsum_target(self.depth - 1) is not None,
-                                                        hold_last=extra is not None, extra_last=extra)
-        held, self.stack.held = getattr(self.stack, "held", None), None
+        # the patch-embed weight (and bias) gradient as a fifth problem of block 0's grouped launch: dy = the stack's input gradient
+        # (cls and masked rows zeroed by token_rows_bwd below, before the launch), x = the im2col rows in the token layout
+        extra = None
+        if not want_dimg and D % 8 == 0:
+            extra = [dict(x=c.patches, gw=self.pe.gw, gb=self.pe.gb, N=self.pe.N, K=self.pe.K, swiglu_h=0)]
+        dx0, dx0_b = yield from self.stack.backward(ws, dx, dx_b, c.stack_segs, 1, c.stack_saved,
+                                                    dy_colsum_done=self.stack.w3_colsum_target(self.depth - 1) is not None,
+                                                    hold_last=extra is not None, extra_last=extra)
+        held, self.stack.held = self.stack.held, None
         # backward of the token assembly (vision_transformer.py:189-219): masked rows -> mask_token, row 0 -> cls_token, both zeroed in the
         # bf16 copy (what is left there is the gradient of the patch-embed output, in token rows)
         for g in c.segs:
             d_s, d_sb = dx0[g.row0:g.row0 + g.B * g.N], dx0_b[g.row0:g.row0 + g.B * g.N]
             ops.token_rows_bwd(d_s, d_sb, g.masks, g_mask if g.masks is not None else None, g_cls, g.B, g.N, D)
-        if held is not None:
-            assert dx0_b.data_ptr() == self.stack.dx_buffers(ws, M)[1].data_ptr()
+        if held is not None:  # (its patch-embed problem reads dx0_b)
             held[1].launch()
             yield ("block", held[0])
         else:
@@ -1409,26 +1353,22 @@ class DecoderEngine:
             # (RopeAugTabs, not a plain pair: _rope_plan keeps a COPY of plain tables, keyed by their address -- a buffer that is
             # refreshed in place would leave the fused qkv + RoPE epilogue rotating with the first step's draw)
             rope = RopeAugTabs(rec["sin"], rec["cos"], 0, h * w)
-        dropped = train and self.stack.drop_plan is not None
-        if dropped:
-            xl = self.stack.forward_drop(ws, x0, [(B, h * w, rope)], 0)
-        else:
-            xl = self.stack.forward(ws, x0, B, h * w, rope, 0, train)
+        segs = [(B, h * w, rope)]
+        xl = self.stack.forward(ws, x0, segs, 0, train)
         xnf = ws.get("xnf", (M, D), BF)
         stf = ws.get("stf", (M, 2), F32)
         ops.norm_fwd(xl, st.p("pixel_decoder.norm.weight"),
                      st.p("pixel_decoder.norm.bias") if self.kind == ops.NORM_LN else None, xnf, stf, M, D, self.eps, self.kind)
         t = ws.get("t", (M, 768), BF)
         ops.gemm_nt(xnf, self.pout.w, t, M=M, N=768, K=D, bias=self.pout.bias, epi=EPI_BF16)
-        self._ctx = (ws, B, h, w, lat, xl, xnf, stf, rope, self.stack.last_saved)
-        self._dropped = dropped
+        self._ctx = (ws, B, h, w, lat, xl, xnf, stf, segs, self.stack.last_saved)
         return t
 
     def backward(self, dt: torch.Tensor):
         """dt bf16 [B*hw, 768] -> d_lat bf16 [B*hw, 64]; parameter grads accumulate into store.flat_g.
         Generator: yields "tail", then ("block", i) per block; returns d_lat."""
         st = self.store
-        ws, B, h, w, lat, xl, xnf, stf, rope, stack_saved = self._ctx
+        ws, B, h, w, lat, xl, xnf, stf, segs, stack_saved = self._ctx
         M, D = B * h * w, self.D
         d_xnf = ws.get("b.d_xnf", (M, D), BF)
         linear_bwd(ws, "pout", self.pout, dt, xnf, M, d_xnf)
@@ -1439,13 +1379,8 @@ class DecoderEngine:
                      dx_colsum=self.stack.w3_colsum_target(self.depth - 1))
         OVERLAP.join()
         yield "tail"
-        if getattr(self, "_dropped", False):
-            dx0 = yield from self.stack.backward_drop(ws, dx, [(B, h * w, rope)], 0, stack_saved)
-            dx0_b = dx_b
-            ops.cast_f32_bf16(dx0, dx0_b, M * D)
-        else:
-            dx0, dx0_b = yield from self.stack.backward(ws, dx, dx_b, B, h * w, rope, 0, stack_saved,
-                                                        dy_colsum_done=self.stack.w3_colsum_target(self.depth - 1) is not None)
+        dx0, dx0_b = yield from self.stack.backward(ws, dx, dx_b, segs, 0, stack_saved,
+                                                    dy_colsum_done=self.stack.w3_colsum_target(self.depth - 1) is not None)
         d_lat = ws.get("b.d_lat", (M, self.cin), BF)
         linear_bwd(ws, "pin", self.pin, dx0_b, lat, M, d_lat)
         OVERLAP.join()
