@@ -16,10 +16,11 @@ Inside the timed region, EVERY step draws fresh block-wise iBOT masks (vtp_amd.d
 the SSL index plan (VTPTrainer.prepare_ssl) and copies it to the device -- one batch ahead of the step that consumes it, as a
 prefetching loader does (the draw for step k + 1 is issued while the GPU runs step k; K timed steps = K draws): the captured
 hipGraph is keyed by the padded masked-token buffer size (the collate's `upperbound`, vtp.py:432-439) and serves every draw.  The image / caption / crop
-tensors stay resident in HBM (the contract's "inputs already resident").  `lpips_on` repeats the measurement (fewer steps) with
-the perceptual term of north_star switched on.
+tensors stay resident in HBM (the contract's "inputs already resident").
 
-Also reported on the same line:
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line.  With --full it goes on, after the timed
+steps (their figures do not change), with what takes runs of its own: `lpips_on` repeats the measurement (fewer steps) with the
+perceptual term of north_star switched on, `separate_passes` with rec and clip on different input tensors, and further on the line:
   roofline     -- the dominant kernel (gemm_nt bf16 MFMA GEMM): algorithmic FLOPs (2*M*N*K per launch) / average launch
                   duration measured with HIP events on the launch stream over one instrumented step run right after
                   the timed region (kept out of it so event overhead cannot inflate `value`); peak = 2.5 PFLOP/s dense
@@ -284,42 +285,42 @@ def bench_forward(args, world, rank, dev):
             el = float(t)
         return el, out
 
+    el_bf16, err, recs = None, None, []
     with torch.no_grad():
-        el_bf16, (lat_b, rec_b) = timed(max(2, args.steps // 2), max(1, args.warmup // 2))
         n_bf16 = max(2, args.steps // 2)
+        if args.full:
+            el_bf16, (lat_b, rec_b) = timed(n_bf16, max(1, args.warmup // 2))
         model.enable_fp8_forward(img[: min(B, 16)])
         el, (lat_8, rec_8) = timed(args.steps, args.warmup)
         if args.dump_outputs and rank == 0:
             dump_outputs(args.dump_outputs, {"latents": lat_8, "reconstruction": rec_8})
-        rec_same = model.get_latents_decoded_images(lat_b)
-        rel = lambda a, b: float((a - b).norm() / b.norm())
-        err = {"latents_rel": round(rel(lat_8, lat_b), 5), "decoder_rel_same_latents": round(rel(rec_same, rec_b), 5),
-               "end_to_end_rel": round(rel(rec_8, rec_b), 5)}
-        # roofline of the dominant kernel: HIP events around every fp8 GEMM launch of one extra pass (rank 0)
-        recs, orig = [], ops.gemm_nt_fp8
+        if args.full:
+            rec_same = model.get_latents_decoded_images(lat_b)
+            rel = lambda a, b: float((a - b).norm() / b.norm())
+            err = {"latents_rel": round(rel(lat_8, lat_b), 5), "decoder_rel_same_latents": round(rel(rec_same, rec_b), 5),
+                   "end_to_end_rel": round(rel(rec_8, rec_b), 5)}
+            # roofline of the dominant kernel: HIP events around every fp8 GEMM launch of one extra pass (rank 0)
+            orig = ops.gemm_nt_fp8
 
-        def probe(a8, b8, c, **kw):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            orig(a8, b8, c, **kw)
-            e1.record()
-            recs.append((2.0 * kw["M"] * kw["N"] * kw["K"], e0, e1))
+            def probe(a8, b8, c, **kw):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                orig(a8, b8, c, **kw)
+                e1.record()
+                recs.append((2.0 * kw["M"] * kw["N"] * kw["K"], e0, e1))
 
-        ops.gemm_nt_fp8 = probe
-        try:
-            one_step()
-            torch.cuda.synchronize()
-        finally:
-            ops.gemm_nt_fp8 = orig
+            ops.gemm_nt_fp8 = probe
+            try:
+                one_step()
+                torch.cuda.synchronize()
+            finally:
+                ops.gemm_nt_fp8 = orig
     c = model.config
     hw = (res // 16) ** 2
     from vtp_amd.config import swiglu_hidden
     enc = vit_fwd_gflop(c.vision_embed_dim, swiglu_hidden(c.vision_embed_dim), c.vision_depth, hw + 1, hw, True)
     dec = vit_fwd_gflop(c.decoder_embed_dim, swiglu_hidden(c.decoder_embed_dim), c.decoder_depth, hw, hw, False)
     ips = world * B * args.steps / el
-    fl = sum(r[0] for r in recs)
-    ms = sum(r[1].elapsed_time(r[2]) for r in recs)
-    ach = fl / (ms * 1e-3) / 1e12
     out = {"metric": "images/sec/node VTP-L f16d64 fp8 forward encode->decode 256x256", "value": round(ips, 2), "unit": "images/sec",
            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(el / args.steps * 1e3, 3),
            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -328,13 +329,19 @@ def bench_forward(args, world, rank, dev):
                                   f"pixel decoder), {B} img/GPU @ {res}x{res}, random-init weights, activation scales calibrated on 16 images",
                       "per_gpu_batch": B, "global_batch": world * B, "resolution": res, "parallelism": f"dp{world} (replicas)",
                       "fwd_gflop_per_image": round(enc + dec, 1)},
-           "bf16_path": {"value": round(world * B * n_bf16 / el_bf16, 2), "unit": "images/sec", "ms_per_step": round(el_bf16 / n_bf16 * 1e3, 3)},
+           "bf16_path": {"value": round(world * B * n_bf16 / el_bf16, 2), "unit": "images/sec", "ms_per_step": round(el_bf16 / n_bf16 * 1e3, 3)}
+           if args.full else None,
            "fp8_vs_bf16": err,
            "step_tflops_per_gpu": round(ips / world * (enc + dec) / 1e3, 1)}
     if rank == 0:
-        out["roofline"] = {"bound": "mfma", "kernel": "vtp::gemm8p_kernel<.., VAR=8> (v_mfma_f32_32x32x64_f8f6f4, e4m3 x e4m3)",
-                           "achieved": round(ach, 1), "peak": PEAK_FP8_TFLOPS, "unit": "TFLOP/s", "frac": round(ach / PEAK_FP8_TFLOPS, 4),
-                           "traffic": None, "launches_per_step": len(recs), "gemm_ms_per_step": round(ms, 3)}
+        out["roofline"] = None
+        if args.full:
+            fl = sum(r[0] for r in recs)
+            ms = sum(r[1].elapsed_time(r[2]) for r in recs)
+            ach = fl / (ms * 1e-3) / 1e12
+            out["roofline"] = {"bound": "mfma", "kernel": "vtp::gemm8p_kernel<.., VAR=8> (v_mfma_f32_32x32x64_f8f6f4, e4m3 x e4m3)",
+                               "achieved": round(ach, 1), "peak": PEAK_FP8_TFLOPS, "unit": "TFLOP/s", "frac": round(ach / PEAK_FP8_TFLOPS, 4),
+                               "traffic": None, "launches_per_step": len(recs), "gemm_ms_per_step": round(ms, 3)}
         out["cpu_baseline"] = None  # reported on the default workload (the reference has no fp8 path)
         print(json.dumps(out), flush=True)
     if world > 1:
@@ -362,6 +369,170 @@ def self_launch(n: int):
     raise SystemExit(subprocess.call(cmd, env=env))
 
 
+def gemm_roofline(args, trainer, img, txt, ssl, rank):
+    """--full: one extra step after the timed region, launched eagerly; rank 0 returns the roofline below, other ranks None"""
+    from vtp_amd import ops
+    # ---- dominant-kernel roofline: one instrumented step, HIP events (recorded on the launch stream) around every launch of
+    # the MFMA GEMM family -- gemm_nt (forward / dgrad) and gemm_tn (wgrad) are the same kernel template (rank 0)
+    roof = None
+    recs = []
+    import vtp_amd.engine as eng
+    orig_nt, orig_tn, orig_qkv, orig_dsw = ops.gemm_nt, ops.gemm_tn, ops.gemm_qkv_rope, ops.gemm_dgrad_swiglu
+
+    def timed(fn):
+        def run(a, b, c, **kw):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn(a, b, c, **kw)
+            e1.record()
+            M = kw["M"] if kw.get("M") is not None else a.shape[0]
+            K = kw["K"] if kw.get("K") is not None else a.shape[1]
+            N = kw["N"] if kw.get("N") is not None else b.shape[0]
+            epi, sp = kw.get("epi", 0), kw.get("splits", 1)
+            # algorithmic HBM bytes: operands once + result once (+ residual read; SwiGLU: x12 and hidden; GELU: pre-activation and output)
+            out_b = {ops.EPI_BF16: 2.0, ops.EPI_F32: 4.0 + (4.0 if kw.get("resid") is not None else 0.0), ops.EPI_SWIGLU: 3.0,
+                     ops.EPI_GELU: 4.0 if kw.get("c2") is not None else 2.0, ops.EPI_F32_ATOMIC: 8.0, ops.EPI_F32_SLAB: 4.0 * sp}.get(epi, 4.0)
+            recs.append((2.0 * M * N * K, e0, e1, (fn.__name__, M, N, K, epi, sp), 2.0 * K * (M + N) + out_b * M * N))
+        return run
+
+    def timed_qkv(a, w, bias, c, M, N, K, *rest):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        orig_qkv(a, w, bias, c, M, N, K, *rest)
+        e1.record()
+        recs.append((2.0 * M * N * K, e0, e1, ("gemm_qkv_rope", M, N, K, 0, 1), 2.0 * K * (M + N) + 2.0 * M * N))
+
+    def timed_dsw(dy, wT, x12, dx12, M, H, K):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        orig_dsw(dy, wT, x12, dx12, M, H, K)
+        e1.record()
+        recs.append((2.0 * M * H * K, e0, e1, ("gemm_dgrad_swiglu", M, H, K, 0, 1), 2.0 * K * (M + H) + 8.0 * M * H))  # + x12 read, dx12 written
+
+    orig_grp = ops.WgradGroup.launch
+
+    def timed_grp(self, kernel=None):  # the block's grouped weight-gradient launch: sum of 2 N K tokens over its problems
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        orig_grp(self, kernel)
+        e1.record()
+        fl = sum(2.0 * r[7] * r[8] * self.Ktok for r in self.rows)
+        by = sum(2.0 * self.Ktok * (r[7] + r[8]) + 4.0 * r[7] * r[8] * (2 if r[12] else 1) for r in self.rows)  # dy + x read, dW written (+ read: C +=)
+        recs.append((fl, e0, e1, ("gemm_tn_grouped", len(self.rows), self.ntiles, self.Ktok, 1, self.splits), by))
+
+    if rank == 0:
+        ops.gemm_nt, ops.gemm_tn, ops.gemm_qkv_rope, ops.gemm_dgrad_swiglu = timed(orig_nt), timed(orig_tn), timed_qkv, timed_dsw
+        ops.WgradGroup.launch = timed_grp
+    trainer.use_graphs = False   # events cannot sit inside a replayed graph: this step launches eagerly
+    overlap_was = eng.OVERLAP.enabled
+    eng.OVERLAP.enabled = False  # per-kernel durations: no second stream sharing the CUs while a GEMM is timed
+    # (without the side streams the step announces its gradient buckets in finer pieces; the rank-sharded optimizer ties chunk
+    # ownership to the bucket layout and refuses a changed one -- this one untimed step after the measurement may re-assign it)
+    shard_layout_was = getattr(trainer, "_shard_layout", None)
+    trainer._shard_layout = None
+    try:
+        trainer.step(img, txt, ssl)  # every rank takes the step (it contains the collectives); rank 0 times its GEMMs
+        torch.cuda.synchronize()
+    finally:
+        trainer._shard_layout = shard_layout_was
+        ops.gemm_nt, ops.gemm_tn, ops.gemm_qkv_rope, ops.gemm_dgrad_swiglu = orig_nt, orig_tn, orig_qkv, orig_dsw
+        ops.WgradGroup.launch = orig_grp
+        eng.OVERLAP.enabled = overlap_was
+    if rank == 0:
+        fl = sum(r[0] for r in recs)
+        ms = sum(r[1].elapsed_time(r[2]) for r in recs)
+        ach = fl / (ms * 1e-3) / 1e12
+        if os.environ.get("VTP_BENCH_GEMM_TABLE"):  # per-shape in-situ table of the instrumented step (tuning aid)
+            tab = {}
+            for f, a, b, key, _by in recs:
+                t = tab.setdefault(key, [0, 0.0, 0.0])
+                t[0] += 1
+                t[1] += a.elapsed_time(b)
+                t[2] += f
+            with open(os.environ["VTP_BENCH_GEMM_TABLE"], "w") as fh:
+                for key, (n, t, f) in sorted(tab.items(), key=lambda kv: -kv[1][1]):
+                    fh.write(f"{key[0]:14s} M={key[1]:6d} N={key[2]:6d} K={key[3]:6d} epi={key[4]} splits={key[5]:2d}  calls={n:3d}  "
+                             f"total={t:7.3f} ms  avg={t / n * 1e3:7.1f} us  {f / t / 1e9:7.1f} TF/s\n")
+        traffic, traffic_src, mfma_util, pmc_extra = None, None, None, None
+        pmc = next((q for q in (os.path.join(ROOT, "profiles", f"r0{r}_pmc_summary.json") for r in (6, 5, 4, 3, 2, 1)) if os.path.exists(q)), "")
+        if pmc and args.workload == "vtp_base_full" and not args.batch:
+            try:  # HBM bytes per launch and SQ counters of the same kernels from the committed rocprofv3 --pmc passes of this command
+                d = json.load(open(pmc))
+                by, n, busy, gui = 0.0, 0, 0.0, 0.0
+                for fam in ("gemm_nt", "gemm_tn", "gemm8p_nt", "gemm8p_tn", "gemm8p_grouped_tn", "gemm8h_nt", "gemm4w_nt", "gemm4w_grouped_tn"):
+                    if fam not in d:
+                        continue
+                    # FETCH_SIZE / WRITE_SIZE are KiB; gfx950 FETCH_SIZE tallies 128-B requests at 64 B (x2, MI355X_MICROARCH.md HBM)
+                    by += 1024.0 * (2.0 * d[fam]["FETCH_SIZE"]["sum"] + d[fam]["WRITE_SIZE"]["sum"])
+                    n += d[fam]["FETCH_SIZE"]["dispatches"]
+                    if "SQ_VALU_MFMA_BUSY_CYCLES" in d[fam]:
+                        busy += d[fam]["SQ_VALU_MFMA_BUSY_CYCLES"]["sum"]
+                        gui += d[fam]["GRBM_GUI_ACTIVE"]["sum"]
+                traffic, traffic_src = round(by / n), f"profiles/{os.path.basename(pmc)} (separate --pmc passes; bytes per launch)"
+                if gui > 0:
+                    # matrix-pipe busy cycles / SIMD-cycles while the kernels ran (tools/pmc_summarize.py `derived`: GRBM_GUI_ACTIVE is
+                    # summed over the 8 XCDs; 1024 SIMDs); attention alongside, from the same pass
+                    mfma_util = round(busy / (gui / 8.0 * 1024.0), 4)
+                    pmc_extra = {k: {m: d[k][m] for m in ("mfma_util", "valu_busy", "lds_bank_conflict_frac") if m in d[k]}
+                                 for k in ("gemm8p_nt", "gemm8h_nt", "gemm4w_nt", "gemm4w_grouped_tn", "gemm8p_grouped_tn", "gemm_nt", "attn_fwd", "attn_bwd_fused") if k in d}
+            except (KeyError, ValueError, ZeroDivisionError):
+                pass
+        # algorithmic HBM bytes of the same launches: every operand read once, every result written once (+ the residual / pre-
+        # activation reads of the fused epilogues) -- what `traffic` is to be compared with
+        alg = sum(r[4] for r in recs if len(r) > 4 and r[4])
+        # the MIXED floor of the same launches (VERDICT r5 item 7): per launch max(FLOP / dense bf16 MFMA peak, algorithmic bytes / the
+        # 6.3 TB/s a streaming copy achieves) -- what the family would take if every launch sat on whichever roof bounds it
+        HBM_ACHIEVABLE = 6.3e12
+        mixed_ms = sum(max(r[0] / (PEAK_BF16_TFLOPS * 1e12), r[4] / HBM_ACHIEVABLE) for r in recs) * 1e3
+        mfma_ms = sum(r[0] for r in recs) / (PEAK_BF16_TFLOPS * 1e12) * 1e3
+        hbm_bound = sum(1 for r in recs if r[4] / HBM_ACHIEVABLE > r[0] / (PEAK_BF16_TFLOPS * 1e12))
+        # HBM floors of the step's other kernel families from the same counter passes (bytes per step / 6.3 TB/s) beside their kernel
+        # time in the committed rocprofv3 --stats summary of the round (single stream): attention, norms, optimizer lane
+        other = None
+        try:
+            if pmc:
+                d = json.load(open(pmc))
+                rnd = os.path.basename(pmc)[:3]
+                stats = os.path.join(ROOT, "profiles", f"{rnd}_kernel_stats_full_eager_b32.csv")
+                tms = {}
+                if os.path.exists(stats):
+                    import csv as _csv
+                    rows_ = list(_csv.DictReader(open(stats)))
+                    nst = max(1, min(int(r_["Calls"]) for r_ in rows_ if "dino_ce_kernel" in r_["Name"])) if any("dino_ce_kernel" in r_["Name"] for r_ in rows_) else 1
+                    for fam in ("attn_fwd", "attn_bwd_fused", "norm_fwd", "norm_bwd", "adamw", "prep_weights"):
+                        tms[fam] = sum(float(r_["TotalDurationNs"]) for r_ in rows_ if fam in r_["Name"]) / nst / 1e6
+                other = {}
+                for fam in ("attn_fwd", "attn_bwd_fused", "norm_fwd", "norm_bwd", "adamw", "prep_weights"):
+                    if fam in d and "FETCH_SIZE" in d[fam]:
+                        steps_pmc = max(1, d["dino_ce"]["FETCH_SIZE"]["dispatches"]) if "dino_ce" in d else 1
+                        byt = 1024.0 * (2.0 * d[fam]["FETCH_SIZE"]["sum"] + d[fam]["WRITE_SIZE"]["sum"]) / steps_pmc
+                        other[fam] = {"hbm_bytes_per_step": round(byt), "hbm_floor_ms": round(byt / HBM_ACHIEVABLE * 1e3, 3),
+                                      "kernel_ms_per_step": round(tms[fam], 3) if fam in tms else None,
+                                      "frac_of_floor": round(byt / HBM_ACHIEVABLE * 1e3 / tms[fam], 3) if tms.get(fam) else None}
+        except (KeyError, ValueError, ZeroDivisionError, OSError):
+            other = None
+        roof = {"bound": "mfma", "kernel": "vtp::gemm8p_kernel<...> + vtp::gemm4w_grouped_tn_kernel + vtp::gemm4w_kernel<...> + vtp::gemm8h_kernel<...> + vtp::gemm_nt_kernel<...> (the bf16 MFMA 32x32x16 GEMM family: NT fwd/dgrad, TN wgrad incl. the per-block grouped launches; 256x256 8-phase, one-wave-per-SIMD and 128x256 kernels, ring tile configs, all epilogues)",
+                "achieved": round(ach, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": round(ach / PEAK_BF16_TFLOPS, 4),
+                "traffic": traffic, "traffic_source": traffic_src,
+                "pmc_replayed": traffic is not None,  # traffic / mfma_util / pmc_by_kernel come from the committed rocprofv3 --pmc passes of this
+                # command (profiles/), NOT from this run: hardware counters cannot be read from inside the process
+                "algorithmic_bytes_per_launch_avg": round(alg / len(recs)) if alg else None,
+                "traffic_over_algorithmic": round(traffic / (alg / len(recs)), 3) if (traffic and alg) else None,
+                "mfma_util": mfma_util, "mfma_util_note": "SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 XCDs x 1024 SIMDs) of the GEMM family, "
+                "rocprofv3 --pmc pass of this command (profiles/); x sustained clock / 2.4 GHz = fraction of the data-sheet peak",
+                "pmc_by_kernel": pmc_extra, "launches_per_step": len(recs),
+                "avg_launch_us": round(ms * 1e3 / len(recs), 2), "gemm_ms_per_step": round(ms, 3),
+                "flop_per_launch_avg": fl / len(recs),
+                "mixed_floor_ms": round(mixed_ms, 3), "mfma_floor_ms": round(mfma_ms, 3), "frac_of_mixed_floor": round(mixed_ms / ms, 4),
+                "launches_hbm_bound_at_the_floor": hbm_bound,
+                "mixed_floor_note": "sum over the instrumented step's launches of max(2MNK / 2.5 PFLOP/s, algorithmic bytes / 6.3 TB/s); "
+                "frac_of_mixed_floor = that / gemm_ms_per_step",
+                "other_families_hbm_floor": other,
+                "other_families_note": "bytes per step = 2 x FETCH_SIZE + WRITE_SIZE of the committed --pmc passes (replayed, like `traffic`); "
+                "kernel_ms_per_step from the committed rocprofv3 --stats CSV of the same round (eager, single stream)"}
+    return roof
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -369,16 +540,20 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="vtp_base_full", choices=sorted(WORKLOADS) + sorted(FORWARD_WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (default: workload's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement, also run what takes runs of its own: the instrumented roofline step, the "
+                         "LPIPS-on and separate-pass measurements, the end-to-end parity and CPU-oracle legs (forward workload: the "
+                         "bf16-path timing, the fp8-vs-bf16 errors and the roofline pass).  Off: set up, warm up, time, dump, print")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the end-to-end parity and CPU-oracle legs")
     ap.add_argument("--cpu-batch", type=int, default=2, help="images per CPU-oracle step (the full step costs ~8 s per image on a 128-thread host)")
     ap.add_argument("--cpu-steps", type=int, default=5, help="timed fp32 steps of the CPU-oracle leg (bf16-autocast leg: half of it)")
     ap.add_argument("--cpu-survey-protocol", action="store_true", help="SURVEY 8d's CPU protocol: batch 8, 10 timed fp32 steps (5 bf16-autocast) -- "
                     "about 25 minutes of host time on a 128-thread box, so NOT the default (the driver's run keeps batch 2, 5 + 3 steps)")
     ap.add_argument("--bucket-blocks", type=int, default=3, help="transformer blocks per gradient bucket (= per hipGraph segment / optimizer-lane update)")
-    ap.add_argument("--no-lpips-run", action="store_true", help="skip the second measurement with the perceptual term on")
+    ap.add_argument("--no-lpips-run", action="store_true", help="--full without the second measurement with the perceptual term on")
     ap.add_argument("--no-graphs", action="store_true", help="eager kernel launches instead of hipGraph segment replay")
     ap.add_argument("--no-separate-run", action="store_true",
-                    help="skip the extra measurement with a separate reconstruction input (rec and clip as separate trunk passes)")
+                    help="--full without the extra measurement with a separate reconstruction input (rec and clip as separate trunk passes)")
     ap.add_argument("--shard-optimizer", action="store_true",
                     help="N > 1: reduce-scatter + rank-sharded AdamW + parameter all-gather instead of all-reduce + replicated AdamW")
     ap.add_argument("--grad-dtype", default="fp32", choices=["fp32", "bf16"], help="gradient bucket dtype (bf16: --shard-optimizer only)")
@@ -574,170 +749,13 @@ def main():
         print(f"[bench] per-step ms (HIP events on the main stream): {state.get('per_step_ms')}", file=sys.stderr, flush=True)
     state["comm_main"] = state.pop("comm", None)  # rank 0's main-stream waits (the second, LPIPS-on measurement overwrites "comm")
     ssl = None
-    if do_ssl:  # the instrumented step below reuses the last drawn batch
+    if do_ssl and args.full:  # the batch of the instrumented step below
         masks, upper = mask_stream.draw()
         ssl = trainer.prepare_ssl(crops[0], crops[1], masks, upperbound=upper)
     loss_val, closs_val = float(loss), float(closs)
     ssl_loss_val = float(trainer.ssl_loss_sum) if do_ssl else 0.0
 
-    # ---- dominant-kernel roofline: one instrumented step, HIP events (recorded on the launch stream) around every launch of
-    # the MFMA GEMM family -- gemm_nt (forward / dgrad) and gemm_tn (wgrad) are the same kernel template (rank 0)
-    roof = None
-    recs = []
-    import vtp_amd.engine as eng
-    orig_nt, orig_tn, orig_qkv, orig_dsw = ops.gemm_nt, ops.gemm_tn, ops.gemm_qkv_rope, ops.gemm_dgrad_swiglu
-
-    def timed(fn):
-        def run(a, b, c, **kw):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn(a, b, c, **kw)
-            e1.record()
-            M = kw["M"] if kw.get("M") is not None else a.shape[0]
-            K = kw["K"] if kw.get("K") is not None else a.shape[1]
-            N = kw["N"] if kw.get("N") is not None else b.shape[0]
-            epi, sp = kw.get("epi", 0), kw.get("splits", 1)
-            # algorithmic HBM bytes: operands once + result once (+ residual read; SwiGLU: x12 and hidden; GELU: pre-activation and output)
-            out_b = {ops.EPI_BF16: 2.0, ops.EPI_F32: 4.0 + (4.0 if kw.get("resid") is not None else 0.0), ops.EPI_SWIGLU: 3.0,
-                     ops.EPI_GELU: 4.0 if kw.get("c2") is not None else 2.0, ops.EPI_F32_ATOMIC: 8.0, ops.EPI_F32_SLAB: 4.0 * sp}.get(epi, 4.0)
-            recs.append((2.0 * M * N * K, e0, e1, (fn.__name__, M, N, K, epi, sp), 2.0 * K * (M + N) + out_b * M * N))
-        return run
-
-    def timed_qkv(a, w, bias, c, M, N, K, *rest):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        orig_qkv(a, w, bias, c, M, N, K, *rest)
-        e1.record()
-        recs.append((2.0 * M * N * K, e0, e1, ("gemm_qkv_rope", M, N, K, 0, 1), 2.0 * K * (M + N) + 2.0 * M * N))
-
-    def timed_dsw(dy, wT, x12, dx12, M, H, K):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        orig_dsw(dy, wT, x12, dx12, M, H, K)
-        e1.record()
-        recs.append((2.0 * M * H * K, e0, e1, ("gemm_dgrad_swiglu", M, H, K, 0, 1), 2.0 * K * (M + H) + 8.0 * M * H))  # + x12 read, dx12 written
-
-    orig_grp = ops.WgradGroup.launch
-
-    def timed_grp(self, kernel=None):  # the block's grouped weight-gradient launch: sum of 2 N K tokens over its problems
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        orig_grp(self, kernel)
-        e1.record()
-        fl = sum(2.0 * r[7] * r[8] * self.Ktok for r in self.rows)
-        by = sum(2.0 * self.Ktok * (r[7] + r[8]) + 4.0 * r[7] * r[8] * (2 if r[12] else 1) for r in self.rows)  # dy + x read, dW written (+ read: C +=)
-        recs.append((fl, e0, e1, ("gemm_tn_grouped", len(self.rows), self.ntiles, self.Ktok, 1, self.splits), by))
-
-    if rank == 0:
-        ops.gemm_nt, ops.gemm_tn, ops.gemm_qkv_rope, ops.gemm_dgrad_swiglu = timed(orig_nt), timed(orig_tn), timed_qkv, timed_dsw
-        ops.WgradGroup.launch = timed_grp
-    trainer.use_graphs = False   # events cannot sit inside a replayed graph: this step launches eagerly
-    overlap_was = eng.OVERLAP.enabled
-    eng.OVERLAP.enabled = False  # per-kernel durations: no second stream sharing the CUs while a GEMM is timed
-    # (without the side streams the step announces its gradient buckets in finer pieces; the rank-sharded optimizer ties chunk
-    # ownership to the bucket layout and refuses a changed one -- this one untimed step after the measurement may re-assign it)
-    shard_layout_was = getattr(trainer, "_shard_layout", None)
-    trainer._shard_layout = None
-    try:
-        trainer.step(img, txt, ssl)  # every rank takes the step (it contains the collectives); rank 0 times its GEMMs
-        torch.cuda.synchronize()
-    finally:
-        trainer._shard_layout = shard_layout_was
-        ops.gemm_nt, ops.gemm_tn, ops.gemm_qkv_rope, ops.gemm_dgrad_swiglu = orig_nt, orig_tn, orig_qkv, orig_dsw
-        ops.WgradGroup.launch = orig_grp
-        eng.OVERLAP.enabled = overlap_was
-    if rank == 0:
-        fl = sum(r[0] for r in recs)
-        ms = sum(r[1].elapsed_time(r[2]) for r in recs)
-        ach = fl / (ms * 1e-3) / 1e12
-        if os.environ.get("VTP_BENCH_GEMM_TABLE"):  # per-shape in-situ table of the instrumented step (tuning aid)
-            tab = {}
-            for f, a, b, key, _by in recs:
-                t = tab.setdefault(key, [0, 0.0, 0.0])
-                t[0] += 1
-                t[1] += a.elapsed_time(b)
-                t[2] += f
-            with open(os.environ["VTP_BENCH_GEMM_TABLE"], "w") as fh:
-                for key, (n, t, f) in sorted(tab.items(), key=lambda kv: -kv[1][1]):
-                    fh.write(f"{key[0]:14s} M={key[1]:6d} N={key[2]:6d} K={key[3]:6d} epi={key[4]} splits={key[5]:2d}  calls={n:3d}  "
-                             f"total={t:7.3f} ms  avg={t / n * 1e3:7.1f} us  {f / t / 1e9:7.1f} TF/s\n")
-        traffic, traffic_src, mfma_util, pmc_extra = None, None, None, None
-        pmc = next((q for q in (os.path.join(ROOT, "profiles", f"r0{r}_pmc_summary.json") for r in (6, 5, 4, 3, 2, 1)) if os.path.exists(q)), "")
-        if pmc and args.workload == "vtp_base_full" and not args.batch:
-            try:  # HBM bytes per launch and SQ counters of the same kernels from the committed rocprofv3 --pmc passes of this command
-                d = json.load(open(pmc))
-                by, n, busy, gui = 0.0, 0, 0.0, 0.0
-                for fam in ("gemm_nt", "gemm_tn", "gemm8p_nt", "gemm8p_tn", "gemm8p_grouped_tn", "gemm8h_nt", "gemm4w_nt", "gemm4w_grouped_tn"):
-                    if fam not in d:
-                        continue
-                    # FETCH_SIZE / WRITE_SIZE are KiB; gfx950 FETCH_SIZE tallies 128-B requests at 64 B (x2, MI355X_MICROARCH.md HBM)
-                    by += 1024.0 * (2.0 * d[fam]["FETCH_SIZE"]["sum"] + d[fam]["WRITE_SIZE"]["sum"])
-                    n += d[fam]["FETCH_SIZE"]["dispatches"]
-                    if "SQ_VALU_MFMA_BUSY_CYCLES" in d[fam]:
-                        busy += d[fam]["SQ_VALU_MFMA_BUSY_CYCLES"]["sum"]
-                        gui += d[fam]["GRBM_GUI_ACTIVE"]["sum"]
-                traffic, traffic_src = round(by / n), f"profiles/{os.path.basename(pmc)} (separate --pmc passes; bytes per launch)"
-                if gui > 0:
-                    # matrix-pipe busy cycles / SIMD-cycles while the kernels ran (tools/pmc_summarize.py `derived`: GRBM_GUI_ACTIVE is
-                    # summed over the 8 XCDs; 1024 SIMDs); attention alongside, from the same pass
-                    mfma_util = round(busy / (gui / 8.0 * 1024.0), 4)
-                    pmc_extra = {k: {m: d[k][m] for m in ("mfma_util", "valu_busy", "lds_bank_conflict_frac") if m in d[k]}
-                                 for k in ("gemm8p_nt", "gemm8h_nt", "gemm4w_nt", "gemm4w_grouped_tn", "gemm8p_grouped_tn", "gemm_nt", "attn_fwd", "attn_bwd_fused") if k in d}
-            except (KeyError, ValueError, ZeroDivisionError):
-                pass
-        # algorithmic HBM bytes of the same launches: every operand read once, every result written once (+ the residual / pre-
-        # activation reads of the fused epilogues) -- what `traffic` is to be compared with
-        alg = sum(r[4] for r in recs if len(r) > 4 and r[4])
-        # the MIXED floor of the same launches: per launch max(FLOP / dense bf16 MFMA peak, algorithmic bytes / the
-        # 6.3 TB/s a streaming copy achieves) -- what the family would take if every launch sat on whichever roof bounds it
-        HBM_ACHIEVABLE = 6.3e12
-        mixed_ms = sum(max(r[0] / (PEAK_BF16_TFLOPS * 1e12), r[4] / HBM_ACHIEVABLE) for r in recs) * 1e3
-        mfma_ms = sum(r[0] for r in recs) / (PEAK_BF16_TFLOPS * 1e12) * 1e3
-        hbm_bound = sum(1 for r in recs if r[4] / HBM_ACHIEVABLE > r[0] / (PEAK_BF16_TFLOPS * 1e12))
-        # HBM floors of the step's other kernel families from the same counter passes (bytes per step / 6.3 TB/s) beside their kernel
-        # time in the committed rocprofv3 --stats summary of the round (single stream): attention, norms, optimizer lane
-        other = None
-        try:
-            if pmc:
-                d = json.load(open(pmc))
-                rnd = os.path.basename(pmc)[:3]
-                stats = os.path.join(ROOT, "profiles", f"{rnd}_kernel_stats_full_eager_b32.csv")
-                tms = {}
-                if os.path.exists(stats):
-                    import csv as _csv
-                    rows_ = list(_csv.DictReader(open(stats)))
-                    nst = max(1, min(int(r_["Calls"]) for r_ in rows_ if "dino_ce_kernel" in r_["Name"])) if any("dino_ce_kernel" in r_["Name"] for r_ in rows_) else 1
-                    for fam in ("attn_fwd", "attn_bwd_fused", "norm_fwd", "norm_bwd", "adamw", "prep_weights"):
-                        tms[fam] = sum(float(r_["TotalDurationNs"]) for r_ in rows_ if fam in r_["Name"]) / nst / 1e6
-                other = {}
-                for fam in ("attn_fwd", "attn_bwd_fused", "norm_fwd", "norm_bwd", "adamw", "prep_weights"):
-                    if fam in d and "FETCH_SIZE" in d[fam]:
-                        steps_pmc = max(1, d["dino_ce"]["FETCH_SIZE"]["dispatches"]) if "dino_ce" in d else 1
-                        byt = 1024.0 * (2.0 * d[fam]["FETCH_SIZE"]["sum"] + d[fam]["WRITE_SIZE"]["sum"]) / steps_pmc
-                        other[fam] = {"hbm_bytes_per_step": round(byt), "hbm_floor_ms": round(byt / HBM_ACHIEVABLE * 1e3, 3),
-                                      "kernel_ms_per_step": round(tms[fam], 3) if fam in tms else None,
-                                      "frac_of_floor": round(byt / HBM_ACHIEVABLE * 1e3 / tms[fam], 3) if tms.get(fam) else None}
-        except (KeyError, ValueError, ZeroDivisionError, OSError):
-            other = None
-        roof = {"bound": "mfma", "kernel": "vtp::gemm8p_kernel<...> + vtp::gemm4w_grouped_tn_kernel + vtp::gemm4w_kernel<...> + vtp::gemm8h_kernel<...> + vtp::gemm_nt_kernel<...> (the bf16 MFMA 32x32x16 GEMM family: NT fwd/dgrad, TN wgrad incl. the per-block grouped launches; 256x256 8-phase, one-wave-per-SIMD and 128x256 kernels, ring tile configs, all epilogues)",
-                "achieved": round(ach, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": round(ach / PEAK_BF16_TFLOPS, 4),
-                "traffic": traffic, "traffic_source": traffic_src,
-                "pmc_replayed": traffic is not None,  # traffic / mfma_util / pmc_by_kernel come from the committed rocprofv3 --pmc passes of this
-                # command (profiles/), NOT from this run: hardware counters cannot be read from inside the process
-                "algorithmic_bytes_per_launch_avg": round(alg / len(recs)) if alg else None,
-                "traffic_over_algorithmic": round(traffic / (alg / len(recs)), 3) if (traffic and alg) else None,
-                "mfma_util": mfma_util, "mfma_util_note": "SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 XCDs x 1024 SIMDs) of the GEMM family, "
-                "rocprofv3 --pmc pass of this command (profiles/); x sustained clock / 2.4 GHz = fraction of the data-sheet peak",
-                "pmc_by_kernel": pmc_extra, "launches_per_step": len(recs),
-                "avg_launch_us": round(ms * 1e3 / len(recs), 2), "gemm_ms_per_step": round(ms, 3),
-                "flop_per_launch_avg": fl / len(recs),
-                "mixed_floor_ms": round(mixed_ms, 3), "mfma_floor_ms": round(mfma_ms, 3), "frac_of_mixed_floor": round(mixed_ms / ms, 4),
-                "launches_hbm_bound_at_the_floor": hbm_bound,
-                "mixed_floor_note": "sum over the instrumented step's launches of max(2MNK / 2.5 PFLOP/s, algorithmic bytes / 6.3 TB/s); "
-                "frac_of_mixed_floor = that / gemm_ms_per_step",
-                "other_families_hbm_floor": other,
-                "other_families_note": "bytes per step = 2 x FETCH_SIZE + WRITE_SIZE of the committed --pmc passes (replayed, like `traffic`); "
-                "kernel_ms_per_step from the committed rocprofv3 --stats CSV of the same round (eager, single stream)"}
+    roof = gemm_roofline(args, trainer, img, txt, ssl, rank) if args.full else None
     if world > 1:
         sync()
 
@@ -758,7 +776,7 @@ def main():
         ssl_trunk = 3.0 * (2 * enc_nb + 8 * loc) + 2 * enc_nb          # student fwd+bwd (2 global + 8 local) + teacher fwd
         dh = model.dino_cfg
         tok_flop = 2.0 * (dh["in_dim"] * dh["hidden"] + dh["hidden"] ** 2 + dh["hidden"] * dh["bott"] + dh["bott"] * dh["K"])
-        pl = ssl["plan"]
+        pl = state["last_plan"]   # Ts and Tm follow from the collate's upperbound: the same for every draw
         head = (3.0 * pl["Ts"] + (2 * B + pl["Tm"])) * tok_flop / 1e9 / B   # student fwd+bwd + teacher fwd, per image
         gflop_img += ssl_trunk + head
         gflop_ref += ssl_trunk + head
@@ -776,7 +794,7 @@ def main():
                       "mean_lpips": round(float(trainer.lpips_val.mean()), 5), "weights": "seeded random (vgg.pth unavailable offline)"}
     ips = world * B * args.steps / elapsed
     lpips_on = None
-    if args.perceptual_weight == 0 and not args.no_lpips_run and args.workload.startswith("vtp_base"):
+    if args.full and args.perceptual_weight == 0 and not args.no_lpips_run and args.workload.startswith("vtp_base"):
         # the same step with the perceptual (LPIPS / VGG16) term of north_star switched on: fewer steps, same protocol
         del trainer, model
         torch.cuda.empty_cache()
@@ -790,7 +808,7 @@ def main():
                     "mean_lpips": round(float(tr2.lpips_val.mean()), 5), "weights": "seeded random VGG16 (vgg.pth is a download)"}
         model = m2
     separate = None
-    if clip and not args.no_separate_run and args.workload.startswith("vtp_base"):
+    if args.full and clip and not args.no_separate_run and args.workload.startswith("vtp_base"):
         # the reference's accounting EXECUTED: `image` and `reconstruction_image` are different tensors (vtp.py:323-338), so the
         # reconstruction objective runs its own trunk pass (one more item of the list forward) -- gflop_ref per image
         try:
@@ -834,7 +852,7 @@ def main():
     }
     if rank == 0:
         out["roofline"] = roof
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             e2e = e2e_parity(model, res, dev)  # (before the CPU leg: the model's weights are still on the device)
             if args.cpu_survey_protocol:
                 args.cpu_batch, args.cpu_steps = 8, 10

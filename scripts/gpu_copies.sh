@@ -1,12 +1,13 @@
 #!/bin/bash
 # which launches are the __amd_rocclr_copyBuffer / fill kernels of a step? (kernel trace, eager, one stream: grid sizes + neighbours)
+export RES=$(realpath -m "${RES:-out}"); mkdir -p "$RES"   # where this script writes its results
 export PYTHONDONTWRITEBYTECODE=1 VTP_OVERLAP=0
 R=$PWD
-rm -rf $R/gpurun_out/prof_cp; mkdir -p $R/gpurun_out/prof_cp
+rm -rf $RES/prof_cp; mkdir -p $RES/prof_cp
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --output-format csv -d $R/gpurun_out/prof_cp -o cp -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-lpips-run --no-separate-run --no-graphs > $R/gpurun_out/prof_cp.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --output-format csv -d $RES/prof_cp -o cp -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-lpips-run --no-separate-run --no-graphs > $RES/prof_cp.log 2>&1
 cd $R
-f=$(find gpurun_out/prof_cp -name "*kernel_trace.csv" | head -1)
+f=$(find $RES/prof_cp -name "*kernel_trace.csv" | head -1)
 python - "$f" <<'PY'
 import csv, sys, collections
 rows = list(csv.DictReader(open(sys.argv[1])))
@@ -30,4 +31,4 @@ for i, r in enumerate(step):
 for k, v in sorted(((k, v) for k, v in c.items() if k[0] != "dur"), key=lambda kv: -c[("dur", kv[0])])[:40]:
     print(f"{v:4d} x {k[0]} grid={k[1]:>9s} total {c[('dur', k)]:8.1f} us | after {k[2]} | before {k[3]}")
 PY
-rm -rf gpurun_out/prof_cp
+rm -rf $RES/prof_cp

@@ -7,12 +7,12 @@ mkdir -p $O
 python -c "import torch; print('stream priority range', torch.cuda.Stream.priority_range() if hasattr(torch.cuda.Stream,'priority_range') else 'n/a')" | tee -a $O/summary.txt
 for rep in 1 2; do
   for cfg in "VTP_SIDE_PRIO=0" "VTP_SIDE_PRIO=1" "VTP_SIDE_PRIO=-1"; do
-    v=$(env $cfg timeout 400 python bench.py --steps 12 --warmup 4 --no-cpu-baseline --no-lpips-run --no-separate-run 2>$O/ab.err | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], d["ms_per_step"], d["roofline"]["gemm_ms_per_step"])')
+    v=$(env $cfg timeout 400 python bench.py --full --steps 12 --warmup 4 --no-cpu-baseline --no-lpips-run --no-separate-run 2>$O/ab.err | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], d["ms_per_step"], d["roofline"]["gemm_ms_per_step"])')
     echo "[$cfg] $v" | tee -a $O/summary.txt
   done
 done
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O/prof -o lane -- python $R/bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-lpips-run --no-separate-run > $O/prof.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O/prof -o lane -- python $R/bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-lpips-run --no-separate-run > $O/prof.log 2>&1
 cd $R
 python - <<'PY'
 import csv, glob, os

@@ -9,7 +9,7 @@ timeout 900 python -m pytest tests/test_parity_ssl_gpu.py tests/test_trainer_inp
 OUT=r06fl REPS=${REPS:-3} STEPS=20 bash scripts/r06_ab.sh "VTP_FORK_LATE=0" "VTP_FORK_LATE=1"
 for v in 0 1; do
   rm -rf $O/trace
-  (cd /tmp && export TMPDIR=/tmp && VTP_FORK_LATE=$v timeout 300 rocprofv3 --kernel-trace --output-format csv -d $R/$O/trace -- python $R/bench.py --steps 6 --warmup 3 --no-cpu-baseline --no-lpips-run --no-separate-run > $R/$O/trace_bench_$v.log 2>&1)
+  (cd /tmp && export TMPDIR=/tmp && VTP_FORK_LATE=$v timeout 300 rocprofv3 --kernel-trace --output-format csv -d $R/$O/trace -- python $R/bench.py --full --steps 6 --warmup 3 --no-cpu-baseline --no-lpips-run --no-separate-run > $R/$O/trace_bench_$v.log 2>&1)
   python - $v <<'PY'
 import csv, glob, sys
 v = sys.argv[1]

@@ -5,7 +5,7 @@ O=gpurun_out/r06_power; mkdir -p $O
 rocm-smi --showpower --showclocks --showmaxpower 2>&1 | head -40 > $O/idle.txt
 ( for i in $(seq 1 400); do rocm-smi --showpower --showclocks 2>/dev/null | grep -E "Power|sclk" | tr '\n' ' '; echo; sleep 0.05; done > $O/samples.txt ) &
 SP=$!
-timeout 300 python bench.py --steps 200 --warmup 5 --no-cpu-baseline --no-lpips-run --no-separate-run > $O/bench.json 2> $O/bench.err
+timeout 300 python bench.py --full --steps 200 --warmup 5 --no-cpu-baseline --no-lpips-run --no-separate-run > $O/bench.json 2> $O/bench.err
 kill $SP 2>/dev/null
 python - <<'PY'
 import re

@@ -6,7 +6,7 @@ export PYTHONDONTWRITEBYTECODE=1
 R=$PWD
 for cfg in "$@"; do
   O=gpurun_out/r06to_$(echo "$cfg" | tr ' =' '__'); mkdir -p $O; rm -rf $O/trace
-  (cd /tmp && export TMPDIR=/tmp && env $cfg timeout 300 rocprofv3 --kernel-trace --output-format csv -d $R/$O/trace -- python $R/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-lpips-run --no-separate-run $EXTRA > $R/$O/trace_bench.log 2>&1)
+  (cd /tmp && export TMPDIR=/tmp && env $cfg timeout 300 rocprofv3 --kernel-trace --output-format csv -d $R/$O/trace -- python $R/bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-lpips-run --no-separate-run $EXTRA > $R/$O/trace_bench.log 2>&1)
   python - "$O" "$cfg" <<'PY'
 import csv, glob, sys
 O, cfg = sys.argv[1], sys.argv[2]

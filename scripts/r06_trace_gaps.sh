@@ -5,7 +5,7 @@ R=$PWD
 O=gpurun_out/${OUT:-r06tg}
 mkdir -p $O
 rm -rf $O/trace
-(cd /tmp && export TMPDIR=/tmp && timeout 300 rocprofv3 --kernel-trace --output-format csv -d $R/$O/trace -- python $R/bench.py --steps 6 --warmup 3 --no-cpu-baseline --no-lpips-run --no-separate-run $EXTRA > $R/$O/trace_bench.log 2>&1)
+(cd /tmp && export TMPDIR=/tmp && timeout 300 rocprofv3 --kernel-trace --output-format csv -d $R/$O/trace -- python $R/bench.py --full --steps 6 --warmup 3 --no-cpu-baseline --no-lpips-run --no-separate-run $EXTRA > $R/$O/trace_bench.log 2>&1)
 python - $O <<'PY'
 import csv, glob, sys
 O = sys.argv[1]
