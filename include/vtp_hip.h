@@ -261,6 +261,20 @@ int vtp_ema_dev(float* t, const float* s, long n, const float* momentum /* devic
  * bucket for the per-bucket optimizer lane of the training step.  Short-lived blocks (4096 elements each). */
 int vtp_adamw_ema_dev(float* p, const float* g, float* m, float* v, float* teacher, const void* nodecay4, long n, const float* hyper,
                       void* stream);
+/* Global gradient-norm clipping (torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2): total_norm = ||g||_2 over every
+ * gradient, coef = clamp(max_norm / (total_norm + 1e-6), max=1), g *= coef) in front of the AdamW kernels above, without float
+ * atomics: bitwise reproducible for a given gradient and partials layout.
+ * vtp_sumsq_partials: partials[j] = sum of g[i]^2 (fp64) over chunk j of g[0, n) (n % 4 == 0); writes vtp_sumsq_partials_count(n)
+ *   partials, a number that depends on n only (one per 8192 elements).  Several ranges may share one partials buffer at different
+ *   offsets.  Short-lived workgroups (one chunk each).
+ * vtp_sum_partials: *sum = partials[0] + ... + partials[count - 1], fp64, in a fixed order (one workgroup).
+ * vtp_grad_clip_finalize: the same sum, then with gs = hyper[7] (the gradient multiplier of vtp_adamw_dev / vtp_adamw_ema_dev) and
+ *   max_norm = hyper[10]: *total_norm = gs * sqrt(sum), *coef = clamp(max_norm / (*total_norm + 1e-6), max=1) (NaN stays NaN, as in
+ *   torch), hyper[7] = gs * coef -- the AdamW kernels launched behind it read the clipped multiplier. */
+int vtp_sumsq_partials_count(long n);
+int vtp_sumsq_partials(const float* g, long n, double* partials, void* stream);
+int vtp_sum_partials(const double* partials, int count, double* sum, void* stream);
+int vtp_grad_clip_finalize(const double* partials, int count, float* hyper, float* total_norm, float* coef, void* stream);
 
 /* ---- CLIP text-tower glue + contrastive head (fp32; clip.hip) -------------------------------------------------
  * embed: x f32 [B*T, D] = table[ids] + pos (modeling_vtp.py:296-297); eot[b] = argmax_t ids[b,t] (text_global_pool

@@ -474,6 +474,27 @@ def adamw_ema_dev(p, g, m, v, teacher, n, hyper, nodecay4=None):
     _lib.check(_lib_().vtp_adamw_ema_dev(_p(p), _p(g), _p(m), _p(v), _p(teacher), _p(nodecay4), n, _p(hyper), _s()), "vtp_adamw_ema_dev")
 
 
+# ---- global gradient-norm clipping (vtp_amd/csrc/gradnorm.hip; torch.nn.utils.clip_grad_norm_, norm_type 2) ---------------------
+def sumsq_partials_count(n: int) -> int:
+    """number of fp64 partials sumsq_partials writes for a range of n elements (depends on n only)"""
+    return int(_lib_().vtp_sumsq_partials_count(n))
+
+
+def sumsq_partials(g, n, partials):
+    """partials[j] = sum of g[i]^2 over chunk j of g[0, n); g f32, partials f64 (a view at the range's slot base)"""
+    _lib.check(_lib_().vtp_sumsq_partials(_p(g), n, _p(partials), _s()), "vtp_sumsq_partials")
+
+
+def sum_partials(partials, count, out):
+    """out f64 [1] = partials[0:count].sum(), in a fixed order"""
+    _lib.check(_lib_().vtp_sum_partials(_p(partials), count, _p(out), _s()), "vtp_sum_partials")
+
+
+def grad_clip_finalize(partials, count, hyper, total_norm, coef):
+    """total_norm = hyper[7] * sqrt(sum(partials[0:count])); coef = clamp(hyper[10] / (total_norm + 1e-6), max=1); hyper[7] *= coef"""
+    _lib.check(_lib_().vtp_grad_clip_finalize(_p(partials), count, _p(hyper), _p(total_norm), _p(coef), _s()), "vtp_grad_clip_finalize")
+
+
 # ---- LPIPS (vtp_amd/csrc/lpips.hip, conv mode of gemm.hip) ---------------------------------------------------------------
 def _f3(v):
     import ctypes

@@ -252,6 +252,17 @@ def default_no_decay(name: str, shape: tuple) -> bool:
     return len(shape) < 2 or name.rsplit(".", 1)[-1] in NO_DECAY_NAMES
 
 
+def _max_norm_value(value) -> float:
+    """VTPTrainer(max_grad_norm=...): a number > 0 (float("inf") allowed)"""
+    try:
+        f = float(value)
+    except (TypeError, ValueError):
+        f = None
+    if f is None or isinstance(value, bool) or not f > 0:
+        raise ValueError(f"max_grad_norm must be None or a number > 0 (float('inf') allowed), got {value!r}")
+    return f
+
+
 CLIP_PREFIXES = ("visual_proj.", "text_transformer.", "token_embedding.", "positional_embedding", "ln_final.",
                  "text_projection", "logit_scale", "logit_bias")
 
@@ -268,9 +279,11 @@ class VTPTrainer:
                  clip_drop_rate: Optional[float] = None, ssl_drop_rate: Optional[float] = None, rec_drop_rate: Optional[float] = None,
                  drop_seed: int = 0, centering: str = "softmax", koleo_weight: float = 0.0, sk_iterations: int = 3,
                  shard_optimizer: Optional[bool] = None, grad_dtype: str = "fp32", no_decay="default",
-                 force_collectives: bool = False):
+                 force_collectives: bool = False, max_grad_norm: Optional[float] = None):
         """lpips: a vtp_amd.LPIPS module (frozen, weights loaded by the caller) -- with perceptual_weight > 0 the
-        reconstruction objective is rec_weight * L1 + perceptual_weight * mean_b LPIPS(decoded_b, image_b)."""
+        reconstruction objective is rec_weight * L1 + perceptual_weight * mean_b LPIPS(decoded_b, image_b).
+        max_grad_norm: global gradient-norm clipping in front of AdamW (torch.nn.utils.clip_grad_norm_, norm_type 2); the step's
+        pre-clip norm and coefficient land in self.grad_norm / self.grad_clip_coef (device tensors).  None: no clipping."""
         self.model = model
         # stochastic depth (block.py:207-289): the student trunk's rate per objective (clip_drop_rate / ssl_drop_rate / rec_drop_rate,
         # vtp.py:205-207; `drop_rate` sets all three) and the pixel decoder's drop_path_rate.  The objectives are items of ONE list
@@ -378,6 +391,24 @@ class VTPTrainer:
         # hyper-parameters live in device memory so that captured hipGraphs replay with per-step values
         self.hyper = torch.zeros(16, dtype=F32, device=st.device)  # [lr b1 b2 eps wd bc1 sqrt(bc2) 1/world | 1/teacher_temp ema_m ...]
         self.momentum_dev = self.hyper[9:10]  # EMA teacher momentum of this step
+        # GLOBAL GRADIENT-NORM CLIPPING (max_grad_norm; torch.nn.utils.clip_grad_norm_, norm_type 2) over exactly the gradient AdamW
+        # reads: every range the step's AdamW updates gets fp64 sum-of-squares partials (one per chunk, csrc/gradnorm.hip) in a static
+        # partials buffer, in the step's fixed launch order; one finalize launch adds them in a fixed order, writes grad_norm /
+        # grad_clip_coef and folds the coefficient into the gradient multiplier hyper[7] that the AdamW kernels read.  No float
+        # atomics: replicas that hold the same reduced gradients compute the same coefficient bit for bit.  max_norm lives in hyper[10]
+        # (a change between steps needs no re-capture).  With the optimizer lane, a bucket's lane work shrinks to its partials: its
+        # AdamW + EMA + weight refresh wait for the last bucket, in the optimizer leg.
+        self._clip = max_grad_norm is not None
+        self._max_grad_norm = _max_norm_value(max_grad_norm) if self._clip else None
+        self.grad_norm = self.grad_clip_coef = self._clip_partials = self._clip_sum = None
+        self._clip_ranges, self._clip_cursor, self._clip_keys = {}, 0, []
+        if self._clip:
+            self.grad_norm = torch.zeros(1, dtype=F32, device=st.device)       # pre-clip total norm of the last step
+            self.grad_clip_coef = torch.zeros(1, dtype=F32, device=st.device)  # its clip coefficient (1 = not clipped)
+            # every range of a step is disjoint from the others and lies inside the flat buffer, and each is a union of parameters
+            cap = ops.sumsq_partials_count(st.numel) + len(st.offsets)
+            self._clip_partials = torch.zeros(cap, dtype=torch.float64, device=st.device)
+            self._clip_sum = torch.zeros(1, dtype=torch.float64, device=st.device)  # sharded optimizer: this rank's sum, all-reduced
         self._hyper_ring = None
         self.use_graphs = use_graphs
         self._graphs = {}
@@ -396,6 +427,19 @@ class VTPTrainer:
         else:
             self._clip_unsupported = None
         self.sync_replicas()
+
+    @property
+    def max_grad_norm(self) -> Optional[float]:
+        return self._max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, value):
+        """a new clipping threshold takes effect from the next step (device memory: no re-capture); clipping itself is decided at
+        construction (its buffers and launches are part of the captured step)"""
+        if (value is None) != (self._max_grad_norm is None):
+            raise ValueError("max_grad_norm: clipping cannot be switched on or off after construction; build the trainer with "
+                             "max_grad_norm=None or with a number")
+        self._max_grad_norm = None if value is None else _max_norm_value(value)
 
     def sync_replicas(self):
         """Data-parallel replicas must start from identical state (what DDP's constructor does with its parameter / buffer
@@ -633,6 +677,7 @@ class VTPTrainer:
         self._reduced_ranges = []
         self._head_keys = []
         self._opt_queue, self._opt_done, self._hooks_done = [], [], set()
+        self._clip_cursor, self._clip_keys = 0, []
         del OVERLAP._deferred[:]  # (an aborted step must not leave an issue queued)
         self._opt_ema = ssl is not None
         lag = 2 if self.collectives else 1
@@ -707,8 +752,14 @@ class VTPTrainer:
     def _opt_launch(self, keys):
         if not keys:
             return
+        if self._clip:  # the bucket's update needs the global norm: the lane computes its partials, the optimizer leg updates it
+            self._clip_keys.append(keys)
+            plan = self._clip_plan(self._clip_views(keys))
+            work = lambda: self._clip_sumsq(plan)  # noqa: E731
+        else:
+            work = lambda: self._opt_update(keys)  # noqa: E731
         if not OVERLAP.enabled:  # VTP_OVERLAP=0 (single-stream attribution profiles): same kernels, in line
-            return self._opt_update(keys)
+            return work()
         main = torch.cuda.current_stream()
         if self._opt_stream is None:
             self._opt_stream = torch.cuda.Stream()
@@ -717,9 +768,57 @@ class VTPTrainer:
 
         def issue():  # ... and its kernels are issued behind the main stream's next kernel (engine.Overlap.defer: queue placement)
             with torch.cuda.stream(self._opt_stream):
-                self._opt_update(keys)
+                work()
         OVERLAP.defer(issue)
         self._opt_busy = True
+
+    # ---- global gradient-norm clipping ---------------------------------------------------------------------------------------
+    def _clip_views(self, keys):
+        """the flat-gradient ranges of one bucket (what its AdamW reads): [(f32 view, n)]"""
+        rs = self._clip_ranges.get(tuple(keys))
+        if rs is None:
+            rs = self._clip_ranges[tuple(keys)] = merge_ranges([r for k in keys for r in self._bucket_plan[k]])
+        return [(self.store.flat_g[lo:hi], hi - lo) for lo, hi in rs]
+
+    def _clip_plan(self, views):
+        """[(f32 view, n)] -> [(view, n, slot base)]: the next slots of the partials buffer.  The launch order of a step is fixed for an
+        objective set, so every step (eager, captured, replayed) and every rank lays its partials out the same way."""
+        plan = []
+        for g, n in views:
+            plan.append((g, n, self._clip_cursor))
+            self._clip_cursor += ops.sumsq_partials_count(n)
+        if self._clip_cursor > self._clip_partials.numel():
+            raise RuntimeError(f"gradient clipping: {self._clip_cursor} partials exceed the buffer ({self._clip_partials.numel()})")
+        return plan
+
+    def _clip_sumsq(self, plan):
+        for g, n, base in plan:
+            ops.sumsq_partials(g, n, self._clip_partials[base:])
+
+    def _clip_finalize(self, partials=None, count=None):
+        """grad_norm, grad_clip_coef and the clipped gradient multiplier hyper[7] from this step's partials"""
+        if partials is None:
+            partials, count = self._clip_partials, self._clip_cursor
+        ops.grad_clip_finalize(partials, count, self.hyper, self.grad_norm, self.grad_clip_coef)
+
+    def _clip_shards(self, recs):
+        """sharded optimizer: partials over this rank's fp32 chunks, their sum all-reduced over the group (a collective event of the
+        step), then the finalize over that one value"""
+        views = []
+        for rec in recs:
+            n = rec.b - rec.a
+            if n > 0:
+                if rec.g32 is not rec.g_out:
+                    rec.g32.copy_(rec.g_out)
+                views.append((rec.g32, n))
+        if views:
+            self._clip_sumsq(self._clip_plan(views))
+            ops.sum_partials(self._clip_partials, self._clip_cursor, self._clip_sum)
+        else:  # a rank that owns no element of this step's buckets
+            self._clip_sum.zero_()
+        dist, total = self.bucketer.dist, self._clip_sum
+        yield lambda: dist.all_reduce(total, group=self.group)
+        self._clip_finalize(total, 1)
 
     def _opt_join(self):
         OVERLAP.run_deferred()
@@ -926,10 +1025,12 @@ class VTPTrainer:
         ranges = merge_ranges(list(self.ranges_all if text is not None else self.ranges_rec) + (self.ranges_ssl if ssl is not None else []))
         if self.shard_optimizer:
             recs = self._shard_recs(ranges)
+            if self._clip:
+                yield from self._clip_shards(recs)  # (copies the bf16 chunks to fp32)
             for rec in recs:  # AdamW on this rank's chunk of every bucket (moments outside the own chunks are never touched)
                 n = rec.b - rec.a
                 if n > 0:
-                    if rec.g32 is not rec.g_out:
+                    if rec.g32 is not rec.g_out and not self._clip:
                         rec.g32.copy_(rec.g_out)
                     ops.adamw_dev(st.flat_p[rec.a:rec.b], rec.g32, self.m[rec.a:rec.b], self.v[rec.a:rec.b], None, n, self.hyper,
                                   None if self.nodecay4 is None else self.nodecay4[rec.a // 4:rec.b // 4])
@@ -939,13 +1040,23 @@ class VTPTrainer:
                 st.flat_p[rec.lo:rec.hi].copy_(rec.p_recv[:rec.hi - rec.lo])
         elif self.overlap_opt:
             # optimizer lane: most buckets were updated beside the backward; the last ones (announced with / right before FINAL) here
-            for keys in self._opt_queue:
+            queue = self._opt_queue
+            if self._clip:  # the lane took the partials only: those of the last buckets, the global norm, then every bucket's update
+                for keys in queue:
+                    if keys:
+                        self._clip_sumsq(self._clip_plan(self._clip_views(keys)))
+                self._clip_finalize()
+                queue = self._clip_keys + queue
+            for keys in queue:
                 if keys:
                     self._opt_update(keys)
             self._opt_queue = []
             if merge_ranges(self._opt_done) != list(ranges):
                 raise RuntimeError(f"optimizer lane: updated ranges {merge_ranges(self._opt_done)} differ from the step's parameter ranges {list(ranges)}")
         else:
+            if self._clip:
+                self._clip_sumsq(self._clip_plan([(st.flat_g[lo:hi], hi - lo) for lo, hi in ranges]))
+                self._clip_finalize()
             for lo, hi in ranges:
                 ops.adamw_dev(st.flat_p[lo:hi], st.flat_g[lo:hi], self.m[lo:hi], self.v[lo:hi], None, hi - lo, self.hyper,
                               None if self.nodecay4 is None else self.nodecay4[lo // 4:hi // 4])
@@ -1060,6 +1171,8 @@ class VTPTrainer:
                 1.0 / self.world, 1.0 / self.teacher_temp, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0]
         if self.ssl_head is not None:
             vals[9] = float(self.teacher_momentum)
+        if self._max_grad_norm is not None:
+            vals[10] = self._max_grad_norm  # the clip finalize multiplies vals[7] by this step's coefficient, in device memory
         # a ring of pinned staging rows: the host may run several steps ahead of the GPU (graph replay), so a row is rewritten
         # only after the async copy that read it has completed (its event); no per-step allocation
         if self._hyper_ring is None:
@@ -1223,6 +1336,7 @@ class VTPTrainer:
                     static_ssl = dict(plan=ssl["plan"], masks=ssl["masks"].clone(), dev={k: v.clone() for k, v in ssl["dev"].items()})
                 static_ssl["global"], static_ssl["local"] = ssl["global"].clone(), ssl["local"].clone()
             snap = (st.flat_p.clone(), self.m.clone(), self.v.clone())
+            hyper0 = self.hyper.clone() if self._clip else None  # the clip finalize rewrites hyper[7]
             if ssl is not None:
                 snap = snap + (self.center_dino.clone(), self.center_ibot.clone())
             # warm-up in eager mode on a side stream (allocates every workspace buffer, sets kernel attributes); the
@@ -1238,6 +1352,8 @@ class VTPTrainer:
             st.flat_p.copy_(snap[0])
             self.m.copy_(snap[1])
             self.v.copy_(snap[2])
+            if hyper0 is not None:
+                self.hyper.copy_(hyper0)
             if ssl is not None:
                 self.center_dino.copy_(snap[3])
                 self.center_ibot.copy_(snap[4])
