@@ -213,9 +213,10 @@ def _attn_ref(q, k, v, causal):
     return F.scaled_dot_product_attention(qf, kf, vf, is_causal=causal).transpose(1, 2)
 
 
-def _sdpa_bf16_errors(q, k, v, d_o, causal, ref_grads):
+def _sdpa_bf16_errors(q, k, v, d_o, causal, ref_grads, ref_out=None):
     """(relF, max|err|) of the bf16 execution of the reference op (F.scaled_dot_product_attention + autograd, attention.py:124)
-    against the fp32 gradients, per SDPA backend; returns the largest per tensor.  Test infrastructure only."""
+    against the fp32 gradients (and, given ref_out [B,N,h,64], the fp32 output: key "out"), per SDPA backend; returns the largest
+    per tensor.  Test infrastructure only."""
     from torch.nn.attention import SDPBackend, sdpa_kernel
     worst = {}
     ran = []
@@ -228,7 +229,10 @@ def _sdpa_bf16_errors(q, k, v, d_o, causal, ref_grads):
         except RuntimeError:
             continue
         ran.append(be.name)
-        for nm, gb, r in zip(("dq", "dk", "dv"), (qb.grad, kb.grad, vb.grad), ref_grads):
+        pairs = list(zip(("dq", "dk", "dv"), (qb.grad, kb.grad, vb.grad), ref_grads))
+        if ref_out is not None:
+            pairs.append(("out", ob.detach(), ref_out))
+        for nm, gb, r in pairs:
             d = gb.transpose(1, 2).float() - r
             e = (float(d.norm() / r.norm()), float(d.abs().max()))
             w = worst.get(nm, (0.0, 0.0))

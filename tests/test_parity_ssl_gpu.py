@@ -59,7 +59,7 @@ class Case:
     """Seeded VTP-B + DINO head (K = 65536) + EMA teacher, one SSL batch, and the oracle's results in fp32 / CPU autocast /
     CUDA autocast: head outputs, the SSL loss with its gradients, and the full step's loss with its gradients."""
 
-    def __init__(self, cfg_kw=None, heads=(HV, HD, HT), K=65536, res=256, seed=31, input_seed=7):
+    def __init__(self, cfg_kw=None, heads=(HV, HD, HT), K=65536, res=256, seed=31, input_seed=7, local_res=96):
         from oracle import vtp_oracle as O
         from vtp_amd import VTP, VTPConfig
         from vtp_amd.data import collate_ssl_masks
@@ -84,7 +84,7 @@ class Case:
         self.img = torch.randn(B, 3, res, res, generator=g)
         self.txt = _captions(B, m.config.text_context_length, m.config.text_vocab_size, input_seed + 1)
         self.gc = torch.randn(2 * B, 3, res, res, generator=g)
-        self.lc = torch.randn(N_LOCAL * B, 3, 96, 96, generator=g)
+        self.lc = torch.randn(N_LOCAL * B, 3, local_res, local_res, generator=g)
         col = collate_ssl_masks(2 * B, (res // 16, res // 16), 0.5, (0.1, 0.5), np.random.default_rng(input_seed + 4))
         self.col, self.masks = col, col["masks"]
         self.c_d = 0.3 * torch.randn(K, generator=g)

@@ -1177,7 +1177,9 @@ int attn_resident_fwd(const void* q, const void* k, const void* v, void* o, floa
   {
     const int ntiles = a.npad / 32, cols = N - 32 * (ntiles - 1);
     const bool odd = (ntiles & 1) && ntiles > 1;
-    if (!odd || cols <= RES_SPLIT_COLS) {  // two query tiles per wave, single pass, odd last tile split over the key blocks
+    // the v2 kernel is compiled for at most 4 waves (__launch_bounds__(256, 2)): 10 tiles (N = 289 .. 320) would need 5, a launch
+    // the runtime rejects -- those take the two-pass kernel below
+    if ((!odd || cols <= RES_SPLIT_COLS) && ntiles / 2 <= 4) {  // two query tiles per wave, single pass, odd last tile split over the key blocks
       const int waves = std::max(1, ntiles / 2);
       const int lds = 2 * a.npad * 128 + (odd ? waves * cols * 2 * 34 * 4 : 0);
       static long long* tbuf = nullptr;
