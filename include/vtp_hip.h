@@ -145,6 +145,15 @@ int vtp_norm_fwd(const float* x, const float* w, const float* b, void* y, float*
                  int kind, void* stream);
 int vtp_norm_bwd(const void* dy, const float* x, const float* w, const float* stats, const float* dres, float* dx,
                  void* dx_bf16, float* dw, float* db, float* dx_colsum, int M, int D, int kind, void* stream);
+/* vtp_norm_bwd where the patch rows of one list item -- rows prow0 + b*pN + t, b < pB, 1 <= t < pN -- take pvec[b] (f32 [pB, D]) on
+ * top of dy, summed in f32 inside the kernel: the gradient of a feature mean-pooled over those rows (vision_clip_feat = 'pooled',
+ * modeling_vtp.py:261-276) rides in the trunk's final-norm backward instead of a pass over dy.  D <= 1024. */
+int vtp_norm_bwd_pvec(const void* dy, const float* x, const float* w, const float* stats, const float* dres, float* dx,
+                      void* dx_bf16, float* dw, float* db, float* dx_colsum, const float* pvec, int prow0, int pB, int pN, int M,
+                      int D, int kind, void* stream);
+/* out f32 [B, D] = scale * sum_{t=1}^{N-1} x[b*N + t] over the bf16 token rows x [B*N, D] of one list item (row 0 of every image is
+ * its cls token and is skipped); scale = 1 / (N - 1) is the mean of the patch tokens.  N >= 2, D % 4 == 0. */
+int vtp_pool_patch_rows(const void* x, float* out, int B, int N, int D, float scale, void* stream);
 
 /* ---- RoPE (attention.py:12-23,70-89) ----------------------------------------------------------
  * In place on the q and k thirds of a packed qkv bf16 [B*N, 3*D] buffer (head h at column h*64 of each third).

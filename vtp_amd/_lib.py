@@ -14,6 +14,9 @@ SIGNATURES = {
     "vtp_gemm_nt": [_P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P],
     "vtp_norm_fwd": [_P, _P, _P, _P, _P, _I, _I, _F, _I, _P],
     "vtp_norm_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],  # dy x w stats dres dx dxb dw db dxsum M D kind stream
+    # ... + pvec prow0 pB pN in front of M
+    "vtp_norm_bwd_pvec": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "vtp_pool_patch_rows": [_P, _P, _I, _I, _I, _F, _P],
     "vtp_rope_qk": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vtp_attn_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _L, _L, _L, _L, _F, _I, _P],
     "vtp_attn_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _L, _L, _L, _L, _F, _I, _P],

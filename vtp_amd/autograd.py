@@ -231,9 +231,11 @@ class SSLStudent(torch.autograd.Function):
             d_logits[nl:nl + B2].copy_(d_global)
         if d_patch is not None and nm > 0:
             d_logits[nl + B2:nl + B2 + nm].copy_(d_patch)
-        dX = head.backward(d_logits, out["head_ctx"])  # bf16 [Ts, D]
+        dX = head.backward(d_logits, out["head_ctx"])  # bf16 [Ts, in_dim]
         if d_cls is not None:  # student_global_cls_tokens are the head's own input rows
             dX[nl:nl + B2] += d_cls.to(BF)
+        from .vtp import ssl_head_input_bwd
+        dX = ssl_head_input_bwd(model, out, dX)  # bf16 [Ts, D] (bottleneck dgrad when the heads read the latents)
         tctx = out["ctx"]
         d_xnf = tr.d_xnf_buffer(tctx)
         d_xnf.zero_()
@@ -288,23 +290,28 @@ class HeadLinear(torch.autograd.Function):
 
 
 class SumTokens(torch.autograd.Function):
-    """tokens f32 [B, n, D] -> their sum over n, f32 [B, D] (the mean pooling of vision_clip_feat = 'pooled'; the 1 / n rides in the
-    following projection's alpha)"""
+    """final-norm tokens f32 [B, N, D] (bf16 values: TrunkTokens) -> the sum of the patch tokens 1..N-1, f32 [B, D] (the mean pooling of
+    vision_clip_feat = 'pooled'; the 1 / (N - 1) rides in the following projection's alpha).  One pool_patch_rows launch for the
+    batch; the cls row gets no gradient."""
 
     @staticmethod
     def forward(ctx, tokens):
-        B, n, D = tokens.shape
-        t = tokens.contiguous().float()
-        out = torch.zeros(B, D, dtype=F32, device=t.device)
-        for b in range(B):
-            ops.strided_rowsum(t[b], D, out[b], n, D)
-        ctx.shape = (B, n, D)
+        B, N, D = tokens.shape
+        # the kernel reads the bf16 token rows the fused step keeps; these f32 tokens are bf16 values (TrunkTokens), so the copy is
+        # exact -- one [B*N, D] pass on the autograd path only
+        t = torch.empty(B * N, D, dtype=BF, device=tokens.device)
+        ops.cast_f32_bf16(tokens.contiguous().float(), t, B * N * D)
+        out = torch.empty(B, D, dtype=F32, device=tokens.device)
+        ops.pool_patch_rows(t, out, B, N, D, scale=1.0)
+        ctx.shape = (B, N, D)
         return out
 
     @staticmethod
     def backward(ctx, d):
-        B, n, D = ctx.shape
-        return d[:, None, :].expand(B, n, D).contiguous()
+        B, N, D = ctx.shape
+        g = torch.zeros(B, N, D, dtype=F32, device=d.device)
+        g[:, 1:] = d[:, None, :]
+        return g
 
 
 class L2Normalize(torch.autograd.Function):

@@ -114,16 +114,35 @@ class TextEngine:
 class ClipHead:
     """visual_proj + F.normalize on both modalities + contrastive loss with (optional) cross-rank feature exchange."""
 
-    def __init__(self, store: ParamStore, vproj, Dv: int, Dt: int):
-        self.store, self.vproj, self.Dv, self.Dt = store, vproj, Dv, Dt
-        self.fused_ok = vproj.K == Dv  # cls token of the un-bottlenecked trunk output (the GEMMs below read K = Dv columns)
+    def __init__(self, store: ParamStore, vproj, Dv: int, Dt: int, feat: str = "cls", trunk=None):
+        """feat: vision_clip_feat ('cls' | 'pooled': the cls token or the mean of the patch tokens, modeling_vtp.py:261-276); trunk: the
+        TrunkEngine whose feature_bottleneck the feature goes through first (vision_bottleneck_ae_only=False), or None"""
+        if feat not in ("cls", "pooled"):
+            raise ValueError(f"vision_clip_feat must be 'cls' or 'pooled', got {feat!r}")
+        self.store, self.vproj, self.Dv, self.Dt, self.feat, self.trunk = store, vproj, Dv, Dt, feat, trunk
+        assert vproj.K == (trunk.bott_dim if trunk is not None else Dv), "visual_proj input width does not match the CLIP feature"
         self.ws = Workspace(store.device)
 
     def image_features(self, xnf: torch.Tensor, B: int, N: int) -> torch.Tensor:
-        """cls rows of the final-norm token matrix (bf16 [B*N, Dv]) -> un-normalised image features f32 [B, Dt]."""
-        assert self.fused_ok, "ClipHead: visual_proj input width != trunk width (bottlenecked CLIP feature): use the autograd path"
-        f = self.ws.get(f"f_img{B}", (B, self.Dt), F32)
-        ops.gemm_nt(xnf, self.vproj.w, f, M=B, N=self.Dt, K=self.Dv, lda=N * self.Dv, epi=EPI_F32)
+        """final-norm token rows of one list item (bf16 [B*N, Dv], image b = rows b*N..) -> un-normalised image features f32 [B, Dt]:
+        the cls row or the mean of the patch rows (one pool_patch_rows launch), through the bottleneck when there is one, then
+        visual_proj (B-row GEMMs; the bottleneck of the pooled feature is applied after the mean: it is linear)."""
+        ws, D = self.ws, self.Dv
+        if self.feat == "cls":
+            x, lda = xnf, N * D  # strided rows: row b = token b*N
+        else:
+            pooled = ws.get(f"pool{B}", (B, D), F32)
+            ops.pool_patch_rows(xnf, pooled, B, N, D)
+            x = ws.get(f"pool_b{B}", (B, D), BF)
+            ops.cast_f32_bf16(pooled, x, B * D)
+            lda = D
+        self._x = (x, lda)
+        if self.trunk is not None:
+            z = self.trunk.bott_rows(x, B, ws.get(f"z{B}", (B, self.trunk.bott_dim), BF), lda=lda)
+            x, lda = z, z.stride(0)
+        self._in = x
+        f = ws.get(f"f_img{B}", (B, self.Dt), F32)
+        ops.gemm_nt(x, self.vproj.w, f, M=B, N=self.Dt, K=self.vproj.K, lda=lda, epi=EPI_F32)
         return f
 
     def normalize(self, f: torch.Tensor, tag: str):
@@ -139,10 +158,32 @@ class ClipHead:
         ops.l2norm_bwd(dy, y, inv, dx, B, D)
         return dx
 
-    def image_backward(self, d_f: torch.Tensor, xnf: torch.Tensor, d_xnf: torch.Tensor, B: int, N: int):
-        """d_f f32 [B, Dt] -> dW(visual_proj) and the cls rows of d_xnf (bf16 [B*N, Dv])."""
-        d_f_b = self.ws.get(f"d_f_b{B}", (B, self.Dt), BF)
+    def image_backward(self, d_f: torch.Tensor, xnf: torch.Tensor, d_xnf: torch.Tensor, B: int, N: int) -> Optional[torch.Tensor]:
+        """d_f f32 [B, Dt] -> dW(visual_proj) and the feature's gradient: cls feature -- written to the cls rows of d_xnf (bf16
+        [B*N, Dv]); pooled feature -- returned as the per-image vector f32 [B, Dv] (already divided by the N - 1 patch rows) that the
+        trunk's final-norm backward adds to every patch row (TrunkEngine.backward(pool=...)).  Through the bottleneck, its weight
+        gradient is queued on the trunk (TrunkEngine.bott_rows_bwd)."""
+        ws, D = self.ws, self.Dv
+        if self.feat == "pooled" and D > 1024:  # (the final-norm backward that takes the pooled gradient: rows up to 1024 wide)
+            raise NotImplementedError(f"the fused step with vision_clip_feat='pooled' needs vision_embed_dim <= 1024 (got {D})")
+        d_f_b = ws.get(f"d_f_b{B}", (B, self.Dt), BF)
         ops.cast_f32_bf16(d_f, d_f_b, B * self.Dt)
-        cls_rows = xnf.view(B, N * self.Dv)[:, :self.Dv]        # strided views: row b = token b*N
-        d_cls_rows = d_xnf.view(B, N * self.Dv)[:, :self.Dv]
-        linear_bwd(self.ws, "vproj", self.vproj, d_f_b, cls_rows, B, d_cls_rows)
+        cls_rows = xnf.view(B, N * D)[:, :D]        # strided views: row b = token b*N
+        d_cls_rows = d_xnf.view(B, N * D)[:, :D]
+        tr = self.trunk
+        if tr is None and self.feat == "cls":
+            linear_bwd(ws, "vproj", self.vproj, d_f_b, cls_rows, B, d_cls_rows)
+            return None
+        pvec = ws.get(f"pvec{B}", (B, D), F32) if self.feat == "pooled" else None
+        x = cls_rows if self.feat == "cls" else self._x[0]
+        if tr is None:  # pooled, un-bottlenecked: d_pooled / (N - 1) = d_f Wv / (N - 1)
+            linear_bwd(ws, "vproj", self.vproj, d_f_b, x, B, None, need_dx=False)
+            ops.gemm_nt(d_f_b, self.vproj.wT, pvec, M=B, N=D, K=self.Dt, epi=EPI_F32, alpha=1.0 / (N - 1))
+            return pvec
+        dz = ws.get(f"dz{B}", (B, tr.bott_dim), BF)
+        linear_bwd(ws, "vproj", self.vproj, d_f_b, self._in, B, dz)
+        if self.feat == "cls":
+            tr.bott_rows_bwd(dz, x, B, d_cls_rows)
+        else:  # the pooled latent's gradient g enters every patch row as (g W_bott) / (N - 1); dW_bott += g^T mean(patch rows)
+            tr.bott_rows_bwd(dz, x, B, pvec, alpha=1.0 / (N - 1))
+        return pvec

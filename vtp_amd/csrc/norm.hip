@@ -87,12 +87,16 @@ __global__ __launch_bounds__(256) void norm_fwd_kernel(const float* __restrict__
   }
 }
 
-template <int KIND, int NC>
+// PV: the rows prow0 + b*pN + t (b < pB, 1 <= t < pN) -- the patch rows of one list item -- take pvec[b] (f32 [pB, D]) on top of
+// dy, added in f32 before anything reads dy (the gradient of a mean-pooled feature, spread over the rows it averaged)
+template <int KIND, int NC, bool PV = false>
 __global__ __launch_bounds__(256, 2) void norm_bwd_kernel(const bf16* __restrict__ dy, const float* __restrict__ x,
                                                        const float* __restrict__ w, const float* __restrict__ stats,
                                                        const float* __restrict__ dres, float* __restrict__ dx,
                                                        bf16* __restrict__ dxb, float* __restrict__ dw, float* __restrict__ db,
-                                                       float* __restrict__ dxsum, int M, int D) {
+                                                       float* __restrict__ dxsum, int M, int D,
+                                                       const float* __restrict__ pvec = nullptr, int prow0 = 0, int pB = 0,
+                                                       int pN = 1) {
   constexpr int R = NC <= 3 ? 2 : 1;  // rows in flight per wave: the x / dy loads of all R rows are issued before the first reduction
   const int lane = threadIdx.x & 63;
   const int wv_id = threadIdx.x >> 6;
@@ -137,11 +141,19 @@ __global__ __launch_bounds__(256, 2) void norm_bwd_kernel(const bf16* __restrict
       if (row >= M) break;
       f32x4 xh[NC], g[NC];
       float s1 = 0.f, s2 = 0.f;
+      const float* pv = nullptr;
+      if constexpr (PV) {
+        const int loc = row - prow0;
+        if (loc >= 0 && loc < pB * pN && loc % pN != 0) pv = pvec + (size_t)(loc / pN) * D;
+      }
 #pragma unroll
       for (int c = 0; c < NC; ++c) {
         const int col = (c * 64 + lane) * 4;
         if (col < D) {
           f32x4 gyf = __builtin_convertvector(gy[r][c], f32x4);
+          if constexpr (PV) {
+            if (pv) gyf += *(const f32x4*)(pv + col);
+          }
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             xh[c][e] = (xv[r][c][e] - mean[r]) * rstd[r];
@@ -200,6 +212,40 @@ __global__ __launch_bounds__(256, 2) void norm_bwd_kernel(const bf16* __restrict
   }
 }
 
+// out[b] = scale * sum_{t=1}^{N-1} x[b*N + t]: one workgroup per (image, 256 columns); its 8 waves take every 8th row, four rows in
+// flight per wave, and are summed through LDS in a fixed order (deterministic, no atomics)
+constexpr int POOL_WAVES = 8;
+
+__global__ __launch_bounds__(POOL_WAVES * 64) void pool_patch_rows_kernel(const bf16* __restrict__ x, float* __restrict__ out, int N,
+                                                                         int D, float scale) {
+  const int lane = threadIdx.x & 63;
+  const int wv = threadIdx.x >> 6;
+  const int col = (blockIdx.x * 64 + lane) * 4;
+  const int b = blockIdx.y;
+  f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+  if (col < D) {
+    const bf16* xb = x + (size_t)b * N * D + col;
+    int t = 1 + wv;
+    for (; t + 3 * POOL_WAVES < N; t += 4 * POOL_WAVES) {
+      bf16x4 v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[u] = *(const bf16x4*)(xb + (size_t)(t + u * POOL_WAVES) * D);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) acc += __builtin_convertvector(v[u], f32x4);
+    }
+    for (; t < N; t += POOL_WAVES) acc += __builtin_convertvector(*(const bf16x4*)(xb + (size_t)t * D), f32x4);
+  }
+  __shared__ f32x4 red[POOL_WAVES][64];
+  red[wv][lane] = acc;
+  __syncthreads();
+  if (wv == 0 && col < D) {
+    f32x4 s = red[0][lane];
+#pragma unroll
+    for (int k = 1; k < POOL_WAVES; ++k) s += red[k][lane];
+    *(f32x4*)(out + (size_t)b * D + col) = s * scale;
+  }
+}
+
 }  // namespace vtp
 using namespace vtp;
 
@@ -239,13 +285,7 @@ extern "C" int vtp_norm_fwd_e4m3(const float* x, const float* w, const float* b,
   return check_launch("norm_fwd_e4m3");
 }
 
-extern "C" int vtp_norm_bwd(const void* dy, const float* x, const float* w, const float* stats, const float* dres,
-                            float* dx, void* dx_bf16, float* dw, float* db, float* dx_colsum, int M, int D, int kind,
-                            void* stream) {
-  VTP_REQUIRE(dy && x && w && stats && dx, "vtp_norm_bwd: null pointer");
-  VTP_REQUIRE(!dx_colsum || dx_bf16, "vtp_norm_bwd: dx_colsum sums the bf16 output and needs dx_bf16");
-  VTP_REQUIRE(M > 0 && D > 0 && D % 4 == 0 && D <= NORM_MAXC * 256, "vtp_norm_bwd: need 0 < D <= 2048, D %% 4 == 0 (D=%d)", D);
-  VTP_REQUIRE(kind == 0 || kind == 1, "vtp_norm_bwd: kind must be 0 or 1");
+static int norm_bwd_blocks(int M, int D) {
   int blocks = cdiv(M, D <= 768 ? 8 : 4);
   // every block ends with one atomic per column and target (dw, db, the column sums of dx): with 1024 blocks that is 1024 adds queued on
   // each of ~2 300 addresses, ~11 us of serialised atomics -- a third of the launch at 8 192 rows.  Fewer, longer-running blocks
@@ -257,11 +297,64 @@ extern "C" int vtp_norm_bwd(const void* dy, const float* x, const float* w, cons
     cap_env = e && atoi(e) > 0 ? atoi(e) : 0;
   }
   const int cap = cap_env ? cap_env : (M >= 24576 ? 512 : (M >= 4096 ? 256 : 128));
-  if (blocks > cap) blocks = cap;
-  dim3 grid(blocks), block(256);
+  return blocks > cap ? cap : blocks;
+}
+
+extern "C" int vtp_norm_bwd(const void* dy, const float* x, const float* w, const float* stats, const float* dres,
+                            float* dx, void* dx_bf16, float* dw, float* db, float* dx_colsum, int M, int D, int kind,
+                            void* stream) {
+  VTP_REQUIRE(dy && x && w && stats && dx, "vtp_norm_bwd: null pointer");
+  VTP_REQUIRE(!dx_colsum || dx_bf16, "vtp_norm_bwd: dx_colsum sums the bf16 output and needs dx_bf16");
+  VTP_REQUIRE(M > 0 && D > 0 && D % 4 == 0 && D <= NORM_MAXC * 256, "vtp_norm_bwd: need 0 < D <= 2048, D %% 4 == 0 (D=%d)", D);
+  VTP_REQUIRE(kind == 0 || kind == 1, "vtp_norm_bwd: kind must be 0 or 1");
+  dim3 grid(norm_bwd_blocks(M, D)), block(256);
   if (kind == 0)
     NORM_DISPATCH(norm_bwd_kernel, 0, (const bf16*)dy, x, w, stats, dres, dx, (bf16*)dx_bf16, dw, db, dx_colsum, M, D);
   else
     NORM_DISPATCH(norm_bwd_kernel, 1, (const bf16*)dy, x, w, stats, dres, dx, (bf16*)dx_bf16, dw, db, dx_colsum, M, D);
   return check_launch("norm_bwd");
+}
+
+template <int KIND>
+static void launch_norm_bwd_pvec(dim3 grid, hipStream_t s, const bf16* dy, const float* x, const float* w, const float* stats,
+                                 const float* dres, float* dx, bf16* dxb, float* dw, float* db, float* dxsum, int M, int D,
+                                 const float* pvec, int prow0, int pB, int pN) {
+  const int nc = cdiv(D, 256);
+#define NORM_PV(NC) \
+  hipLaunchKernelGGL((norm_bwd_kernel<KIND, NC, true>), grid, dim3(256), 0, s, dy, x, w, stats, dres, dx, dxb, dw, db, dxsum, M, D, \
+                     pvec, prow0, pB, pN)
+  // (no NC = 8 variant: the wide rows leave no registers for the vector's read -- it spilled ~2 100 VGPRs)
+  if (nc <= 1) NORM_PV(1);
+  else if (nc == 2) NORM_PV(2);
+  else if (nc == 3) NORM_PV(3);
+  else NORM_PV(4);
+#undef NORM_PV
+}
+
+extern "C" int vtp_norm_bwd_pvec(const void* dy, const float* x, const float* w, const float* stats, const float* dres, float* dx,
+                                 void* dx_bf16, float* dw, float* db, float* dx_colsum, const float* pvec, int prow0, int pB, int pN,
+                                 int M, int D, int kind, void* stream) {
+  VTP_REQUIRE(dy && x && w && stats && dx && pvec, "vtp_norm_bwd_pvec: null pointer");
+  VTP_REQUIRE(!dx_colsum || dx_bf16, "vtp_norm_bwd_pvec: dx_colsum sums the bf16 output and needs dx_bf16");
+  VTP_REQUIRE(M > 0 && D > 0 && D % 4 == 0 && D <= 1024, "vtp_norm_bwd_pvec: need 0 < D <= 1024, D %% 4 == 0 (D=%d)", D);
+  VTP_REQUIRE(kind == 0 || kind == 1, "vtp_norm_bwd_pvec: kind must be 0 or 1");
+  VTP_REQUIRE(pB > 0 && pN >= 2 && prow0 >= 0 && (long)prow0 + (long)pB * pN <= M,
+              "vtp_norm_bwd_pvec: segment rows [%d, %d + %d*%d) must lie in [0, M=%d), N >= 2", prow0, prow0, pB, pN, M);
+  dim3 grid(norm_bwd_blocks(M, D));
+  if (kind == 0)
+    launch_norm_bwd_pvec<0>(grid, (hipStream_t)stream, (const bf16*)dy, x, w, stats, dres, dx, (bf16*)dx_bf16, dw, db, dx_colsum, M, D,
+                            pvec, prow0, pB, pN);
+  else
+    launch_norm_bwd_pvec<1>(grid, (hipStream_t)stream, (const bf16*)dy, x, w, stats, dres, dx, (bf16*)dx_bf16, dw, db, dx_colsum, M, D,
+                            pvec, prow0, pB, pN);
+  return check_launch("norm_bwd_pvec");
+}
+
+extern "C" int vtp_pool_patch_rows(const void* x, float* out, int B, int N, int D, float scale, void* stream) {
+  VTP_REQUIRE(x && out, "vtp_pool_patch_rows: null pointer");
+  VTP_REQUIRE(B > 0 && N >= 2 && D > 0 && D % 4 == 0, "vtp_pool_patch_rows: need B > 0, N >= 2, D %% 4 == 0 (B=%d N=%d D=%d)", B, N, D);
+  VTP_REQUIRE((long)B * N * D < (1L << 40), "vtp_pool_patch_rows: matrix too large");
+  hipLaunchKernelGGL(pool_patch_rows_kernel, dim3(cdiv(D, 256), B), dim3(POOL_WAVES * 64), 0, (hipStream_t)stream, (const bf16*)x, out,
+                     N, D, scale);
+  return check_launch("pool_patch_rows");
 }

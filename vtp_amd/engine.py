@@ -1159,6 +1159,10 @@ class TrunkEngine:
         self.bott_dim = cfg.vision_feature_bottleneck
         self.bott = store.lin(self.prefix + "feature_bottleneck.weight", None, self.bott_dim, self.D) \
             if store.has(self.prefix + "feature_bottleneck.weight") else None
+        # weight-gradient problems of the bottleneck on row sets other than the latent item's patch rows (the CLIP feature and the SSL
+        # head rows when vision_bottleneck_ae_only=False): run by backward() in front of the latent item's own, on the main stream, so
+        # that every contribution is in dW before the trunk's tail bucket is announced and no two of them write dW concurrently
+        self.bott_wgrads: List[tuple] = []
         self.ws: Dict[tuple, Workspace] = {}
         # train-time RoPE coordinate augmentations (embeddings.py:155-171): one draw per block and list item
         self.rope_aug = RopeAugmenter(self.periods, self.depth, True, getattr(cfg, "vision_rope_shift_coords", None),
@@ -1237,6 +1241,19 @@ class TrunkEngine:
                     epi=EPI_F32 if out_f32 else EPI_BF16, a_remap=(g.hw, 1))
         return lat
 
+    def bott_rows(self, x: torch.Tensor, R: int, out: torch.Tensor, lda: Optional[int] = None) -> torch.Tensor:
+        """bottleneck on R arbitrary rows: out bf16 [R, 64] = x[R, D] W_bott^T (x bf16, row stride lda)"""
+        ops.gemm_nt(x, self.bott.w, out, M=R, N=self.bott_dim, K=self.D, lda=x.stride(0) if lda is None else lda, epi=EPI_BF16)
+        return out
+
+    def bott_rows_bwd(self, dz: torch.Tensor, x: torch.Tensor, R: int, dx: Optional[torch.Tensor], alpha: float = 1.0):
+        """backward of bott_rows: dx (bf16 [R, D], or f32 with alpha) = alpha * dz W_bott now; dW_bott += dz^T x is queued for
+        backward() (self.bott_wgrads).  dz bf16 [R, 64]; x bf16 [R, D] (any row stride)."""
+        if dx is not None:
+            ops.gemm_nt(dz, self.bott.wT, dx, M=R, N=self.D, K=self.bott_dim, ldc=dx.stride(0),
+                        epi=EPI_F32 if dx.dtype == F32 else EPI_BF16, alpha=alpha)
+        self.bott_wgrads.append((dz, x, R))
+
     def d_xnf_buffer(self, ctx=None) -> torch.Tensor:
         """bf16 [M, D] gradient w.r.t. the final-norm tokens of the last forward (all items, row-concatenated).  The patch
         rows of the latent item are written by backward() (bottleneck dgrad); every other row must be written (or zeroed)
@@ -1244,9 +1261,12 @@ class TrunkEngine:
         c = self._ctx if ctx is None else ctx
         return c.ws.get("b.d_xnf", (c.M, self.D), BF, zero=True)
 
-    def backward(self, d_lat: Optional[torch.Tensor], ctx=None, lat_seg: int = 0, want_dimg: bool = False):
+    def backward(self, d_lat: Optional[torch.Tensor], ctx=None, lat_seg: int = 0, want_dimg: bool = False, pool=None):
         """d_lat: bf16 [B*hw, 64] grad of latents(seg=lat_seg), or None.  Accumulates every trunk parameter gradient into
         store.flat_g.  Generator (see Stack.backward): yields "tail", then ("block", i) per block.
+        pool = (seg, pvec f32 [B_seg, D]): the gradient of a mean over the patch rows of item `seg`, already divided by their count --
+        added to those rows of d_xnf in f32 inside the final-norm backward (norm_bwd_pvec).
+        The queued bottleneck weight-gradient problems (bott_rows_bwd) run here, in front of the latent item's own.
         want_dimg: also form the gradient w.r.t. the input images (PatchEmbed backward, embeddings.py:61-70: d_tokens[patch rows]
         W_pe folded back to pixels) -- ctx.d_img[i] f32 [B_i,3,H_i,W_i] for list item i (freshly allocated: this path is the eager
         autograd boundary, never a captured segment; the caller pops the entry -- ctx.take_d_img(i) -- so the tensor does not outlive the
@@ -1257,15 +1277,23 @@ class TrunkEngine:
         c = self._ctx
         ws, M, D = c.ws, c.M, self.D
         d_xnf = ws.get("b.d_xnf", (M, D), BF, zero=True)  # rows stay zero unless a head wrote them before backward()
+        wgrads, self.bott_wgrads = self.bott_wgrads, []
+        for dz, x, R in wgrads:
+            linear_bwd(ws, "bott", self.bott, dz, x, R, None, need_dx=False)
         if d_lat is not None:
             g = c.segs[lat_seg]
             linear_bwd(ws, "bott", self.bott, d_lat, c.xnf[g.row0:], g.B * g.hw, d_xnf[g.row0:], x_remap=(g.hw, 1),
                        dx_remap=(g.hw, 1))
         dx = ws.get("b.dxt", (M, D), F32)
         dx_b = ws.get("b.dxt_b", (M, D), BF)
-        ops.norm_bwd(d_xnf, c.xl, st.p(self.prefix + "norm.weight"), c.stf, None, dx, dx_b, st.g(self.prefix + "norm.weight"),
-                     st.g(self.prefix + "norm.bias") if self.kind == ops.NORM_LN else None, M, D, self.kind,
-                     dx_colsum=self.stack.w3_colsum_target(self.depth - 1))
+        nw, nb = st.g(self.prefix + "norm.weight"), st.g(self.prefix + "norm.bias") if self.kind == ops.NORM_LN else None
+        if pool is None:
+            ops.norm_bwd(d_xnf, c.xl, st.p(self.prefix + "norm.weight"), c.stf, None, dx, dx_b, nw, nb, M, D, self.kind,
+                         dx_colsum=self.stack.w3_colsum_target(self.depth - 1))
+        else:
+            g = c.segs[pool[0]]
+            ops.norm_bwd_pvec(d_xnf, c.xl, st.p(self.prefix + "norm.weight"), c.stf, None, dx, dx_b, nw, nb, M, D, self.kind, pool[1],
+                              g.row0, g.B, g.N, dx_colsum=self.stack.w3_colsum_target(self.depth - 1))
         OVERLAP.join()
         yield "tail"
         g_cls, g_mask = st.g(self.prefix + "cls_token"), st.g(self.prefix + "mask_token")

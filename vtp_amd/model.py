@@ -244,7 +244,9 @@ class VTPModel(nn.Module):
                 self._vproj = st.lin("visual_proj.weight", None, self.visual_proj.weight.shape[0],
                                      self.visual_proj.weight.shape[1])
                 self._text = TextEngine(st, self.config)
-                self._clip = ClipHead(st, self._vproj, self.config.vision_embed_dim, self.config.text_embed_dim)
+                bott = not self.config.vision_bottleneck_ae_only and self._trunk.bott is not None
+                self._clip = ClipHead(st, self._vproj, self.config.vision_embed_dim, self.config.text_embed_dim,
+                                      feat=self.config.vision_clip_feat, trunk=self._trunk if bott else None)
             self._build_extra_engines(st)
             st.finalize()
             self._store = st
@@ -471,7 +473,7 @@ class VTPModel(nn.Module):
                 if c.vision_clip_feat == "cls":
                     feat, scale = tokens[:, 0], 1.0
                 else:  # mean over the patch tokens: the sum here, 1 / hw in the next projection (linear maps commute with the mean)
-                    feat, scale = ag.SumTokens.apply(tokens[:, 1:]), 1.0 / (tokens.shape[1] - 1)
+                    feat, scale = ag.SumTokens.apply(tokens), 1.0 / (tokens.shape[1] - 1)
                 if not c.vision_bottleneck_ae_only and self._trunk.bott is not None:
                     feat, scale = ag.HeadLinear.apply(feat, a, self, self._trunk.bott, scale, self.trunk.feature_bottleneck.weight.requires_grad), 1.0
                 feat = ag.HeadLinear.apply(feat, a, self, self._vproj, scale, self.visual_proj.weight.requires_grad)

@@ -58,6 +58,21 @@ def norm_bwd(dy, x, w, stats, dres, dx, dxb, dw, db, M, D, kind, dx_colsum=None)
                                     M, D, kind, _s()), "vtp_norm_bwd")
 
 
+def norm_bwd_pvec(dy, x, w, stats, dres, dx, dxb, dw, db, M, D, kind, pvec, row0, B, N, dx_colsum=None):
+    """norm_bwd with pvec f32 [B, D] added to dy of the patch rows row0 + b*N + t (t >= 1) of one list item, in f32"""
+    _lib.check(_lib_().vtp_norm_bwd_pvec(_p(dy), _p(x), _p(w), _p(stats), _p(dres), _p(dx), _p(dxb), _p(dw), _p(db), _p(dx_colsum),
+                                         _p(pvec), row0, B, N, M, D, kind, _s()), "vtp_norm_bwd_pvec")
+
+
+def pool_patch_rows(x, out, B, N, D, scale=None):
+    """out f32 [B, D] = scale * sum of the patch rows 1..N-1 of every image of the bf16 token rows x [B*N, D]; default scale 1/(N-1): the
+    mean pooling of vision_clip_feat = 'pooled'"""
+    assert x.dtype == torch.bfloat16 and x.is_contiguous() and x.numel() >= B * N * D and out.dtype == torch.float32
+    assert out.is_contiguous() and out.numel() >= B * D
+    s = 1.0 / (N - 1) if scale is None else float(scale)
+    _lib.check(_lib_().vtp_pool_patch_rows(_p(x), _p(out), B, N, D, s, _s()), "vtp_pool_patch_rows")
+
+
 def rope_qk(qkv, sin, cos, B, N, heads, prefix, inverse=False):
     _lib.check(_lib_().vtp_rope_qk(_p(qkv), _p(sin), _p(cos), B, N, heads, prefix, int(inverse), _s()), "vtp_rope_qk")
 

@@ -418,12 +418,12 @@ class VTPTrainer:
         # stream's kernels, which put every block's closing norm backward on the weight-gradient branch's queue (engine.Overlap.defer);
         # with the main chain on one queue the segment boundaries are what is left between blocks: 44.72 -> 44.38 ms, same box
         self.single_graph = (not self.collectives) and os.environ.get("VTP_SINGLE_GRAPH", "1") in ("1", "true", "on")
-        if self.text is not None and (model.config.vision_clip_feat != "cls" or not model.config.vision_bottleneck_ae_only):
-            self._clip_unsupported = ("the fused trainer implements the cls-token / un-bottlenecked CLIP image feature only "
-                                      "(vision_clip_feat='cls', vision_bottleneck_ae_only=True); other settings train through "
-                                      "the autograd path (model(...); loss.backward())")
-        elif self.text is not None and model.config.text_pool_type == "none":
+        if self.text is not None and model.config.text_pool_type == "none":
             self._clip_unsupported = "the contrastive objective needs pooled text features (text_pool_type argmax | first | last)"
+        elif self.text is not None and model.config.vision_clip_feat == "pooled" and model.config.vision_embed_dim > 1024:
+            # the final-norm backward that takes the pooled feature's gradient (vtp_norm_bwd_pvec) has rows up to 1024 wide
+            self._clip_unsupported = (f"vision_clip_feat='pooled' needs vision_embed_dim <= 1024 on the fused step "
+                                      f"(got {model.config.vision_embed_dim}); the autograd path (model(...); loss.backward()) has no limit")
         else:
             self._clip_unsupported = None
         self.sync_replicas()
@@ -577,8 +577,10 @@ class VTPTrainer:
                     d_logits, Ts, K)
         dX = head.backward(d_logits, out["head_ctx"])
         if self.koleo_weight > 0:  # KoLeo on the student's global cls tokens = rows [nl, nl + B2) of the head input, per view
-            self._koleo(ws, out["Xs"], dX, nl, B2, D)
+            self._koleo(ws, out["Hs"], dX, nl, B2, head.Din)
         yield ["dino_head"]
+        from .vtp import ssl_head_input_bwd
+        dX = ssl_head_input_bwd(model, out, dX)  # (through the bottleneck when the heads read the latents)
         ctx = out["ctx"]
         d_xnf = self.trunk.d_xnf_buffer(ctx)
         if zero_dxnf:
@@ -679,6 +681,7 @@ class VTPTrainer:
         self._opt_queue, self._opt_done, self._hooks_done = [], [], set()
         self._clip_cursor, self._clip_keys = 0, []
         del OVERLAP._deferred[:]  # (an aborted step must not leave an issue queued)
+        del self.trunk.bott_wgrads[:]  # (nor a queued bottleneck weight gradient)
         self._opt_ema = ssl is not None
         lag = 2 if self.collectives else 1
         # the lane is joined in front of every event when an event ends a graph segment / launches a collective; with one graph per
@@ -892,6 +895,7 @@ class VTPTrainer:
         if self.perceptual_weight > 0:  # perceptual term: adds its gradient w.r.t. the decoder output into dt
             self.lpips_val = self.lpips.loss_and_grad(t, rec_img, dt, self.perceptual_weight, B, H, W)
         held = None  # bucket keys whose gradients are being produced on the text stream
+        pvec = None
         if text is not None:
             d_xnf = self.trunk.d_xnf_buffer()[:Bc * Nc]  # rows of the clip item
             cw = self.clip.ws
@@ -970,7 +974,9 @@ class VTPTrainer:
                 yield from self._tower_backward("text", self.text.backward(d_f_txt), self.text.depth)
                 yield ["text_head"]
             d_f_img = self.clip.normalize_bwd(d_img_l, img_n, inv_i, "img")
-            self.clip.image_backward(d_f_img, xnf, d_xnf, Bc, Nc)  # writes the cls rows of the clip item in d_xnf
+            # cls feature: writes the cls rows of the clip item in d_xnf; pooled: the per-image vector the final-norm backward adds to
+            # the item's patch rows
+            pvec = self.clip.image_backward(d_f_img, xnf, d_xnf, Bc, Nc)
             OVERLAP.join()
             if held is not None:
                 held.append("clip_head")
@@ -1017,7 +1023,8 @@ class VTPTrainer:
             # no head writes the cls rows of d_xnf on this step: clear what an earlier step with another objective set left there
             # (the workspace is keyed by shape, not by objectives)
             self.trunk.d_xnf_buffer().zero_()
-        yield from self._tower_backward("trunk", self.trunk.backward(d_lat, lat_seg=rec_seg), self.trunk.depth)
+        pool = (0, pvec) if pvec is not None else None  # (the clip item is item 0)
+        yield from self._tower_backward("trunk", self.trunk.backward(d_lat, lat_seg=rec_seg, pool=pool), self.trunk.depth)
         yield ["trunk_head", "FINAL"]
         for fn in self._deferred:
             fn()

@@ -44,11 +44,12 @@ class VTP(VTPModel):
         super().__init__(config)
         if dino_nlayers != 3:
             raise ValueError("only the 3-layer DINO head MLP is implemented")
-        if not config.vision_bottleneck_ae_only:
-            raise NotImplementedError("the DINO head reads the un-bottlenecked trunk features (bottleneck_ae_only=True)")
-        D = config.vision_embed_dim
-        self.dino_cfg = dict(in_dim=D, hidden=dino_hidden_dim, bott=dino_bottleneck_dim, K=dino_out_dim)
-        self.dino_head = _dino_head_tree(D, dino_hidden_dim, dino_bottleneck_dim, dino_out_dim)
+        # vision_bottleneck_ae_only=False: the DINO / iBOT heads (and the CLIP feature) read the bottleneck latents of the cls and patch
+        # tokens instead of the trunk output (vtp.py:215-261, vision_transformer_bottleneck.py:43-79)
+        in_dim = config.vision_embed_dim if config.vision_bottleneck_ae_only or not hasattr(self.trunk, "feature_bottleneck") \
+            else config.vision_feature_bottleneck
+        self.dino_cfg = dict(in_dim=in_dim, hidden=dino_hidden_dim, bott=dino_bottleneck_dim, K=dino_out_dim)
+        self.dino_head = _dino_head_tree(in_dim, dino_hidden_dim, dino_bottleneck_dim, dino_out_dim)
         with torch.no_grad():
             for i in (0, 2, 4):
                 nn.init.trunc_normal_(self.dino_head.mlp[i].weight, std=0.02)
@@ -274,10 +275,16 @@ def ssl_forward(model: "VTP", global_crops, local_crops, masks_u8, plan, dev_pla
     ws = model._head.workspace(Ts, "ssl_io")
     Xt = ws.get("Xt", (Tt, D), BF)
 
+    # vision_bottleneck_ae_only=False: the head rows go through the (teacher's / student's) feature_bottleneck first -- gathered, then
+    # bottlenecked: the same bf16 rows as bottlenecking every token and gathering (row-wise map)
+    Dh = model.dino_cfg["in_dim"]
+    bott = Dh != D
+
     def teacher():
         xnf_t = model._t_trunk.forward(global_crops, train=False, tag="teacher", rope_aug=train)  # (teacher_trunk is in training mode too)
         ops.gather_token_rows(xnf_t, idx["teacher_src"], Xt, Tt, D)
-        return model._t_head.forward(Xt, Tt, tag="teacher")[0]
+        Ht = model._t_trunk.bott_rows(Xt, Tt, ws.get("Zt", (Tt, Dh), BF)) if bott else Xt
+        return model._t_head.forward(Ht, Tt, tag="teacher")[0]
 
     if OVERLAP.enabled:
         OVERLAP.join()
@@ -297,7 +304,19 @@ def ssl_forward(model: "VTP", global_crops, local_crops, masks_u8, plan, dev_pla
     Xs = ws.get("Xs", (Ts, D), BF)
     ops.gather_token_rows(xnf[seg_l.row0:], idx["student_local_src"], Xs, nl, D)
     ops.gather_token_rows(xnf[seg_g.row0:], idx["student_global_src"], Xs[nl:], Ts - nl, D)
-    s_logits, head_ctx = model._head.forward(Xs, Ts, tag="student")
+    Hs = model._trunk.bott_rows(Xs, Ts, ws.get("Zs", (Ts, Dh), BF)) if bott else Xs  # the head's input rows
+    s_logits, head_ctx = model._head.forward(Hs, Ts, tag="student")
     OVERLAP.join()  # teacher logits complete
     return dict(teacher_logits=t_logits, student_logits=s_logits, head_ctx=head_ctx, ctx=ctx, xnf=xnf, idx=idx,
-                Xs=Xs, student_global_cls=Xs[nl:nl + B2], Tt=Tt, Ts=Ts, Tm=Tm, nl=nl, B2=B2, N=N, ws=ws)
+                Xs=Xs, Hs=Hs, bott=bott, student_global_cls=Hs[nl:nl + B2], Tt=Tt, Ts=Ts, Tm=Tm, nl=nl, B2=B2, N=N, ws=ws)
+
+
+def ssl_head_input_bwd(model: "VTP", out, dH):
+    """gradient w.r.t. the head's input rows (bf16 [Ts, in_dim]) -> gradient w.r.t. the gathered trunk rows Xs (bf16 [Ts, D]): the
+    bottleneck's dgrad when the heads read the latents (its weight gradient is queued on the trunk engine), dH itself otherwise"""
+    if not out["bott"]:
+        return dH
+    Ts, D = out["Ts"], model._trunk.D
+    dXs = out["ws"].get("b.dXs", (Ts, D), BF)
+    model._trunk.bott_rows_bwd(dH, out["Xs"], Ts, dXs)
+    return dXs
