@@ -69,17 +69,18 @@ int vtp_gemm_tn(const void* A, int lda, const void* B, int ldb, void* C, int ldc
  * probs: device array of nprob records of 16 int64 {A, B, C, colsum | lda, ldb, ldc | M, N | c_grp, c_pre | tile0 | accumulate | 0 0 0};
  * part: ntiles * splits_eff * 65536 floats, ticket: ntiles ints, zero before the first launch (the kernel leaves them zero). */
 int vtp_gemm_tn_grouped(const void* probs, int nprob, int ntiles, int K, int splits, void* part, void* ticket, void* stream);
-/* the same launch with the kernel named: 0 = the 8-phase kernel (= vtp_gemm_tn_grouped), 1 = the one-wave-per-SIMD kernel with the
- * hand-scheduled k loop (needs K % 8 == 0; bit-identical results per K slice) */
-int vtp_gemm_tn_grouped_k(const void* probs, int nprob, int ntiles, int K, int splits, void* part, void* ticket, int kernel, void* stream);
-/* the same launch (one-wave-per-SIMD kernel, K % 8 == 0) from an explicit work-item list, so that the tiles need not be cut alike: items =
- * device array of nitems records of 8 int32 {tile, kbeg, kcount, nparts, part, 0, 0, 0}, one workgroup each; the items of a tile partition
- * [0, K) (kbeg multiples of 64); slots = the largest nparts; part: ntiles * slots * 65536 floats.  The tiles that also form a bias gradient
- * (column sums of dY beside the MFMAs: 27 % more time per k-tile) get one slice more than the rest -- same reference call sites as above. */
+/* the same launch on the one-wave-per-SIMD kernel with the hand-scheduled k loop (K % 8 == 0; bit-identical results per K slice), from an
+ * explicit work-item list, so that the tiles need not be cut alike: items = device array of nitems records of 8 int32 {tile, kbeg, kcount,
+ * nparts, part, 0, 0, 0}, one workgroup each; the items of a tile partition [0, K) (kbeg multiples of 64); slots = the largest nparts;
+ * part: ntiles * slots * 65536 floats.  The tiles that also form a bias gradient (column sums of dY beside the MFMAs: 27 % more time per
+ * k-tile) get one slice more than the rest -- same reference call sites as above. */
 int vtp_gemm_tn_grouped_items(const void* probs, int nprob, int ntiles, int K, const void* items, int nitems, int slots, void* part,
                               void* ticket, void* stream);
-/* tuning knob (benchmarks / experiments): force a tile configuration id (-1 = heuristic) and toggle the XCD-aware
- * workgroup remap.  Process-global; not part of the reference-facing surface. */
+/* tuning knob (benchmarks / experiments / tests): force a kernel configuration id and toggle the XCD-aware workgroup remap.
+ * force_cfg: -1 = heuristic | ring kernel tiles 0 = 128x128 4 waves, 3 = 256x128 3 stages, 4 = 256x256, 5 = 128x128 8 waves,
+ * 7 = 128x64, 21 = 5 software-pipelined | 8 = 256x256 8-phase kernel | 9 = 128x256 half-size kernel | 10 = one-wave-per-SIMD kernel
+ * (8 / 9 / 10 fall back to 5 where their limits do not hold; vtp_gemm_tn knows 8 and runs 5 for every other id).  Any other id is
+ * refused and leaves the state as it was.  Process-global; not part of the reference-facing surface. */
 int vtp_set_gemm_tuning(int force_cfg, int xcd_swizzle);
 /* persistent 256 x 256 NT launches draw their tiles from per-XCD queues in device memory (1) instead of owning a static tile list (0,
  * default): a launch that cannot get every CU at once -- RCCL channels hold some for the whole backward -- then ends when the tiles

@@ -68,6 +68,9 @@ def test_argument_validation_needs_no_gpu(lib):
     rc = lib.vtp_adamw(ctypes.c_void_p(16), ctypes.c_void_p(16), ctypes.c_void_p(16), ctypes.c_void_p(16), None, 6, 1e-3, 0.9,
                        0.99, 1e-8, 0.0, 1, 1.0, None)
     assert rc == -1
+    # a configuration id that names no kernel is refused (it used to run configuration 0 silently); the heuristic id is accepted
+    assert lib.vtp_set_gemm_tuning(2, 3) != 0 and b"force_cfg" in lib.vtp_last_error()
+    assert lib.vtp_set_gemm_tuning(-1, 3) == 0
 
 
 def test_missing_library_is_a_loud_error(monkeypatch, tmp_path):

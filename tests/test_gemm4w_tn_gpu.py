@@ -1,5 +1,6 @@
-"""The grouped weight-gradient launch on the one-wave-per-SIMD kernel (vtp_amd/csrc/gemm4w_tn.hip + gemm4w_tn_ktile.inc, `kernel = 1` of
-vtp_gemm_tn_grouped_k) -- against fp32 torch on the bf16 operands, and against the 8-phase kernel (`kernel = 0`): BIT FOR BIT where the
+"""The grouped weight-gradient launch on the one-wave-per-SIMD kernel (vtp_amd/csrc/gemm4w_tn.hip + gemm4w_tn_ktile.inc,
+vtp_gemm_tn_grouped_items: `WgradGroup.launch(kernel=1)`, on the work-item list of finalize() at the large token counts and on a uniform
+tiles x slices list at the small ones) -- against fp32 torch on the bf16 operands, and against the 8-phase kernel (`kernel = 0`): BIT FOR BIT where the
 launch has one K slice (same k order per output element, same MFMA, same epilogue), within the run-to-run bound of the in-launch combine
 where it has several (the last-arriving slice differs from run to run, in both kernels).  K tails inside a k-tile, odd k-tile counts
 (padded with a zero k-tile), M / N tails (clamped staging columns), SwiGLU row de-interleave, fused bias-gradient column sums, C += and

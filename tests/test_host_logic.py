@@ -582,7 +582,7 @@ def test_shipped_kernels_spill_ratchet():
             assert rows[n][0] == 0, f"{n}: {rows[n][0]} spilled VGPRs (was 0)"
     # epilogue-only spills of the 8-phase family and the one-wave kernels (tools/spill_report.py shows where): may shrink, not grow
     caps = {"vtp::gemm8p_kernel<0, false, 0, 0>": 4, "vtp::gemm8p_kernel<1, false, 0, 0>": 1, "vtp::gemm8p_kernel<2, false, 0, 0>": 4,
-            "vtp::gemm8p_kernel<0, false, 0, 1>": 33, "vtp::gemm8p_kernel<0, false, 0, 2>": 8, "vtp::gemm4w_grouped_tn_kernel": 48,
+            "vtp::gemm8p_kernel<0, false, 0, 1>": 33, "vtp::gemm8p_kernel<0, false, 0, 2>": 8,
             "vtp::gemm4w_grouped_tn_items_kernel": 48, "vtp::gemm8p_grouped_tn_kernel": 4, "vtp::gemm4w_kernel<1, 0, false>": 18,
             # the queue-drawing variants (on beside collectives only): epilogue-side spills, none inside a k loop
             "vtp::gemm8p_dyn_kernel<0, 0, 0>": 4, "vtp::gemm8p_dyn_kernel<1, 0, 0>": 12, "vtp::gemm8p_dyn_kernel<2, 0, 0>": 4,
@@ -593,6 +593,17 @@ def test_shipped_kernels_spill_ratchet():
         assert hit, f"kernel {k} not in the built objects"
         for n in hit:
             assert rows[n][0] <= cap, f"{n}: {rows[n][0]} spilled VGPRs (cap {cap})"
+    # the ring kernel ships the tile shapes <BM, BN, WAVES_M, WAVES_N, STAGES, TRANS, PIPE> that a dispatch function returns or a test
+    # forces (launch_gemm / launch_conv in gemm.hip), and no others: a configuration nothing can reach is not compiled
+    import re
+    ring = [re.search(r"gemm_nt_kernel<(\d+), (\d+), (\d+), (\d+), (\d+), \d+, (true|false), (true|false)>", n) for n in rows
+            if "vtp::gemm_nt_kernel<" in n]
+    assert all(ring), "unparsed gemm_nt_kernel name"
+    shapes = {tuple(int(v) if v.isdigit() else v == "true" for v in m.groups()) for m in ring}
+    assert shapes == {(128, 128, 2, 2, 2, False, False), (256, 128, 4, 2, 3, False, False), (128, 128, 4, 2, 2, False, False),
+                      (128, 64, 4, 1, 3, False, False), (128, 128, 4, 2, 2, False, True), (256, 128, 4, 2, 2, False, False),
+                      (256, 256, 4, 2, 2, False, False), (256, 64, 4, 2, 2, False, False), (128, 128, 4, 2, 2, True, False)}, sorted(shapes)
+    assert len(ring) == 45, f"{len(ring)} gemm_nt_kernel instantiations (45 = the epilogues each shape is launched with)"
 
 
 def test_wgrad_group_item_list_partitions_every_tile():

@@ -21,7 +21,7 @@ SHAPES = [  # (tag, M, N, K, epilogue)
     ("wgrad_proj", 768, 768, 8224, ops.EPI_F32_SLAB),
     ("big_4096", 4096, 4096, 4096, ops.EPI_BF16),
 ]
-CFGS = {0: "128x128 4w s2", 5: "128x128 8w s2", 21: "128x128 8w s2 PIPE", 2: "256x128 8w s2", 4: "256x256 8w s2"}
+CFGS = {0: "128x128 4w s2", 5: "128x128 8w s2", 21: "128x128 8w s2 PIPE", 4: "256x256 8w s2"}
 
 
 def main():

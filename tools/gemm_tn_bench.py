@@ -1,4 +1,4 @@
-"""Micro-benchmark of vtp_gemm_tn (weight-gradient GEMM from untransposed activations) tile configurations."""
+"""Micro-benchmark of vtp_gemm_tn (weight-gradient GEMM from untransposed activations): ring kernel against 8-phase kernel."""
 import os
 import sys
 
@@ -9,7 +9,7 @@ from vtp_amd import _lib, ops
 
 SHAPES = [("wgrad_qkv", 2304, 768, 8224), ("wgrad_w12", 4096, 768, 8224), ("wgrad_proj", 768, 768, 8224),
           ("wgrad_w3", 768, 2048, 8224)]
-CFGS = {0: "128x128 4w s2", 5: "128x128 8w s2", 2: "256x128 8w s2", 3: "256x128 8w s3"}
+CFGS = {5: "ring 128x128 8w s2", 8: "8-phase 256x256"}  # the two kernels vtp_gemm_tn dispatches between
 
 
 def main():

@@ -12,7 +12,7 @@ kind, M, N, K, cfg = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), int(sys.ar
 splits = int(sys.argv[6]) if len(sys.argv) > 6 else 1
 lib = _lib.load()
 g = torch.Generator(device="cuda").manual_seed(0)
-lib.vtp_set_gemm_tuning(cfg, 3)
+_lib.check(lib.vtp_set_gemm_tuning(cfg, 3), "vtp_set_gemm_tuning")  # (an id that names no kernel is refused)
 if kind == "nt":
     a = torch.randn(M, K, device="cuda", generator=g).to(torch.bfloat16)
     b = (torch.randn(N, K, device="cuda", generator=g) * 0.05).to(torch.bfloat16)

@@ -35,7 +35,7 @@ def main():
                 for (a, x, N, K, sh, _), gw, gb in zip(probs, gws, gbs):
                     g2.add(a, x, gw, gb, N, K, sh)
                 g2.finalize(dev, {})
-                g2.splits = sp
+                g2.splits, g2.items = sp, None  # (no list of finalize(): launch(kernel=1) cuts every tile into `sp` slices)
                 g2.part = torch.empty(g2.ntiles * sp * 65536, device=dev)
                 g2.ticket = torch.zeros(max(g2.ntiles, 256), dtype=torch.int32, device=dev)
                 tt = timeit({"x": lambda: g2.launch(kernel=1)})["x"]

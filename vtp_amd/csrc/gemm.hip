@@ -39,7 +39,7 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N) void gemm_nt_kernel(const Ge
   constexpr int PA = BM / 8 / NW, PB = BN / 8 / NW;  // 1-KiB LDS-DMA pieces per wave per k-tile
   constexpr int P = PA + PB;
   static_assert(PA >= 1 && PB >= 1 && TM >= 1 && TN >= 1, "bad tile config");
-  static_assert(STAGES >= 2 && STAGES <= 4, "2..4 stages");
+  static_assert(STAGES == 2 || STAGES == 3, "2 or 3 stages");
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int tid = threadIdx.x;
@@ -345,8 +345,10 @@ static int launch_cfg(const GemmArgs& a, int splits, hipStream_t s) {
   return check_launch(TRANS ? "gemm_tn" : "gemm_nt");
 }
 
-// tile configurations (cfg id): 0 = 128x128 4 waves 2 stages | 1 = 128x128 4w 3 stages | 2 = 256x128 8w 2 stages |
-// 3 = 256x128 8w 3 stages | 4 = 256x256 8w 2 stages | 5 = 128x128 8w 2 stages | 6 = 128x128 4w 4 stages
+// ring tile configurations (cfg id, NT): 0 = 128x128 4 waves 2 stages | 3 = 256x128 8w 3 stages | 4 = 256x256 8w 2 stages (bf16 epilogue:
+// 256x128) | 5 = 128x128 8w 2 stages | 7 = 128x64 4w 3 stages | 21 = 5 with the software-pipelined k-tile body.  TN runs 5 only.
+// 8 / 9 / 10 = the 8-phase, half-size and one-wave-per-SIMD kernels below.  Every id here is returned by a dispatch function or forced
+// by a test; vtp_set_gemm_tuning refuses any other.
 static int g_force_cfg = -1;
 static int g_xcd_swizzle = 3;  // bit 0: XCD-aware tile order | bit 1: LDS-staged full-line stores for bf16 outputs
 static int swz_flags() { return g_xcd_swizzle; }
@@ -387,19 +389,10 @@ static int launch_gemm(const GemmArgs& a, int splits, int cfg, hipStream_t s) {
       cfg = 5;
     }
   }
-  if constexpr (TRANS) {  // weight-gradient shapes only: keep the instantiation count small
-    switch (cfg) {
-      case 2: return launch_cfg<256, 128, 4, 2, 2, EPI, true>(a, splits, s);
-      case 3: return launch_cfg<256, 128, 4, 2, 3, EPI, true>(a, splits, s);
-      case 5: return launch_cfg<128, 128, 4, 2, 2, EPI, true>(a, splits, s);
-      case 21: return launch_cfg<128, 128, 4, 2, 2, EPI, true, true>(a, splits, s);
-      case 16: return launch_cfg<128, 128, 2, 2, 2, EPI, true, true>(a, splits, s);
-      default: return launch_cfg<128, 128, 2, 2, 2, EPI, true>(a, splits, s);
-    }
+  if constexpr (TRANS) {  // weight-gradient shapes: the 8-wave 128x128 tile is the only ring configuration (vtp_gemm_tn)
+    return launch_cfg<128, 128, 4, 2, 2, EPI, true>(a, splits, s);
   } else {
     switch (cfg) {
-      case 1: return launch_cfg<128, 128, 2, 2, 3, EPI, false>(a, splits, s);
-      case 2: return launch_cfg<256, 128, 4, 2, 2, EPI, false>(a, splits, s);
       case 3: return launch_cfg<256, 128, 4, 2, 3, EPI, false>(a, splits, s);
       case 4:
         // the bf16 instantiation of the 256 x 256 ring tile spilled 462 VGPRs (the run-time RoPE / SwiGLU-backward extras on top of 256
@@ -407,10 +400,7 @@ static int launch_gemm(const GemmArgs& a, int splits, int cfg, hipStream_t s) {
         if constexpr (EPI == EPI_BF16) return launch_cfg<256, 128, 4, 2, 2, EPI, false>(a, splits, s);
         else return launch_cfg<256, 256, 4, 2, 2, EPI, false>(a, splits, s);
       case 5: return launch_cfg<128, 128, 4, 2, 2, EPI, false>(a, splits, s);
-      case 6: return launch_cfg<128, 128, 2, 2, 4, EPI, false>(a, splits, s);
       case 7: return launch_cfg<128, 64, 4, 1, 3, EPI, false>(a, splits, s);   // few-tile shapes: twice the workgroups
-      case 16: return launch_cfg<128, 128, 2, 2, 2, EPI, false, true>(a, splits, s);
-      case 18: return launch_cfg<256, 128, 4, 2, 2, EPI, false, true>(a, splits, s);
       case 21: return launch_cfg<128, 128, 4, 2, 2, EPI, false, true>(a, splits, s);
       default: return launch_cfg<128, 128, 2, 2, 2, EPI, false>(a, splits, s);
     }
@@ -572,6 +562,9 @@ extern "C" int vtp_gemm_tn_splits(int M, int N, int K) {
 }
 
 extern "C" int vtp_set_gemm_tuning(int force_cfg, int xcd_swizzle) {
+  bool known = false;
+  for (int id : {-1, 0, 3, 4, 5, 7, 8, 9, 10, 21}) known |= force_cfg == id;
+  VTP_REQUIRE(known, "vtp_set_gemm_tuning: force_cfg %d names no kernel configuration (-1, 0, 3, 4, 5, 7, 8, 9, 10, 21)", force_cfg);
   g_force_cfg = force_cfg;
   g_xcd_swizzle = xcd_swizzle;
   return VTP_OK;
@@ -738,7 +731,7 @@ extern "C" int vtp_gemm_tn(const void* A, int lda, const void* B, int ldb, void*
   splits = (K + ks - 1) / ks;
   // tools/gemm_tn_bench.py on MI355X: the 8-wave 128x128 tile wins on every wgrad shape (transpose reads want more waves)
   int cfg = g_force_cfg >= 0 ? g_force_cfg : (use_8p_tn(M, N, K, splits, a) ? 8 : 5);
-  if (cfg != 2 && cfg != 3 && cfg != 5 && cfg != 8 && cfg != 16 && cfg != 21) cfg = 0;
+  if (cfg != 8) cfg = 5;  // a forced NT-only id: the one ring configuration
   hipStream_t s = (hipStream_t)stream;
   if (a_colsum) {  // bias gradient db[m] += sum_t A[t, m]: fused into the 8-phase kernel, a separate pass otherwise
     VTP_REQUIRE(c_grp <= 0, "vtp_gemm_tn: a_colsum supports the identity and the SwiGLU (c_grp = -1) row maps only");

@@ -1,7 +1,8 @@
 // Grouped weight gradients C_g[M_g, N_g] (+)= A_g[K, M_g]^T B_g[K, N_g] on the one-wave-per-SIMD 256 x 256 kernel: the TN counterpart of
 // gemm4w.hip (same X / Y schedule, hand-scheduled k loop as generated inline asm: gemm4w_tn_ktile.inc / tools/gen_gemm4w_ktile.py),
-// launched like gemm8p_grouped_tn_kernel -- one workgroup per (256 x 256 tile, K slice), slices combined in the launch by the last
-// arriver, bias-gradient column sums riding along -- and bit-identical to it per K slice (same k order per output element, same MFMA).
+// launched from a host-built work-item list -- one workgroup per (256 x 256 tile, K range), the ranges of a tile combined in the launch
+// by the last arriver as in gemm8p_grouped_tn_kernel, bias-gradient column sums riding along -- and bit-identical to that kernel per
+// K slice (same k order per output element, same MFMA).  A uniform tiles x slices cut is one particular list (ops.WgradGroup).
 //
 //   * 4 waves = 2 (M) x 2 (N), wave tile 128 x 128, 256 accumulator AGPRs, fragments in PHYSICAL VGPRs v64..v255 (the asm owns them);
 //   * a staged k-tile (64 k rows) = eight 8-KiB sub-images [64 k][64 columns] with 128-B rows -- A columns wr * 128 + {0..63 | 64..127},
@@ -12,7 +13,8 @@
 //     rows lie beyond the slice read a zero block (so a slice needs no K-tail path, and an odd k-tile count is padded with a zero one);
 //   * ring of two k-tiles (128 KiB) + 32 KiB (4 KiB per wave of fp32 epilogue staging; the arrival flag of the combine in its last
 //     word): 160 KiB, one workgroup per CU.
-// Limits (launcher; otherwise the 8-phase kernel takes the launch): M, N, K multiples of 8, 32-bit operand offsets.
+// Limits (checked where the records are built, ops.WgradGroup; otherwise the 8-phase kernel takes the launch): M, N, K multiples of
+// 8, 32-bit operand offsets.
 #include "gemm_common.h"
 #include "gemm_group.h"
 #include "gemm4w_tn_ktile.inc"
@@ -238,14 +240,6 @@ __device__ __forceinline__ void w4t_segment(const GroupArgs& ga, int tile, int k
 }
 
 
-// one workgroup per (tile, K slice): the launch geometry of gemm8p_grouped_tn_kernel (tiles x splits workgroups, split-major over the XCDs)
-__global__ __launch_bounds__(256, 1) void gemm4w_grouped_tn_kernel(const GroupArgs ga) {
-  const int c = xcd_chunk_start(blockIdx.x, gridDim.x) + ((int)blockIdx.x >> 3);
-  const int zslice = c / ga.ntiles, tile = c - zslice * ga.ntiles;
-  const int kbeg = zslice * ga.k_split;
-  w4t_segment(ga, tile, kbeg, min(ga.K, kbeg + ga.k_split) - kbeg, ga.splits, zslice);
-}
-
 // item-list launch (vtp_gemm_tn_grouped_items): every workgroup reads its (tile, K range, slot) from a host-built table, so the tiles of
 // a launch need not be cut alike -- the tiles that also sum the columns of A (bias gradients: 64 v_dot2 per k-tile beside the 64 MFMAs,
 // measured 27 % slower per k-tile, tools/wgrad_timeline.py) get one slice more than the others and the launch ends level
@@ -263,20 +257,6 @@ int launch_gemm4w_grouped_tn_items(const GroupArgs& ga, int nitems, hipStream_t 
   }
   hipLaunchKernelGGL(gemm4w_grouped_tn_items_kernel, dim3(nitems), dim3(256), W4T_LDS, s, ga);
   return check_launch("gemm4w_grouped_tn_items");
-}
-
-// launcher used by vtp_gemm_tn_grouped_k (gemm8p.hip, kernel = 1).  The problem records live in DEVICE memory, so the C entry can only
-// check what it is passed by value (token count % 8); the per-problem limits of this kernel -- M_g, N_g and both leading dimensions
-// multiples of 8 (16-B staging pieces, `min(.., M - 8)` column clamps), operand spans below 4 GiB (32-bit lane offsets) -- are enforced
-// where the records are BUILT: ops.WgradGroup.add / finalize raise ValueError (vtp_amd/ops.py), and a C caller must do the same.
-int launch_gemm4w_grouped_tn(const GroupArgs& ga, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm4w_grouped_tn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, W4T_LDS);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(gemm4w_grouped_tn_kernel, dim3(ga.ntiles * ga.splits), dim3(256), W4T_LDS, s, ga);
-  return check_launch("gemm4w_grouped_tn");
 }
 
 }  // namespace vtp

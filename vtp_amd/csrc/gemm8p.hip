@@ -723,25 +723,20 @@ int launch_gemm8p_tn(const GemmArgs& a, int epi, int splits, hipStream_t s) {
 // GroupProblem records (16 x int64 each); ntiles = sum of their 256 x 256 tile counts; part / ticket: device scratch of
 // ntiles * splits * 256 KiB and ntiles ints (ticket zero-initialised by the caller once; the kernel leaves it zero).
 namespace vtp {
-int launch_gemm4w_grouped_tn(const GroupArgs& ga, hipStream_t s);  // gemm4w_tn.hip
-int launch_gemm4w_grouped_tn_items(const GroupArgs& ga, int nitems, hipStream_t s);
+int launch_gemm4w_grouped_tn_items(const GroupArgs& ga, int nitems, hipStream_t s);  // gemm4w_tn.hip
 }
-// kernel: 0 = the 8-phase kernel | 1 = the one-wave-per-SIMD kernel (gemm4w_tn.hip; the caller guarantees K % 8 == 0 and, as for
-// every grouped launch, M_g, N_g, lda, ldb multiples of 8 and operands within 32-bit byte offsets)
-extern "C" int vtp_gemm_tn_grouped_k(const void* probs, int nprob, int ntiles, int K, int splits, void* part, void* ticket, int kernel,
-                                     void* stream) {
+extern "C" int vtp_gemm_tn_grouped(const void* probs, int nprob, int ntiles, int K, int splits, void* part, void* ticket,
+                                   void* stream) {
   using namespace vtp;
   VTP_REQUIRE(probs && nprob >= 1 && nprob <= 8, "vtp_gemm_tn_grouped: 1..8 problems");
   VTP_REQUIRE(ntiles >= 1 && K >= 1 && splits >= 1, "vtp_gemm_tn_grouped: bad shape (ntiles %d, K %d, splits %d)", ntiles, K, splits);
   VTP_REQUIRE(splits == 1 || (part && ticket), "vtp_gemm_tn_grouped: split-K needs the partial-sum and ticket buffers");
-  VTP_REQUIRE(kernel == 0 || (kernel == 1 && K % 8 == 0), "vtp_gemm_tn_grouped: kernel %d not available for K = %d", kernel, K);
   GroupArgs ga{};
   ga.probs = (const GroupProblem*)probs; ga.part = (float*)part; ga.ticket = (int*)ticket;
   ga.nprob = nprob; ga.ntiles = ntiles; ga.K = K;
   ga.k_split = ((K + splits - 1) / splits + 63) / 64 * 64;
   ga.splits = (K + ga.k_split - 1) / ga.k_split;
   ga.timing = g_p8_timing;
-  if (kernel == 1) return launch_gemm4w_grouped_tn(ga, (hipStream_t)stream);  // (stamps [workgroup][8] under vtp_gemm_debug)
   static bool attr_set = false;
   if (!attr_set) {
     hipFuncSetAttribute((const void*)gemm8p_grouped_tn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, P8_LDS);
@@ -750,9 +745,13 @@ extern "C" int vtp_gemm_tn_grouped_k(const void* probs, int nprob, int ntiles, i
   hipLaunchKernelGGL(gemm8p_grouped_tn_kernel, dim3(ntiles * ga.splits), dim3(512), P8_LDS, (hipStream_t)stream, ga);
   return check_launch("gemm8p_grouped_tn");
 }
-// The same launch from an explicit work-item list (one-wave-per-SIMD kernel only): items = device array of nitems records of 8 int32
-// {tile, kbeg, kcount, nparts, part, 0, 0, 0} -- one workgroup each; the items of a tile partition [0, K) into nparts ranges (kbeg
-// multiples of 64), part = 0 .. nparts - 1.  slots = the largest nparts: part holds ntiles * slots * 65536 floats.
+// The same launch on the one-wave-per-SIMD kernel (gemm4w_tn.hip), from an explicit work-item list: items = device array of nitems
+// records of 8 int32 {tile, kbeg, kcount, nparts, part, 0, 0, 0} -- one workgroup each; the items of a tile partition [0, K) into
+// nparts ranges (kbeg multiples of 64), part = 0 .. nparts - 1.  slots = the largest nparts: part holds ntiles * slots * 65536 floats.
+// The problem records live in DEVICE memory, so this entry can only check what it is passed by value (token count % 8); the
+// per-problem limits of the kernel -- M_g, N_g and both leading dimensions multiples of 8 (16-B staging pieces, `min(.., M - 8)` column
+// clamps), operand spans below 4 GiB (32-bit lane offsets) -- are enforced where the records are BUILT: ops.WgradGroup.add / finalize
+// raise ValueError (vtp_amd/ops.py).
 extern "C" int vtp_gemm_tn_grouped_items(const void* probs, int nprob, int ntiles, int K, const void* items, int nitems, int slots,
                                          void* part, void* ticket, void* stream) {
   using namespace vtp;
@@ -766,10 +765,6 @@ extern "C" int vtp_gemm_tn_grouped_items(const void* probs, int nprob, int ntile
   ga.timing = g_p8_timing;
   ga.items = (const GroupItem*)items;
   return launch_gemm4w_grouped_tn_items(ga, nitems, (hipStream_t)stream);
-}
-extern "C" int vtp_gemm_tn_grouped(const void* probs, int nprob, int ntiles, int K, int splits, void* part, void* ticket,
-                                   void* stream) {
-  return vtp_gemm_tn_grouped_k(probs, nprob, ntiles, K, splits, part, ticket, 0, stream);
 }
 
 extern "C" int vtp_set_gemm_dynamic(int on) {

@@ -1,5 +1,5 @@
-// Argument records of the grouped weight-gradient launch (vtp_gemm_tn_grouped): shared by the 8-phase kernel (gemm8p.hip) and the
-// one-wave-per-SIMD kernel (gemm4w_tn.hip).
+// Argument records of the grouped weight-gradient launches: the 8-phase kernel (gemm8p.hip, vtp_gemm_tn_grouped) runs a uniform
+// tiles x splits grid, the one-wave-per-SIMD kernel (gemm4w_tn.hip, vtp_gemm_tn_grouped_items) a host-built work-item list.
 #pragma once
 #include "gemm_common.h"
 
@@ -27,9 +27,9 @@ struct GroupArgs {
   const GroupProblem* probs;
   float* part;
   int* ticket;
-  int nprob, ntiles, splits, K, k_split;  // splits: slices per tile (uniform launches) | partial-sum slots per tile (item lists)
+  int nprob, ntiles, splits, K, k_split;  // splits: slices per tile (8-phase kernel) | partial-sum slots per tile (item lists)
   unsigned long long* timing;
-  const GroupItem* items;  // null: uniform tiles x splits geometry
+  const GroupItem* items;  // one-wave-per-SIMD kernel: one record per workgroup, never null | 8-phase kernel: unused (null)
 };
 
 }  // namespace vtp

@@ -318,9 +318,12 @@ def linear_bwd(ws: Workspace, tag: str, L, dy_b, x_b, M: int, d_in, *, need_dx: 
                x_remap=(0, 0), dx_remap=(0, 0), gw=None, gb=None, N=None, K=None, wT=None, swiglu_h: int = 0,
                bias_grad_done: bool = False, ls=None, dgrad_swiglu=None, defer=None):
     """Backward of y[M,N] = x[M,K] W^T + b given dy (bf16 [M,N]):  dW += dy^T x,  db += colsum(dy),  dx = dy W.
-    Reaches the NT GEMM through transposed operands: dy^T and x^T are produced by the LDS transpose kernel (the
-    column sums for db ride along), W^T is the cached transposed weight.  The wgrad GEMM is split-K over the token
-    dimension; slices write private fp32 slabs (plain stores) that one reduce kernel folds into the flat gradient."""
+    dx is an NT GEMM against the cached transposed weight W^T.  dW is a TN GEMM (ops.gemm_tn) straight from the activation layouts --
+    no transposed copies; the transpose happens in the kernel's LDS reads -- split-K over the token dimension: slices write private
+    fp32 slabs (plain stores) that one reduce kernel folds into the flat gradient; db is a column-sum launch beside it.  With `defer`
+    (the transformer blocks) the problem is only recorded and the caller runs the block's weight gradients as ONE grouped launch
+    (ops.WgradGroup: the 8-phase kernel, or the one-wave-per-SIMD kernel on a work-item list; K slices combined inside the launch,
+    column sums fused)."""
     if L is not None:
         N = L.N if N is None else N
         K = L.K if K is None else K

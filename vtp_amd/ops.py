@@ -219,7 +219,7 @@ def wgrad_group_splits(ntiles: int, Ktok: int):
 
 def wgrad_group_kernel(ntiles: int, splits: int, Ktok: int) -> int:
     """which kernel runs a grouped weight-gradient launch: 0 = the 8-phase kernel; 1 = the one-wave-per-SIMD kernel (gemm4w_tn.hip) on the
-    same tiles x slices geometry, when the token count allows its 8-row staging pieces and a K slice is long enough to amortise its
+    same tiles (cut by wgrad_group_items), when the token count allows its 8-row staging pieces and a K slice is long enough to amortise its
     pipeline fill.  VTP_GEMM4W_TN=0 / 1 forces the choice (same-box A/B of the step); a token count that is not a multiple of 8
     always takes the 8-phase kernel."""
     import os
@@ -231,6 +231,12 @@ def wgrad_group_kernel(ntiles: int, splits: int, Ktok: int) -> int:
     return 1 if Ktok // max(splits, 1) >= W4_TN_MIN_SLICE else 0
 
 
+def wgrad_k_cuts(Ktok: int, n: int):
+    """[(kbeg, kcount)] of a K range cut into n slices of whole k-tiles (64 rows): fewer than n when the rounding leaves none for the last"""
+    ks = ((Ktok + n - 1) // n + 63) // 64 * 64
+    return [(b, min(Ktok, b + ks) - b) for b in range(0, Ktok, ks)]
+
+
 def wgrad_group_items(rows, Ktok: int, base_splits: int, cus: int = None):
     """work-item list of a grouped launch on the one-wave-per-SIMD kernel (vtp_gemm_tn_grouped_items).  rows: the GroupProblem records
     (WgradGroup.rows).  Every tile is cut into `base_splits` K ranges, except the tiles that also form a bias gradient -- the first tile
@@ -240,11 +246,6 @@ def wgrad_group_items(rows, Ktok: int, base_splits: int, cus: int = None):
     Order: per problem, the heavier-cut tiles first, slice-major inside a group -- the kernel deals contiguous chunks of the list to
     the XCDs, so the workgroups that stream the same K range of the same operand panels sit behind one L2."""
     cus = gemm_cus() if cus is None else cus
-
-    def cuts(n):
-        ks = ((Ktok + n - 1) // n + 63) // 64 * 64
-        return [(b, min(Ktok, b + ks) - b) for b in range(0, Ktok, ks)]
-
     tiles = []  # (tile index, problem, has colsum work)
     for pi, r in enumerate(rows):
         gb, N, K, tile0 = r[3], r[7], r[8], r[11]
@@ -259,11 +260,19 @@ def wgrad_group_items(rows, Ktok: int, base_splits: int, cus: int = None):
             grp = [t for t in tiles if t[1] == pi and t[2] == heavy]
             if not grp:
                 continue
-            cs = cuts(base_splits + 1 if (heavy and more) else base_splits)
+            cs = wgrad_k_cuts(Ktok, base_splits + 1 if (heavy and more) else base_splits)
             slots = max(slots, len(cs))
             for z, (kb, kc) in enumerate(cs):
                 items += [[t[0], kb, kc, len(cs), z, 0, 0, 0] for t in grp]
     return items, slots
+
+
+def wgrad_group_uniform_items(ntiles: int, Ktok: int, splits: int):
+    """the uniform tiles x slices cut (the geometry of the 8-phase kernel's grouped launch) as a work-item list: every tile in `splits`
+    K ranges, slice-major over all tiles (items[z * ntiles + tile]), so a workgroup gets the tile and slice that grid would give it.
+    Returns (items, slots) like wgrad_group_items."""
+    cs = wgrad_k_cuts(Ktok, max(int(splits), 1))
+    return [[t, kb, kc, len(cs), z, 0, 0, 0] for z, (kb, kc) in enumerate(cs) for t in range(ntiles)], len(cs)
 
 
 W4_TN_MIN_SLICE = 4096  # token rows per K slice from which the one-wave-per-SIMD kernel is taken (tools/wgrad_kernel_ab.py against the two-phase 8-phase kernel: x0.97 at 1232 .. 2048 rows, x1.01 at 4096, x1.06 at 8224, x1.08 .. 1.12 at 17072)
@@ -277,6 +286,7 @@ class WgradGroup:
     def __init__(self, Ktok: int):
         self.Ktok, self.rows, self.ntiles, self.keep = int(Ktok), [], 0, []
         self.table = self.part = self.ticket = None
+        self._uniform = {}  # splits -> (items, nitems, slots): uniform lists of a forced launch(kernel=1)
 
     def add(self, dy, x, gw, gb, N: int, K: int, swiglu_h: int = 0, accumulate: bool = True):
         """dy bf16 [Ktok, N] (row stride dy.stride(0)), x bf16 [Ktok, K], gw f32 [N * K], gb f32 [N] or None (bias gradient =
@@ -303,10 +313,8 @@ class WgradGroup:
         _, self.splits = wgrad_group_splits(self.ntiles, self.Ktok)
         self.table = torch.tensor(self.rows, dtype=torch.int64, device=device)
         self.kernel = wgrad_group_kernel(self.ntiles, self.splits, self.Ktok)
-        self.items, self.slots = None, self.splits
-        import os
-        if self.kernel == 1 and os.environ.get("VTP_WGRAD_ITEMS", "1") not in ("0", "false", "off"):
-            # uneven cut: the tiles with bias-gradient work get one slice more (wgrad_group_items); VTP_WGRAD_ITEMS=0: uniform geometry
+        self.items, self.nitems, self.slots = None, None, self.splits
+        if self.kernel == 1:  # uneven cut: the tiles with bias-gradient work get one slice more (wgrad_group_items)
             items, self.slots = wgrad_group_items(self.rows, self.Ktok, self.splits)
             self.nitems = len(items)
             self.items = torch.tensor(items, dtype=torch.int32, device=device)
@@ -321,16 +329,26 @@ class WgradGroup:
         return self
 
     def launch(self, kernel=None):
-        """kernel: 0 = the 8-phase kernel, 1 = the one-wave-per-SIMD kernel (gemm4w_tn.hip), None = the measured choice made by finalize()
-        (ops.wgrad_group_kernel)"""
+        """kernel: 0 = the 8-phase kernel on the uniform tiles x self.splits grid, 1 = the one-wave-per-SIMD kernel (gemm4w_tn.hip) on the
+        work-item list of finalize() -- or, forced on a group for which finalize() built none (tools, tests), on the uniform cut of the
+        current self.splits written as a list -- None = the measured choice made by finalize() (ops.wgrad_group_kernel)"""
         if kernel is None:
             kernel = self.kernel
-        if kernel == 1 and self.items is not None:
-            _lib.check(_lib_().vtp_gemm_tn_grouped_items(_p(self.table), len(self.rows), self.ntiles, self.Ktok, _p(self.items), self.nitems,
-                                                         self.slots, _p(self.part), _p(self.ticket), _s()), "vtp_gemm_tn_grouped_items")
+        if kernel == 0:
+            _lib.check(_lib_().vtp_gemm_tn_grouped(_p(self.table), len(self.rows), self.ntiles, self.Ktok, self.splits, _p(self.part),
+                                                   _p(self.ticket), _s()), "vtp_gemm_tn_grouped")
             return
-        _lib.check(_lib_().vtp_gemm_tn_grouped_k(_p(self.table), len(self.rows), self.ntiles, self.Ktok, self.splits, _p(self.part),
-                                                  _p(self.ticket), kernel, _s()), "vtp_gemm_tn_grouped")
+        if kernel != 1:
+            raise ValueError(f"WgradGroup.launch: kernel must be 0, 1 or None, not {kernel!r}")
+        items, nitems, slots = self.items, self.nitems, self.slots
+        if items is None:
+            if self.splits not in self._uniform:
+                import torch
+                rows, slots = wgrad_group_uniform_items(self.ntiles, self.Ktok, self.splits)
+                self._uniform[self.splits] = (torch.tensor(rows, dtype=torch.int32, device=self.table.device), len(rows), slots)
+            items, nitems, slots = self._uniform[self.splits]
+        _lib.check(_lib_().vtp_gemm_tn_grouped_items(_p(self.table), len(self.rows), self.ntiles, self.Ktok, _p(items), nitems, slots,
+                                                     _p(self.part), _p(self.ticket), _s()), "vtp_gemm_tn_grouped_items")
 
 
 def colsum_bf16(inp, ld, out, R, C, swiglu_h=0, in_remap=(0, 0)):
