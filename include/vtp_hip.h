@@ -271,6 +271,19 @@ int vtp_ema_dev(float* t, const float* s, long n, const float* momentum /* devic
  * bucket for the per-bucket optimizer lane of the training step.  Short-lived blocks (4096 elements each). */
 int vtp_adamw_ema_dev(float* p, const float* g, float* m, float* v, float* teacher, const void* nodecay4, long n, const float* hyper,
                       void* stream);
+/* Per-parameter-group learning-rate / weight-decay scales (VTPTrainer(param_groups=...)): vtp_adamw_dev_masked and vtp_adamw_ema_dev
+ * with a group index in place of the exemption flag.  group4: uint8 [n / 4], the group of elements [4i, 4i + 4) (parameters are padded
+ * to 4 elements, so a float4 lies in one parameter); group_tab: DEVICE f32 [ngroups][2] rows {lr_scale, wd_scale}, 8-byte aligned,
+ * 1 <= ngroups <= 256.  Group g runs torch.optim.AdamW with lr = hyper[0] * lr_scale[g] and weight_decay = hyper[4] * wd_scale[g]:
+ * p *= 1 - lr_g * wd_g; m, v as in vtp_adamw_dev; p -= (lr_g / bc1) * m / (sqrt(v) / bc2_sqrt + eps).  lr_scale = 0 leaves p
+ * bit-unchanged while m, v and the fused EMA teacher still move (torch with lr = 0).  Rows {(1,1), (1,0)} with group4 = nodecay4
+ * reproduce the masked entry points bit for bit.  An index >= ngroups in group4 is clamped to the last row by the kernels (the table
+ * is never read past its end).  The table is device memory like hyper: a captured hipGraph replays with the values of each step.
+ * Same argument checks and error codes as their siblings; group4 and group_tab must not be NULL. */
+int vtp_adamw_dev_grouped(float* p, const float* g, float* m, float* v, void* p_bf16, const void* group4, const float* group_tab,
+                          int ngroups, long n, const float* hyper, void* stream);
+int vtp_adamw_ema_dev_grouped(float* p, const float* g, float* m, float* v, float* teacher, const void* group4, const float* group_tab,
+                              int ngroups, long n, const float* hyper, void* stream);
 /* Global gradient-norm clipping (torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2): total_norm = ||g||_2 over every
  * gradient, coef = clamp(max_norm / (total_norm + 1e-6), max=1), g *= coef) in front of the AdamW kernels above, without float
  * atomics: bitwise reproducible for a given gradient and partials layout.

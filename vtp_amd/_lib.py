@@ -88,6 +88,8 @@ SIGNATURES = {
     "vtp_lpips_tap": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
     "vtp_ema_dev": [_P, _P, _L, _P, _P],
     "vtp_adamw_ema_dev": [_P, _P, _P, _P, _P, _P, _L, _P, _P],
+    "vtp_adamw_dev_grouped": [_P, _P, _P, _P, _P, _P, _P, _I, _L, _P, _P],
+    "vtp_adamw_ema_dev_grouped": [_P, _P, _P, _P, _P, _P, _P, _I, _L, _P, _P],
     "vtp_sumsq_partials_count": [_L],
     "vtp_sumsq_partials": [_P, _L, _P, _P],
     "vtp_sum_partials": [_P, _I, _P, _P],

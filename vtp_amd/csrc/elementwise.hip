@@ -473,6 +473,49 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
   }
 }
 
+// ---- per-parameter-group learning-rate / weight-decay scales (VTPTrainer(param_groups=...)) ----------------------------------
+// group4[i] names the group of elements [4i, 4i + 4) (one index per float4, where the masked kernels read one flag) and group_tab holds
+// ngroups <= 256 rows {lr_scale, wd_scale}: group g steps with lr_g = lr * lr_scale[g] and decays with wd_g = wd * wd_scale[g], i.e.
+// torch.optim.AdamW with that group's lr / weight_decay.  The index differs from lane to lane, so the table cannot come through scalar
+// loads; it is COPIED INTO LDS once per workgroup (<= 2 KiB: thread g loads row g, folds the step's lr / wd / bc1 in and stores
+// {keep, lr_g / bc1}), and every float4 costs one 8-byte LDS read behind its index byte -- no second trip to global memory behind the
+// byte.  The folded values are the masked kernels' own expressions, so rows {(1,1), (1,0)} with group4 = nodecay4 give their bits.
+// An index >= ngroups is CLAMPED to the last row here (the table is never read past its end); VTPTrainer builds only valid indices.
+__device__ __forceinline__ float2 fold_group_row(float2 row, float lr, float wd, float bc1) {
+  const float lr_g = lr * row.x, wd_g = wd * row.y;
+  return make_float2(1.f - lr_g * wd_g, lr_g / bc1);  // lr_scale = 0: keep = 1 and a step of 0 -- p keeps its bits, m and v still move
+}
+
+__global__ __launch_bounds__(256) void adamw_grouped_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                            float* __restrict__ m, float* __restrict__ v, bf16* __restrict__ pb, long n,
+                                                            const float* __restrict__ hyper, const uint8_t* __restrict__ group4,
+                                                            const float2* __restrict__ group_tab, int ngroups) {
+  __shared__ float2 tab[256];
+  const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4], bc1 = hyper[5], bc2_sqrt = hyper[6], gs = hyper[7];
+  if ((int)threadIdx.x < ngroups) tab[threadIdx.x] = fold_group_row(group_tab[threadIdx.x], lr, wd, bc1);
+  __syncthreads();
+  const long n4 = n / 4;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256L) {
+    f32x4 pv = *(const f32x4*)(p + 4 * i), gv = *(const f32x4*)(g + 4 * i);
+    f32x4 mv = *(const f32x4*)(m + 4 * i), vv = *(const f32x4*)(v + 4 * i);
+    const float2 row = tab[min((int)group4[i], ngroups - 1)];
+    const float keep = row.x, step = row.y;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float gg = gv[e] * gs;
+      pv[e] *= keep;
+      mv[e] = b1 * mv[e] + (1.f - b1) * gg;
+      vv[e] = b2 * vv[e] + (1.f - b2) * gg * gg;
+      const float denom = sqrtf(vv[e]) / bc2_sqrt + eps;
+      pv[e] -= step * (mv[e] / denom);
+    }
+    *(f32x4*)(p + 4 * i) = pv;
+    *(f32x4*)(m + 4 * i) = mv;
+    *(f32x4*)(v + 4 * i) = vv;
+    if (pb) *(bf16x4*)(pb + 4 * i) = __builtin_convertvector(pv, bf16x4);
+  }
+}
+
 // dst[i] (+)= sum_s slabs[s*stride + i]   (split-K wgrad partials -> flat gradient buffer)
 __global__ __launch_bounds__(256) void reduce_slabs_kernel(const float* __restrict__ slabs, long stride, int S,
                                                            float* __restrict__ dst, long n, int accumulate) {
@@ -533,6 +576,57 @@ __global__ __launch_bounds__(256) void adamw_ema_kernel(float* __restrict__ p, c
       vv[u][e] = b2 * vv[u][e] + (1.f - b2) * gg * gg;
       const float denom = sqrtf(vv[u][e]) / bc2_sqrt + eps;
       pv[u][e] -= (lr / bc1) * (mv[u][e] / denom);
+    }
+    *(f32x4*)(p + 4 * i) = pv[u];
+    *(f32x4*)(m + 4 * i) = mv[u];
+    *(f32x4*)(v + 4 * i) = vv[u];
+    if (t) *(f32x4*)(t + 4 * i) = tv[u] * mom + pv[u] * (1.f - mom);
+  }
+}
+
+// adamw_ema_kernel with per-group scales (see adamw_grouped_kernel): the same short-lived block -- 4096 elements, no grid-stride loop.
+// The thread's table row is requested first and its 16-20 float4 loads and four index bytes right behind it, all before the first use;
+// the LDS copy of the table is written while they are in flight, and the lookups follow the one barrier.
+__global__ __launch_bounds__(256) void adamw_ema_grouped_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                                float* __restrict__ v, float* __restrict__ t, long n4,
+                                                                const float* __restrict__ hyper, const uint8_t* __restrict__ group4,
+                                                                const float2* __restrict__ group_tab, int ngroups) {
+  __shared__ float2 tab[256];
+  const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4], bc1 = hyper[5], bc2_sqrt = hyper[6], gs = hyper[7];
+  const float mom = hyper[9];
+  const long base = blockIdx.x * 1024L + threadIdx.x;
+  float2 row = make_float2(1.f, 1.f);
+  if ((int)threadIdx.x < ngroups) row = group_tab[threadIdx.x];
+  f32x4 pv[4], gv[4], mv[4], vv[4], tv[4];
+  int gi[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const long i = base + u * 256;
+    if (i < n4) {
+      pv[u] = *(const f32x4*)(p + 4 * i);
+      gv[u] = *(const f32x4*)(g + 4 * i);
+      mv[u] = *(const f32x4*)(m + 4 * i);
+      vv[u] = *(const f32x4*)(v + 4 * i);
+      if (t) tv[u] = *(const f32x4*)(t + 4 * i);
+      gi[u] = group4[i];
+    }
+  }
+  if ((int)threadIdx.x < ngroups) tab[threadIdx.x] = fold_group_row(row, lr, wd, bc1);
+  __syncthreads();
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const long i = base + u * 256;
+    if (i >= n4) continue;
+    const float2 r = tab[min(gi[u], ngroups - 1)];
+    const float keep = r.x, step = r.y;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float gg = gv[u][e] * gs;
+      pv[u][e] *= keep;
+      mv[u][e] = b1 * mv[u][e] + (1.f - b1) * gg;
+      vv[u][e] = b2 * vv[u][e] + (1.f - b2) * gg * gg;
+      const float denom = sqrtf(vv[u][e]) / bc2_sqrt + eps;
+      pv[u][e] -= step * (mv[u][e] / denom);
     }
     *(f32x4*)(p + 4 * i) = pv[u];
     *(f32x4*)(m + 4 * i) = mv[u];
@@ -859,4 +953,23 @@ extern "C" int vtp_adamw_ema_dev(float* p, const float* g, float* m, float* v, f
   hipLaunchKernelGGL(adamw_ema_kernel, dim3((unsigned)((n / 4 + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, teacher,
                      n / 4, hyper, (const uint8_t*)nodecay4);
   return check_launch("adamw_ema_dev");
+}
+
+extern "C" int vtp_adamw_dev_grouped(float* p, const float* g, float* m, float* v, void* p_bf16, const void* group4,
+                                     const float* group_tab, int ngroups, long n, const float* hyper, void* stream) {
+  VTP_REQUIRE(p && g && m && v && hyper && n > 0 && n % 4 == 0, "vtp_adamw_dev_grouped: bad argument (n %% 4 == 0)");
+  VTP_REQUIRE(group4 && group_tab && ngroups >= 1 && ngroups <= 256, "vtp_adamw_dev_grouped: bad group table (1 <= ngroups <= 256)");
+  hipLaunchKernelGGL(adamw_grouped_kernel, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16*)p_bf16, n,
+                     hyper, (const uint8_t*)group4, (const float2*)group_tab, ngroups);
+  return check_launch("adamw_dev_grouped");
+}
+
+extern "C" int vtp_adamw_ema_dev_grouped(float* p, const float* g, float* m, float* v, float* teacher, const void* group4,
+                                         const float* group_tab, int ngroups, long n, const float* hyper, void* stream) {
+  VTP_REQUIRE(p && g && m && v && hyper && n > 0 && n % 4 == 0, "vtp_adamw_ema_dev_grouped: bad argument (n %% 4 == 0)");
+  VTP_REQUIRE(group4 && group_tab && ngroups >= 1 && ngroups <= 256, "vtp_adamw_ema_dev_grouped: bad group table (1 <= ngroups <= 256)");
+  VTP_REQUIRE(n / 4096 < 0x7fffffffL, "vtp_adamw_ema_dev_grouped: range too long for one launch");
+  hipLaunchKernelGGL(adamw_ema_grouped_kernel, dim3((unsigned)((n / 4 + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+                     teacher, n / 4, hyper, (const uint8_t*)group4, (const float2*)group_tab, ngroups);
+  return check_launch("adamw_ema_dev_grouped");
 }

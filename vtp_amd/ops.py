@@ -507,6 +507,20 @@ def adamw_ema_dev(p, g, m, v, teacher, n, hyper, nodecay4=None):
     _lib.check(_lib_().vtp_adamw_ema_dev(_p(p), _p(g), _p(m), _p(v), _p(teacher), _p(nodecay4), n, _p(hyper), _s()), "vtp_adamw_ema_dev")
 
 
+
+def adamw_dev_grouped(p, g, m, v, p_bf16, n, hyper, group4, group_tab, ngroups):
+    """adamw_dev with per-group scales.  group4: uint8 [n / 4], the group of each float4; group_tab: device f32 [ngroups, 2] rows
+    (lr_scale, wd_scale): group g steps with lr * lr_scale[g] and decays with weight_decay * wd_scale[g]"""
+    _lib.check(_lib_().vtp_adamw_dev_grouped(_p(p), _p(g), _p(m), _p(v), _p(p_bf16), _p(group4), _p(group_tab), ngroups, n, _p(hyper),
+                                             _s()), "vtp_adamw_dev_grouped")
+
+
+def adamw_ema_dev_grouped(p, g, m, v, teacher, n, hyper, group4, group_tab, ngroups):
+    """adamw_ema_dev with per-group scales (see adamw_dev_grouped)"""
+    _lib.check(_lib_().vtp_adamw_ema_dev_grouped(_p(p), _p(g), _p(m), _p(v), _p(teacher), _p(group4), _p(group_tab), ngroups, n,
+                                                 _p(hyper), _s()), "vtp_adamw_ema_dev_grouped")
+
+
 # ---- global gradient-norm clipping (vtp_amd/csrc/gradnorm.hip; torch.nn.utils.clip_grad_norm_, norm_type 2) ---------------------
 def sumsq_partials_count(n: int) -> int:
     """number of fp64 partials sumsq_partials writes for a range of n elements (depends on n only)"""

@@ -92,6 +92,10 @@ def _adamw(p, g, m, v, n, hyper):
     ops.adamw_dev(p, g, m, v, None, n, hyper)
 
 
+def _adamw_grouped(p, g, m, v, n, hyper, group4, group_tab):
+    ops.adamw_dev_grouped(p, g, m, v, None, n, hyper, group4, group_tab, group_tab.shape[0])
+
+
 def _ema(t, s, n, momentum):
     ops.ema(t, s, n, momentum)
 
@@ -126,6 +130,8 @@ _define("pixel_unshuffle16(Tensor d_img, Tensor(t!) dt, int B, int h, int w) -> 
 _define("l1_loss_fwd_bwd(Tensor t, Tensor target, Tensor(d!) dt, Tensor(l!) loss_sum, int B, int h, int w, float gscale) -> ()",
         _l1_loss_fwd_bwd)
 _define("adamw(Tensor(p!) p, Tensor g, Tensor(m!) m, Tensor(v!) v, int n, Tensor hyper) -> ()", _adamw)
+_define("adamw_grouped(Tensor(p!) p, Tensor g, Tensor(m!) m, Tensor(v!) v, int n, Tensor hyper, Tensor group4, Tensor group_tab) -> ()",
+        _adamw_grouped)
 _define("ema(Tensor(t!) t, Tensor s, int n, float momentum) -> ()", _ema)
 _define("clip_loss(Tensor img_l, Tensor txt_l, Tensor img_all, Tensor txt_all, Tensor logit_scale, int label_offset, Tensor(a!) loss_sum, "
         "Tensor(b!) d_img_l, Tensor(c!) d_txt_l, Tensor(d!) d_img_all, Tensor(e!) d_txt_all, Tensor(f!) d_logit_scale, "

@@ -263,6 +263,114 @@ def _max_norm_value(value) -> float:
     return f
 
 
+MAX_PARAM_GROUPS = 128  # one table row per (group, decay-exempt) pair, 256 rows at most (csrc/elementwise.hip)
+
+
+def _group_scale(group: dict, key: str) -> float:
+    value = group.get(key, 1.0)
+    try:
+        f = float(value)
+    except (TypeError, ValueError):
+        f = float("nan")
+    if isinstance(value, bool) or not (math.isfinite(f) and f >= 0):
+        raise ValueError(f"param group {group.get('name')!r}: {key} must be a finite number >= 0, got {value!r}")
+    return f
+
+
+def resolve_param_groups(param_groups, shapes: dict, no_decay=None):
+    """VTPTrainer(param_groups=...) on the host.  param_groups: [{"name", "match": tuple of name prefixes | callable (name, shape) ->
+    bool, "lr_scale" = 1.0, "wd_scale" = 1.0}]; shapes: parameter name -> shape (the keys of store.offsets); no_decay: None or a
+    predicate (name, shape) -> bool.  The first matching group takes a parameter; what no group matches falls into an implicit last
+    group "default" with scales (1, 1).  Returns (groups, rows): `groups` the list the trainer exposes (dicts {"name", "lr_scale",
+    "wd_scale"}, in table order), `rows` parameter name -> table row = 2 * group index + (1 if the parameter is exempt from decay)."""
+    user = []
+    for g in param_groups:
+        if not isinstance(g, dict) or "name" not in g or "match" not in g:
+            raise ValueError(f"a param group is a dict with 'name' and 'match', got {g!r}")
+        unknown = set(g) - {"name", "match", "lr_scale", "wd_scale"}
+        if unknown:
+            raise ValueError(f"param group {g['name']!r}: unknown keys {sorted(unknown)}")
+        match = g["match"]
+        if isinstance(match, str):
+            match = (match,)
+        if not callable(match):
+            match = tuple(match)
+            if not match or not all(isinstance(x, str) for x in match):
+                raise ValueError(f"param group {g['name']!r}: match must be a tuple of name prefixes or a callable (name, shape) -> bool")
+        user.append(({"name": str(g["name"]), "lr_scale": _group_scale(g, "lr_scale"), "wd_scale": _group_scale(g, "wd_scale")}, match))
+    names = [g["name"] for g, _ in user]
+    dup = sorted({n for n in names if names.count(n) > 1})
+    if dup:
+        raise ValueError(f"duplicate param group names: {dup}")
+    if len(user) > MAX_PARAM_GROUPS:
+        raise ValueError(f"{len(user)} param groups: at most {MAX_PARAM_GROUPS} are supported")
+    rows, hit, rest = {}, [False] * len(user), False
+    for name, shape in shapes.items():
+        shape = tuple(shape)
+        gi = next((i for i, (_, match) in enumerate(user)
+                   if (match(name, shape) if callable(match) else name.startswith(match))), len(user))
+        if gi < len(user):
+            hit[gi] = True
+        else:
+            rest = True
+        rows[name] = 2 * gi + (1 if no_decay is not None and no_decay(name, shape) else 0)
+    empty = [g["name"] for (g, _), h in zip(user, hit) if not h]
+    if empty:
+        raise ValueError(f"param groups that match no parameter: {empty}")
+    groups = [g for g, _ in user]
+    if rest:
+        if "default" in names:
+            raise ValueError("duplicate param group names: ['default'] (the implicit group of the unmatched parameters)")
+        if len(groups) == MAX_PARAM_GROUPS:
+            raise ValueError(f"{MAX_PARAM_GROUPS} param groups and unmatched parameters: the implicit 'default' group would be one too many")
+        groups.append({"name": "default", "lr_scale": 1.0, "wd_scale": 1.0})
+    return groups, rows
+
+
+def group_table(groups) -> List[float]:
+    """the device table of this step: rows {lr_scale, wd_scale}, two per group -- row 2i for its decayed parameters, row 2i + 1 for
+    those that no_decay exempts (wd_scale 0 whatever the group says)"""
+    vals = []
+    for g in groups:
+        ls, ws = _group_scale(g, "lr_scale"), _group_scale(g, "wd_scale")
+        vals += [ls, ws, ls, 0.0]
+    return vals
+
+
+_LAYER0 = ("cls_token", "mask_token", "storage_tokens", "register_tokens", "pos_embed", "positional_embedding", "rope_embed.")
+
+
+def layerwise_lr_decay(names, depth: int, decay: float, patch_embed_lr_mult: float = 1.0, prefix: str = "trunk."):
+    """DINOv2's layer-wise learning-rate decay as a param_groups list.  Of the parameters under `prefix`, patch_embed.*, the cls /
+    mask / storage tokens and positional tables have layer id 0, blocks.i.* have i + 1, everything else (the final norm) depth + 1;
+    lr_scale = decay ** (depth + 1 - layer id), times patch_embed_lr_mult for patch_embed.*.  Parameters outside `prefix` are left
+    to the default group; parameters with equal scales share a group."""
+    import re
+    by_scale: dict = {}
+    for name in names:
+        if not name.startswith(prefix):
+            continue
+        local = name[len(prefix):]
+        blk = re.match(r"blocks\.(\d+)\.", local)
+        patch = local.startswith("patch_embed.")
+        if patch or local.startswith(_LAYER0):
+            layer = 0
+        elif blk:
+            layer = int(blk.group(1)) + 1
+        else:
+            layer = depth + 1
+        scale = decay ** (depth + 1 - layer)
+        if patch:
+            scale *= patch_embed_lr_mult
+        label = f"layer{layer}" + (".patch_embed" if patch else "")
+        labels, members = by_scale.setdefault(scale, ([], set()))
+        if label not in labels:
+            labels.append(label)
+        members.add(name)
+    return [{"name": prefix + "+".join(labels), "match": (lambda name, shape, members=frozenset(members): name in members),
+             "lr_scale": scale, "wd_scale": 1.0} for scale, (labels, members) in by_scale.items()]
+
+
 CLIP_PREFIXES = ("visual_proj.", "text_transformer.", "token_embedding.", "positional_embedding", "ln_final.",
                  "text_projection", "logit_scale", "logit_bias")
 
@@ -279,11 +387,14 @@ class VTPTrainer:
                  clip_drop_rate: Optional[float] = None, ssl_drop_rate: Optional[float] = None, rec_drop_rate: Optional[float] = None,
                  drop_seed: int = 0, centering: str = "softmax", koleo_weight: float = 0.0, sk_iterations: int = 3,
                  shard_optimizer: Optional[bool] = None, grad_dtype: str = "fp32", no_decay="default",
-                 force_collectives: bool = False, max_grad_norm: Optional[float] = None):
+                 force_collectives: bool = False, max_grad_norm: Optional[float] = None, param_groups=None):
         """lpips: a vtp_amd.LPIPS module (frozen, weights loaded by the caller) -- with perceptual_weight > 0 the
         reconstruction objective is rec_weight * L1 + perceptual_weight * mean_b LPIPS(decoded_b, image_b).
         max_grad_norm: global gradient-norm clipping in front of AdamW (torch.nn.utils.clip_grad_norm_, norm_type 2); the step's
-        pre-clip norm and coefficient land in self.grad_norm / self.grad_clip_coef (device tensors).  None: no clipping."""
+        pre-clip norm and coefficient land in self.grad_norm / self.grad_clip_coef (device tensors).  None: no clipping.
+        param_groups: per-group learning-rate / weight-decay scales (resolve_param_groups; layerwise_lr_decay builds DINOv2's list):
+        group g runs AdamW with lr * lr_scale and weight_decay * wd_scale.  self.param_groups lists them; its scales are read at
+        every step() (a scheduler may mutate them; no re-capture).  None: one lr / weight decay for every parameter."""
         self.model = model
         # stochastic depth (block.py:207-289): the student trunk's rate per objective (clip_drop_rate / ssl_drop_rate / rec_drop_rate,
         # vtp.py:205-207; `drop_rate` sets all three) and the pixel decoder's drop_path_rate.  The objectives are items of ONE list
@@ -345,6 +456,17 @@ class VTPTrainer:
                 if no_decay(name, tuple(st.params[name].shape)):
                     flags[o // 4:(o + (k + 3) // 4 * 4) // 4] = 1
             self.nodecay4 = flags.to(st.device)
+        # per-group lr / weight-decay scales: one table row index per float4 where nodecay4 holds one flag, and a device table of
+        # {lr_scale, wd_scale} rows that _set_hyper refreshes every step (two rows per group: decayed / exempt -- no_decay composes)
+        self.param_groups = self.group_tab = self._group4 = self._group_ring = None
+        if param_groups is not None:
+            shapes = {name: tuple(st.params[name].shape) for name in st.offsets}
+            self.param_groups, rows = resolve_param_groups(param_groups, shapes, no_decay)
+            idx = torch.zeros(st.numel // 4, dtype=torch.uint8)
+            for name, (o, k) in st.offsets.items():
+                idx[o // 4:(o + (k + 3) // 4 * 4) // 4] = rows[name]
+            self._group4 = idx.to(st.device)
+            self.group_tab = torch.tensor(group_table(self.param_groups), dtype=F32, device=st.device).view(-1, 2)
         self.step_no = 0
         self.loss_sum = torch.zeros(1, dtype=F32, device=st.device)       # L1 numerator
         self.clip_loss_sum = torch.zeros(1, dtype=F32, device=st.device)  # contrastive loss (already a mean)
@@ -739,9 +861,15 @@ class VTPTrainer:
         """fused AdamW (+ EMA teacher) over the bucket's ranges and the refresh of its bf16 weight copies, on the current stream"""
         st = self.store
         pieces, runs = self._opt_plan(keys, self._opt_ema)
+        tab = self.group_tab
         for a, b, tl in pieces:
-            ops.adamw_ema_dev(st.flat_p[a:b], st.flat_g[a:b], self.m[a:b], self.v[a:b], None if tl is None else st.flat_p[tl:tl + b - a],
-                              b - a, self.hyper, None if self.nodecay4 is None else self.nodecay4[a // 4:b // 4])
+            teacher = None if tl is None else st.flat_p[tl:tl + b - a]
+            if tab is not None:
+                ops.adamw_ema_dev_grouped(st.flat_p[a:b], st.flat_g[a:b], self.m[a:b], self.v[a:b], teacher, b - a, self.hyper,
+                                          self._group4[a // 4:b // 4], tab, tab.shape[0])
+            else:
+                ops.adamw_ema_dev(st.flat_p[a:b], st.flat_g[a:b], self.m[a:b], self.v[a:b], teacher,
+                                  b - a, self.hyper, None if self.nodecay4 is None else self.nodecay4[a // 4:b // 4])
         st.prep_runs(runs)
         # derived weights that depend only on what this bucket updated (the DINO heads' weight-normed last layers, student and -- through
         # the fused EMA -- teacher): re-derived here, beside the backward, not in the serial tail
@@ -751,6 +879,16 @@ class VTPTrainer:
                 hook()
                 self._hooks_done.add(hook)
         self._opt_done += [(a, b) for a, b, _ in pieces]
+
+    def _adamw(self, lo, hi, g):
+        """AdamW over flat elements [lo, hi) (4-element aligned) with the gradient g: grouped when param_groups were given"""
+        st, tab = self.store, self.group_tab
+        if tab is not None:
+            ops.adamw_dev_grouped(st.flat_p[lo:hi], g, self.m[lo:hi], self.v[lo:hi], None, hi - lo, self.hyper,
+                                  self._group4[lo // 4:hi // 4], tab, tab.shape[0])
+        else:
+            ops.adamw_dev(st.flat_p[lo:hi], g, self.m[lo:hi], self.v[lo:hi], None, hi - lo, self.hyper,
+                          None if self.nodecay4 is None else self.nodecay4[lo // 4:hi // 4])
 
     def _opt_launch(self, keys):
         if not keys:
@@ -1039,8 +1177,7 @@ class VTPTrainer:
                 if n > 0:
                     if rec.g32 is not rec.g_out and not self._clip:
                         rec.g32.copy_(rec.g_out)
-                    ops.adamw_dev(st.flat_p[rec.a:rec.b], rec.g32, self.m[rec.a:rec.b], self.v[rec.a:rec.b], None, n, self.hyper,
-                                  None if self.nodecay4 is None else self.nodecay4[rec.a // 4:rec.b // 4])
+                    self._adamw(rec.a, rec.b, rec.g32)
                     rec.p_send[:n].copy_(st.flat_p[rec.a:rec.b])
             yield lambda: self.bucketer.all_gather_params(st.flat_p, recs)
             for rec in recs:
@@ -1065,8 +1202,7 @@ class VTPTrainer:
                 self._clip_sumsq(self._clip_plan([(st.flat_g[lo:hi], hi - lo) for lo, hi in ranges]))
                 self._clip_finalize()
             for lo, hi in ranges:
-                ops.adamw_dev(st.flat_p[lo:hi], st.flat_g[lo:hi], self.m[lo:hi], self.v[lo:hi], None, hi - lo, self.hyper,
-                              None if self.nodecay4 is None else self.nodecay4[lo // 4:hi // 4])
+                self._adamw(lo, hi, st.flat_g[lo:hi])
         if text is not None:
             st.p("logit_scale").clamp_(max=math.log(100.0))  # OpenCLIP training-loop convention
         if self.overlap_opt:  # EMA and the weight refresh rode along bucket by bucket
@@ -1172,6 +1308,7 @@ class VTPTrainer:
         return full
 
     def _set_hyper(self):
+        tab = None if self.param_groups is None else group_table(self.param_groups)  # (a bad scale raises before anything moves)
         self.step_no += 1
         b1, b2 = self.betas
         vals = [self.lr, b1, b2, self.eps, self.wd, 1.0 - b1 ** self.step_no, (1.0 - b2 ** self.step_no) ** 0.5,
@@ -1190,6 +1327,11 @@ class VTPTrainer:
             events[slot].synchronize()
         ring[slot].copy_(torch.tensor(vals, dtype=torch.float32))
         self.hyper.copy_(ring[slot], non_blocking=True)
+        if tab is not None:  # the group table rides in the same slot of a ring of its own, under the same event
+            if self._group_ring is None:
+                self._group_ring = torch.zeros(ring.shape[0], len(tab), dtype=torch.float32).pin_memory()
+            self._group_ring[slot].copy_(torch.tensor(tab, dtype=torch.float32))
+            self.group_tab.view(-1).copy_(self._group_ring[slot], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
         events[slot] = ev
@@ -1289,6 +1431,8 @@ class VTPTrainer:
             sd["exp_avg_sq"][name] = v[o:o + k].detach().clone().view(st.params[name].shape).cpu()
         if self.ssl_head is not None:
             sd["center_dino"], sd["center_ibot"] = self.center_dino.cpu().clone(), self.center_ibot.cpu().clone()
+        if self.param_groups is not None:
+            sd["param_groups"] = [{k: g[k] for k in ("name", "lr_scale", "wd_scale")} for g in self.param_groups]
         aug = [e.rope_aug.get_state() for e in self._aug_engines() if e.rope_aug.active]
         if aug:  # this rank's RoPE-augmentation streams (per-rank state: saved and restored rank by rank)
             sd["rope_aug_rng"] = aug
@@ -1299,6 +1443,16 @@ class VTPTrainer:
         missing = [n for n in st.offsets if n not in sd["exp_avg"] or n not in sd["exp_avg_sq"]]
         if missing:
             raise KeyError(f"optimizer state lacks {len(missing)} parameters, e.g. {missing[:3]}")
+        if "param_groups" in sd or self.param_groups is not None:
+            # scales are restored by name; a checkpoint written without groups leaves a grouped trainer's scales as constructed
+            saved = sd.get("param_groups")
+            mine = [g["name"] for g in self.param_groups or []]
+            if saved is not None:
+                if [g["name"] for g in saved] != mine:
+                    raise ValueError(f"checkpoint param groups {[g['name'] for g in saved]} differ from the trainer's {mine}")
+                scales = [(_group_scale(g, "lr_scale"), _group_scale(g, "wd_scale")) for g in saved]
+                for g, (ls, ws) in zip(self.param_groups, scales):
+                    g["lr_scale"], g["wd_scale"] = ls, ws
         self.step_no = int(sd["step"])
         for name, (o, k) in st.offsets.items():
             self.m[o:o + k].copy_(sd["exp_avg"][name].reshape(-1))
