@@ -444,35 +444,9 @@ __global__ __launch_bounds__(256) void gelu_bwd_kernel(const bf16* __restrict__ 
 }
 
 // ---------------------------------------------------------------- optimizer / EMA (flat buffers)
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                    float* __restrict__ m, float* __restrict__ v,
-                                                    bf16* __restrict__ pb, long n, float lr, float b1, float b2, float eps,
-                                                    float wd, float bc1, float bc2_sqrt, float gs,
-                                                    const float* __restrict__ hyper, const uint8_t* __restrict__ nodecay4 = nullptr) {
-  if (hyper) {  // device-resident hyper-parameters: a captured hipGraph replays with fresh values every step
-    lr = hyper[0]; b1 = hyper[1]; b2 = hyper[2]; eps = hyper[3]; wd = hyper[4]; bc1 = hyper[5]; bc2_sqrt = hyper[6]; gs = hyper[7];
-  }
-  const long n4 = n / 4;
-  for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256L) {
-    f32x4 pv = *(const f32x4*)(p + 4 * i), gv = *(const f32x4*)(g + 4 * i);
-    f32x4 mv = *(const f32x4*)(m + 4 * i), vv = *(const f32x4*)(v + 4 * i);
-    const float keep = (nodecay4 && nodecay4[i]) ? 1.f : 1.f - lr * wd;  // parameters are padded to 4 elements: one flag per float4
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float gg = gv[e] * gs;
-      pv[e] *= keep;
-      mv[e] = b1 * mv[e] + (1.f - b1) * gg;
-      vv[e] = b2 * vv[e] + (1.f - b2) * gg * gg;
-      const float denom = sqrtf(vv[e]) / bc2_sqrt + eps;
-      pv[e] -= (lr / bc1) * (mv[e] / denom);
-    }
-    *(f32x4*)(p + 4 * i) = pv;
-    *(f32x4*)(m + 4 * i) = mv;
-    *(f32x4*)(v + 4 * i) = vv;
-    if (pb) *(bf16x4*)(pb + 4 * i) = __builtin_convertvector(pv, bf16x4);
-  }
-}
-
+// AdamW is written once per launch shape (adamw_kernel: grid-stride; adamw_ema_kernel: short-lived blocks with the EMA teacher fused in)
+// as a template over how a float4 finds its weight decay and step: TABLE = false reads one exemption flag per float4 (idx4 may be NULL),
+// TABLE = true one row index per float4 into the group table.  Each instantiation compiles to what the separate kernels did.
 // ---- per-parameter-group learning-rate / weight-decay scales (VTPTrainer(param_groups=...)) ----------------------------------
 // group4[i] names the group of elements [4i, 4i + 4) (one index per float4, where the masked kernels read one flag) and group_tab holds
 // ngroups <= 256 rows {lr_scale, wd_scale}: group g steps with lr_g = lr * lr_scale[g] and decays with wd_g = wd * wd_scale[g], i.e.
@@ -486,20 +460,32 @@ __device__ __forceinline__ float2 fold_group_row(float2 row, float lr, float wd,
   return make_float2(1.f - lr_g * wd_g, lr_g / bc1);  // lr_scale = 0: keep = 1 and a step of 0 -- p keeps its bits, m and v still move
 }
 
-__global__ __launch_bounds__(256) void adamw_grouped_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                            float* __restrict__ m, float* __restrict__ v, bf16* __restrict__ pb, long n,
-                                                            const float* __restrict__ hyper, const uint8_t* __restrict__ group4,
-                                                            const float2* __restrict__ group_tab, int ngroups) {
-  __shared__ float2 tab[256];
-  const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4], bc1 = hyper[5], bc2_sqrt = hyper[6], gs = hyper[7];
-  if ((int)threadIdx.x < ngroups) tab[threadIdx.x] = fold_group_row(group_tab[threadIdx.x], lr, wd, bc1);
-  __syncthreads();
+template <bool TABLE>
+__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                    float* __restrict__ m, float* __restrict__ v,
+                                                    bf16* __restrict__ pb, long n, float lr, float b1, float b2, float eps,
+                                                    float wd, float bc1, float bc2_sqrt, float gs,
+                                                    const float* __restrict__ hyper, const uint8_t* __restrict__ idx4,
+                                                    const float2* __restrict__ group_tab, int ngroups) {
+  __shared__ float2 tab[TABLE ? 256 : 1];
+  if (TABLE || hyper) {  // device-resident hyper-parameters: a captured hipGraph replays with fresh values every step
+    lr = hyper[0]; b1 = hyper[1]; b2 = hyper[2]; eps = hyper[3]; wd = hyper[4]; bc1 = hyper[5]; bc2_sqrt = hyper[6]; gs = hyper[7];
+  }
+  if constexpr (TABLE) {
+    if ((int)threadIdx.x < ngroups) tab[threadIdx.x] = fold_group_row(group_tab[threadIdx.x], lr, wd, bc1);
+    __syncthreads();
+  }
   const long n4 = n / 4;
   for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256L) {
     f32x4 pv = *(const f32x4*)(p + 4 * i), gv = *(const f32x4*)(g + 4 * i);
     f32x4 mv = *(const f32x4*)(m + 4 * i), vv = *(const f32x4*)(v + 4 * i);
-    const float2 row = tab[min((int)group4[i], ngroups - 1)];
-    const float keep = row.x, step = row.y;
+    float keep, step;  // parameters are padded to 4 elements: one flag / row index per float4
+    if constexpr (TABLE) {
+      const float2 row = tab[min((int)idx4[i], ngroups - 1)];
+      keep = row.x, step = row.y;
+    } else {
+      keep = (idx4 && idx4[i]) ? 1.f : 1.f - lr * wd, step = lr / bc1;
+    }
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const float gg = gv[e] * gs;
@@ -542,63 +528,23 @@ __global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ t, const f
 // bucket's gradients are final, it runs beside the rest of the backward -- so a block is SHORT-LIVED (4096 elements, no grid-stride
 // loop: it takes a free CU slot between the persistent GEMM workgroups and gives it back after one round of loads and stores) and
 // requests all of its 16-20 float4 loads before the first use.  hyper[9] = teacher momentum.  Same arithmetic, element by element,
-// as adamw_kernel followed by ema_kernel.
+// as adamw_kernel followed by ema_kernel.  TABLE (per-group scales, see adamw_kernel): the thread's table row is requested first, the
+// LDS copy of the table is written while the float4 loads are in flight, and the lookups follow the one barrier.
+template <bool TABLE>
 __global__ __launch_bounds__(256) void adamw_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                         float* __restrict__ v, float* __restrict__ t, long n4,
-                                                        const float* __restrict__ hyper, const uint8_t* __restrict__ nodecay4) {
-  const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4], bc1 = hyper[5], bc2_sqrt = hyper[6], gs = hyper[7];
-  const float mom = hyper[9];
-  const long base = blockIdx.x * 1024L + threadIdx.x;
-  f32x4 pv[4], gv[4], mv[4], vv[4], tv[4];
-  bool nd[4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const long i = base + u * 256;
-    if (i < n4) {
-      pv[u] = *(const f32x4*)(p + 4 * i);
-      gv[u] = *(const f32x4*)(g + 4 * i);
-      mv[u] = *(const f32x4*)(m + 4 * i);
-      vv[u] = *(const f32x4*)(v + 4 * i);
-      if (t) tv[u] = *(const f32x4*)(t + 4 * i);
-      nd[u] = nodecay4 && nodecay4[i];
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const long i = base + u * 256;
-    if (i >= n4) continue;
-    const float keep = nd[u] ? 1.f : 1.f - lr * wd;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float gg = gv[u][e] * gs;
-      pv[u][e] *= keep;
-      mv[u][e] = b1 * mv[u][e] + (1.f - b1) * gg;
-      vv[u][e] = b2 * vv[u][e] + (1.f - b2) * gg * gg;
-      const float denom = sqrtf(vv[u][e]) / bc2_sqrt + eps;
-      pv[u][e] -= (lr / bc1) * (mv[u][e] / denom);
-    }
-    *(f32x4*)(p + 4 * i) = pv[u];
-    *(f32x4*)(m + 4 * i) = mv[u];
-    *(f32x4*)(v + 4 * i) = vv[u];
-    if (t) *(f32x4*)(t + 4 * i) = tv[u] * mom + pv[u] * (1.f - mom);
-  }
-}
-
-// adamw_ema_kernel with per-group scales (see adamw_grouped_kernel): the same short-lived block -- 4096 elements, no grid-stride loop.
-// The thread's table row is requested first and its 16-20 float4 loads and four index bytes right behind it, all before the first use;
-// the LDS copy of the table is written while they are in flight, and the lookups follow the one barrier.
-__global__ __launch_bounds__(256) void adamw_ema_grouped_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                                float* __restrict__ v, float* __restrict__ t, long n4,
-                                                                const float* __restrict__ hyper, const uint8_t* __restrict__ group4,
-                                                                const float2* __restrict__ group_tab, int ngroups) {
-  __shared__ float2 tab[256];
+                                                        const float* __restrict__ hyper, const uint8_t* __restrict__ idx4,
+                                                        const float2* __restrict__ group_tab, int ngroups) {
+  __shared__ float2 tab[TABLE ? 256 : 1];
   const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4], bc1 = hyper[5], bc2_sqrt = hyper[6], gs = hyper[7];
   const float mom = hyper[9];
   const long base = blockIdx.x * 1024L + threadIdx.x;
   float2 row = make_float2(1.f, 1.f);
-  if ((int)threadIdx.x < ngroups) row = group_tab[threadIdx.x];
+  if constexpr (TABLE)
+    if ((int)threadIdx.x < ngroups) row = group_tab[threadIdx.x];
   f32x4 pv[4], gv[4], mv[4], vv[4], tv[4];
-  int gi[4];
+  int gi[4];   // TABLE: the row index
+  bool nd[4];  // !TABLE: the exemption flag
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
     const long i = base + u * 256;
@@ -608,17 +554,25 @@ __global__ __launch_bounds__(256) void adamw_ema_grouped_kernel(float* __restric
       mv[u] = *(const f32x4*)(m + 4 * i);
       vv[u] = *(const f32x4*)(v + 4 * i);
       if (t) tv[u] = *(const f32x4*)(t + 4 * i);
-      gi[u] = group4[i];
+      if constexpr (TABLE) gi[u] = idx4[i];
+      else nd[u] = idx4 && idx4[i];
     }
   }
-  if ((int)threadIdx.x < ngroups) tab[threadIdx.x] = fold_group_row(row, lr, wd, bc1);
-  __syncthreads();
+  if constexpr (TABLE) {
+    if ((int)threadIdx.x < ngroups) tab[threadIdx.x] = fold_group_row(row, lr, wd, bc1);
+    __syncthreads();
+  }
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
     const long i = base + u * 256;
     if (i >= n4) continue;
-    const float2 r = tab[min(gi[u], ngroups - 1)];
-    const float keep = r.x, step = r.y;
+    float keep, step;
+    if constexpr (TABLE) {
+      const float2 r = tab[min(gi[u], ngroups - 1)];
+      keep = r.x, step = r.y;
+    } else {
+      keep = nd[u] ? 1.f : 1.f - lr * wd, step = lr / bc1;
+    }
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const float gg = gv[u][e] * gs;
@@ -907,24 +861,25 @@ extern "C" int vtp_adamw(float* p, const float* g, float* m, float* v, void* p_b
   VTP_REQUIRE(p && g && m && v && n > 0 && n % 4 == 0 && step >= 1, "vtp_adamw: bad argument (n %% 4 == 0, step >= 1)");
   const float bc1 = 1.f - powf(beta1, (float)step);
   const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
-  hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16*)p_bf16, n, lr,
-                     beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale, (const float*)nullptr);
+  hipLaunchKernelGGL(adamw_kernel<false>, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16*)p_bf16, n, lr,
+                     beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale, (const float*)nullptr, (const uint8_t*)nullptr,
+                     (const float2*)nullptr, 0);
   return check_launch("adamw");
 }
 
 extern "C" int vtp_adamw_dev(float* p, const float* g, float* m, float* v, void* p_bf16, long n, const float* hyper,
                              void* stream) {
   VTP_REQUIRE(p && g && m && v && hyper && n > 0 && n % 4 == 0, "vtp_adamw_dev: bad argument (n %% 4 == 0)");
-  hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16*)p_bf16, n, 0.f,
-                     0.f, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, hyper);
+  hipLaunchKernelGGL(adamw_kernel<false>, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16*)p_bf16, n, 0.f,
+                     0.f, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, hyper, (const uint8_t*)nullptr, (const float2*)nullptr, 0);
   return check_launch("adamw_dev");
 }
 
 extern "C" int vtp_adamw_dev_masked(float* p, const float* g, float* m, float* v, void* p_bf16, const void* nodecay4, long n,
                                     const float* hyper, void* stream) {
   VTP_REQUIRE(p && g && m && v && hyper && nodecay4 && n > 0 && n % 4 == 0, "vtp_adamw_dev_masked: bad argument (n %% 4 == 0)");
-  hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16*)p_bf16, n, 0.f,
-                     0.f, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, hyper, (const uint8_t*)nodecay4);
+  hipLaunchKernelGGL(adamw_kernel<false>, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16*)p_bf16, n, 0.f,
+                     0.f, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, hyper, (const uint8_t*)nodecay4, (const float2*)nullptr, 0);
   return check_launch("adamw_dev_masked");
 }
 
@@ -950,8 +905,8 @@ extern "C" int vtp_adamw_ema_dev(float* p, const float* g, float* m, float* v, f
                                  const float* hyper, void* stream) {
   VTP_REQUIRE(p && g && m && v && hyper && n > 0 && n % 4 == 0, "vtp_adamw_ema_dev: bad argument (n %% 4 == 0)");
   VTP_REQUIRE(n / 4096 < 0x7fffffffL, "vtp_adamw_ema_dev: range too long for one launch");
-  hipLaunchKernelGGL(adamw_ema_kernel, dim3((unsigned)((n / 4 + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, teacher,
-                     n / 4, hyper, (const uint8_t*)nodecay4);
+  hipLaunchKernelGGL(adamw_ema_kernel<false>, dim3((unsigned)((n / 4 + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+                     teacher, n / 4, hyper, (const uint8_t*)nodecay4, (const float2*)nullptr, 0);
   return check_launch("adamw_ema_dev");
 }
 
@@ -959,8 +914,8 @@ extern "C" int vtp_adamw_dev_grouped(float* p, const float* g, float* m, float* 
                                      const float* group_tab, int ngroups, long n, const float* hyper, void* stream) {
   VTP_REQUIRE(p && g && m && v && hyper && n > 0 && n % 4 == 0, "vtp_adamw_dev_grouped: bad argument (n %% 4 == 0)");
   VTP_REQUIRE(group4 && group_tab && ngroups >= 1 && ngroups <= 256, "vtp_adamw_dev_grouped: bad group table (1 <= ngroups <= 256)");
-  hipLaunchKernelGGL(adamw_grouped_kernel, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16*)p_bf16, n,
-                     hyper, (const uint8_t*)group4, (const float2*)group_tab, ngroups);
+  hipLaunchKernelGGL(adamw_kernel<true>, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16*)p_bf16, n, 0.f,
+                     0.f, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, hyper, (const uint8_t*)group4, (const float2*)group_tab, ngroups);
   return check_launch("adamw_dev_grouped");
 }
 
@@ -969,7 +924,7 @@ extern "C" int vtp_adamw_ema_dev_grouped(float* p, const float* g, float* m, flo
   VTP_REQUIRE(p && g && m && v && hyper && n > 0 && n % 4 == 0, "vtp_adamw_ema_dev_grouped: bad argument (n %% 4 == 0)");
   VTP_REQUIRE(group4 && group_tab && ngroups >= 1 && ngroups <= 256, "vtp_adamw_ema_dev_grouped: bad group table (1 <= ngroups <= 256)");
   VTP_REQUIRE(n / 4096 < 0x7fffffffL, "vtp_adamw_ema_dev_grouped: range too long for one launch");
-  hipLaunchKernelGGL(adamw_ema_grouped_kernel, dim3((unsigned)((n / 4 + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+  hipLaunchKernelGGL(adamw_ema_kernel<true>, dim3((unsigned)((n / 4 + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
                      teacher, n / 4, hyper, (const uint8_t*)group4, (const float2*)group_tab, ngroups);
   return check_launch("adamw_ema_dev_grouped");
 }
