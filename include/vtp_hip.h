@@ -298,6 +298,29 @@ int vtp_sumsq_partials_count(long n);
 int vtp_sumsq_partials(const float* g, long n, double* partials, void* stream);
 int vtp_sum_partials(const double* partials, int count, double* sum, void* stream);
 int vtp_grad_clip_finalize(const double* partials, int count, float* hyper, float* total_norm, float* coef, void* stream);
+/* Skipping the optimizer step on a non-finite gradient norm (VTPTrainer(skip_nonfinite=True)), decided on the device: no host sync,
+ * and a captured hipGraph replays the decision of each step.
+ * state: DEVICE int32 [4], owned by the caller: state[0] = applied_steps (Adam's step count), state[1] = skipped_steps,
+ *   state[2] = skip_now (1 when the step in flight is skipped, else 0), state[3] unused.
+ * vtp_grad_clip_finalize_guarded: vtp_grad_clip_finalize (same *total_norm and *coef, bit for bit, the inf or NaN included), then
+ *   skip = !isfinite(*total_norm) -- the reported f32 norm: a finite sum whose scaled root overflows f32 skips as well.  Skipped:
+ *   hyper[7] keeps its value, skipped_steps += 1, skip_now = 1.  Applied: hyper[7] = gs * coef, applied_steps += 1, skip_now = 0.
+ *   Either way it writes this step's bias corrections from the device counter, hyper[5] = (float)(1 - beta1^t) and hyper[6] =
+ *   (float)sqrt(1 - beta2^t) with t = applied_steps after the increment (applied_steps + 1 on a skipped step, where nothing reads
+ *   them), in fp64 with the power formed by squaring and multiplying.  betas: HOST double [2] = {beta1, beta2}, each in [0, 1), read
+ *   during the call (they become launch arguments).
+ * vtp_adamw_dev_guarded / vtp_adamw_ema_dev_guarded / vtp_ema_dev_guarded: the AdamW, AdamW + EMA and EMA launches above with
+ *   skip = &state[2] (any DEVICE int32; must not be NULL): a non-zero *skip makes every workgroup return before its first store, so
+ *   p, m, v, p_bf16 and teacher keep their bits (-0.0 and NaN payloads included); *skip == 0 gives the unguarded entry point's bits.
+ *   group_tab == NULL: idx4 is nodecay4 of vtp_adamw_dev_masked / vtp_adamw_ema_dev (may be NULL) and ngroups is ignored;
+ *   otherwise idx4 is group4 of the _grouped entry points (must not be NULL) and 1 <= ngroups <= 256. */
+int vtp_grad_clip_finalize_guarded(const double* partials, int count, float* hyper, float* total_norm, float* coef, int* state,
+                                   const double* betas, void* stream);
+int vtp_adamw_dev_guarded(float* p, const float* g, float* m, float* v, void* p_bf16, const void* idx4, const float* group_tab,
+                          int ngroups, long n, const float* hyper, const int* skip, void* stream);
+int vtp_adamw_ema_dev_guarded(float* p, const float* g, float* m, float* v, float* teacher, const void* idx4, const float* group_tab,
+                              int ngroups, long n, const float* hyper, const int* skip, void* stream);
+int vtp_ema_dev_guarded(float* t, const float* s, long n, const float* momentum, const int* skip, void* stream);
 
 /* ---- CLIP text-tower glue + contrastive head (fp32; clip.hip) -------------------------------------------------
  * embed: x f32 [B*T, D] = table[ids] + pos (modeling_vtp.py:296-297); eot[b] = argmax_t ids[b,t] (text_global_pool

@@ -94,6 +94,10 @@ SIGNATURES = {
     "vtp_sumsq_partials": [_P, _L, _P, _P],
     "vtp_sum_partials": [_P, _I, _P, _P],
     "vtp_grad_clip_finalize": [_P, _I, _P, _P, _P, _P],
+    "vtp_grad_clip_finalize_guarded": [_P, _I, _P, _P, _P, _P, _P, _P],
+    "vtp_adamw_dev_guarded": [_P, _P, _P, _P, _P, _P, _P, _I, _L, _P, _P, _P],
+    "vtp_adamw_ema_dev_guarded": [_P, _P, _P, _P, _P, _P, _P, _I, _L, _P, _P, _P],
+    "vtp_ema_dev_guarded": [_P, _P, _L, _P, _P, _P],
     "vtp_embed_tokens": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "vtp_embed_tokens_bwd": [_P, _P, _P, _P, _I, _I, _I, _P],
     "vtp_gather_rows": [_P, _P, _P, _I, _I, _I, _P],

@@ -466,8 +466,10 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
                                                     bf16* __restrict__ pb, long n, float lr, float b1, float b2, float eps,
                                                     float wd, float bc1, float bc2_sqrt, float gs,
                                                     const float* __restrict__ hyper, const uint8_t* __restrict__ idx4,
-                                                    const float2* __restrict__ group_tab, int ngroups) {
+                                                    const float2* __restrict__ group_tab, int ngroups,
+                                                    const int* __restrict__ skip) {
   __shared__ float2 tab[TABLE ? 256 : 1];
+  if (skip && *skip) return;  // a skipped step stores nothing (workgroup-uniform, in front of the barrier below)
   if (TABLE || hyper) {  // device-resident hyper-parameters: a captured hipGraph replays with fresh values every step
     lr = hyper[0]; b1 = hyper[1]; b2 = hyper[2]; eps = hyper[3]; wd = hyper[4]; bc1 = hyper[5]; bc2_sqrt = hyper[6]; gs = hyper[7];
   }
@@ -514,7 +516,8 @@ __global__ __launch_bounds__(256) void reduce_slabs_kernel(const float* __restri
 }
 
 __global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ t, const float* __restrict__ s, long n, float mom,
-                                                  const float* __restrict__ mom_ptr) {
+                                                  const float* __restrict__ mom_ptr, const int* __restrict__ skip) {
+  if (skip && *skip) return;
   if (mom_ptr) mom = mom_ptr[0];  // device-resident momentum: graph replays follow the teacher-momentum schedule
   const long n4 = n / 4;
   for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256L) {
@@ -534,8 +537,10 @@ template <bool TABLE>
 __global__ __launch_bounds__(256) void adamw_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                         float* __restrict__ v, float* __restrict__ t, long n4,
                                                         const float* __restrict__ hyper, const uint8_t* __restrict__ idx4,
-                                                        const float2* __restrict__ group_tab, int ngroups) {
+                                                        const float2* __restrict__ group_tab, int ngroups,
+                                                        const int* __restrict__ skip) {
   __shared__ float2 tab[TABLE ? 256 : 1];
+  if (skip && *skip) return;  // as in adamw_kernel
   const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4], bc1 = hyper[5], bc2_sqrt = hyper[6], gs = hyper[7];
   const float mom = hyper[9];
   const long base = blockIdx.x * 1024L + threadIdx.x;
@@ -863,7 +868,7 @@ extern "C" int vtp_adamw(float* p, const float* g, float* m, float* v, void* p_b
   const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
   hipLaunchKernelGGL(adamw_kernel<false>, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16*)p_bf16, n, lr,
                      beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale, (const float*)nullptr, (const uint8_t*)nullptr,
-                     (const float2*)nullptr, 0);
+                     (const float2*)nullptr, 0, (const int*)nullptr);
   return check_launch("adamw");
 }
 
@@ -871,7 +876,7 @@ extern "C" int vtp_adamw_dev(float* p, const float* g, float* m, float* v, void*
                              void* stream) {
   VTP_REQUIRE(p && g && m && v && hyper && n > 0 && n % 4 == 0, "vtp_adamw_dev: bad argument (n %% 4 == 0)");
   hipLaunchKernelGGL(adamw_kernel<false>, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16*)p_bf16, n, 0.f,
-                     0.f, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, hyper, (const uint8_t*)nullptr, (const float2*)nullptr, 0);
+                     0.f, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, hyper, (const uint8_t*)nullptr, (const float2*)nullptr, 0, (const int*)nullptr);
   return check_launch("adamw_dev");
 }
 
@@ -879,7 +884,7 @@ extern "C" int vtp_adamw_dev_masked(float* p, const float* g, float* m, float* v
                                     const float* hyper, void* stream) {
   VTP_REQUIRE(p && g && m && v && hyper && nodecay4 && n > 0 && n % 4 == 0, "vtp_adamw_dev_masked: bad argument (n %% 4 == 0)");
   hipLaunchKernelGGL(adamw_kernel<false>, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16*)p_bf16, n, 0.f,
-                     0.f, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, hyper, (const uint8_t*)nodecay4, (const float2*)nullptr, 0);
+                     0.f, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, hyper, (const uint8_t*)nodecay4, (const float2*)nullptr, 0, (const int*)nullptr);
   return check_launch("adamw_dev_masked");
 }
 
@@ -891,13 +896,15 @@ extern "C" int vtp_reduce_slabs(const float* slabs, long stride, int S, float* d
 
 extern "C" int vtp_ema(float* t, const float* s, long n, float momentum, void* stream) {
   VTP_REQUIRE(t && s && n > 0 && n % 4 == 0, "vtp_ema: bad argument (n %% 4 == 0)");
-  hipLaunchKernelGGL(ema_kernel, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, t, s, n, momentum, (const float*)nullptr);
+  hipLaunchKernelGGL(ema_kernel, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, t, s, n, momentum, (const float*)nullptr,
+                     (const int*)nullptr);
   return check_launch("ema");
 }
 
 extern "C" int vtp_ema_dev(float* t, const float* s, long n, const float* momentum, void* stream) {
   VTP_REQUIRE(t && s && momentum && n > 0 && n % 4 == 0, "vtp_ema_dev: bad argument (n %% 4 == 0)");
-  hipLaunchKernelGGL(ema_kernel, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, t, s, n, 0.f, momentum);
+  hipLaunchKernelGGL(ema_kernel, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, t, s, n, 0.f, momentum,
+                     (const int*)nullptr);
   return check_launch("ema_dev");
 }
 
@@ -906,7 +913,7 @@ extern "C" int vtp_adamw_ema_dev(float* p, const float* g, float* m, float* v, f
   VTP_REQUIRE(p && g && m && v && hyper && n > 0 && n % 4 == 0, "vtp_adamw_ema_dev: bad argument (n %% 4 == 0)");
   VTP_REQUIRE(n / 4096 < 0x7fffffffL, "vtp_adamw_ema_dev: range too long for one launch");
   hipLaunchKernelGGL(adamw_ema_kernel<false>, dim3((unsigned)((n / 4 + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
-                     teacher, n / 4, hyper, (const uint8_t*)nodecay4, (const float2*)nullptr, 0);
+                     teacher, n / 4, hyper, (const uint8_t*)nodecay4, (const float2*)nullptr, 0, (const int*)nullptr);
   return check_launch("adamw_ema_dev");
 }
 
@@ -915,7 +922,7 @@ extern "C" int vtp_adamw_dev_grouped(float* p, const float* g, float* m, float* 
   VTP_REQUIRE(p && g && m && v && hyper && n > 0 && n % 4 == 0, "vtp_adamw_dev_grouped: bad argument (n %% 4 == 0)");
   VTP_REQUIRE(group4 && group_tab && ngroups >= 1 && ngroups <= 256, "vtp_adamw_dev_grouped: bad group table (1 <= ngroups <= 256)");
   hipLaunchKernelGGL(adamw_kernel<true>, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16*)p_bf16, n, 0.f,
-                     0.f, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, hyper, (const uint8_t*)group4, (const float2*)group_tab, ngroups);
+                     0.f, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, hyper, (const uint8_t*)group4, (const float2*)group_tab, ngroups, (const int*)nullptr);
   return check_launch("adamw_dev_grouped");
 }
 
@@ -925,6 +932,46 @@ extern "C" int vtp_adamw_ema_dev_grouped(float* p, const float* g, float* m, flo
   VTP_REQUIRE(group4 && group_tab && ngroups >= 1 && ngroups <= 256, "vtp_adamw_ema_dev_grouped: bad group table (1 <= ngroups <= 256)");
   VTP_REQUIRE(n / 4096 < 0x7fffffffL, "vtp_adamw_ema_dev_grouped: range too long for one launch");
   hipLaunchKernelGGL(adamw_ema_kernel<true>, dim3((unsigned)((n / 4 + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
-                     teacher, n / 4, hyper, (const uint8_t*)group4, (const float2*)group_tab, ngroups);
+                     teacher, n / 4, hyper, (const uint8_t*)group4, (const float2*)group_tab, ngroups, (const int*)nullptr);
   return check_launch("adamw_ema_dev_grouped");
+}
+
+// ---- the guarded forms (VTPTrainer(skip_nonfinite=True)): *skip != 0 (device int32, skip_now of vtp_grad_clip_finalize_guarded) makes
+// every workgroup return before its first store; *skip == 0 runs the launch of the unguarded entry point.  One entry point per kernel:
+// group_tab == NULL is the flag form (idx4 = nodecay4, may be NULL), otherwise idx4 = group4 indexes the table.
+extern "C" int vtp_adamw_dev_guarded(float* p, const float* g, float* m, float* v, void* p_bf16, const void* idx4,
+                                     const float* group_tab, int ngroups, long n, const float* hyper, const int* skip, void* stream) {
+  VTP_REQUIRE(p && g && m && v && hyper && skip && n > 0 && n % 4 == 0, "vtp_adamw_dev_guarded: bad argument (n %% 4 == 0)");
+  if (group_tab) {
+    VTP_REQUIRE(idx4 && ngroups >= 1 && ngroups <= 256, "vtp_adamw_dev_guarded: bad group table (1 <= ngroups <= 256)");
+    hipLaunchKernelGGL(adamw_kernel<true>, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16*)p_bf16, n, 0.f,
+                       0.f, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, hyper, (const uint8_t*)idx4, (const float2*)group_tab, ngroups, skip);
+  } else {
+    hipLaunchKernelGGL(adamw_kernel<false>, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16*)p_bf16, n, 0.f,
+                       0.f, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, hyper, (const uint8_t*)idx4, (const float2*)nullptr, 0, skip);
+  }
+  return check_launch("adamw_dev_guarded");
+}
+
+extern "C" int vtp_adamw_ema_dev_guarded(float* p, const float* g, float* m, float* v, float* teacher, const void* idx4,
+                                         const float* group_tab, int ngroups, long n, const float* hyper, const int* skip,
+                                         void* stream) {
+  VTP_REQUIRE(p && g && m && v && hyper && skip && n > 0 && n % 4 == 0, "vtp_adamw_ema_dev_guarded: bad argument (n %% 4 == 0)");
+  VTP_REQUIRE(n / 4096 < 0x7fffffffL, "vtp_adamw_ema_dev_guarded: range too long for one launch");
+  const dim3 grid((unsigned)((n / 4 + 1023) / 1024));
+  if (group_tab) {
+    VTP_REQUIRE(idx4 && ngroups >= 1 && ngroups <= 256, "vtp_adamw_ema_dev_guarded: bad group table (1 <= ngroups <= 256)");
+    hipLaunchKernelGGL(adamw_ema_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, p, g, m, v, teacher, n / 4, hyper,
+                       (const uint8_t*)idx4, (const float2*)group_tab, ngroups, skip);
+  } else {
+    hipLaunchKernelGGL(adamw_ema_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, p, g, m, v, teacher, n / 4, hyper,
+                       (const uint8_t*)idx4, (const float2*)nullptr, 0, skip);
+  }
+  return check_launch("adamw_ema_dev_guarded");
+}
+
+extern "C" int vtp_ema_dev_guarded(float* t, const float* s, long n, const float* momentum, const int* skip, void* stream) {
+  VTP_REQUIRE(t && s && momentum && skip && n > 0 && n % 4 == 0, "vtp_ema_dev_guarded: bad argument (n %% 4 == 0)");
+  hipLaunchKernelGGL(ema_kernel, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, t, s, n, 0.f, momentum, skip);
+  return check_launch("ema_dev_guarded");
 }

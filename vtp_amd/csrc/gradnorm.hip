@@ -38,12 +38,27 @@ __global__ __launch_bounds__(GN_THREADS) void sumsq_partials_kernel(const float*
   if (threadIdx.x == 0) partials[blockIdx.x] = (ws[0] + ws[1]) + (ws[2] + ws[3]);
 }
 
+// b^t by plain fp64 multiplications (square and multiply): exact wherever the power is representable
+__device__ __forceinline__ double pow_by_squaring(double b, int t) {
+  double r = 1.0;
+  for (; t > 0; t >>= 1, b *= b)
+    if (t & 1) r *= b;
+  return r;
+}
+
 // One workgroup: sum = partials[0, count) added in a fixed order (thread t: t, t + 1024, ... in sequence; then an LDS tree).
 // hyper == nullptr: *sum_out = sum.  Otherwise the clip_grad_norm_ tail, with gs = hyper[7] (the gradient multiplier AdamW applies)
 // and max_norm = hyper[10]:  total_norm = gs * sqrt(sum);  coef = clamp(max_norm / (total_norm + 1e-6), max=1);  hyper[7] = gs * coef.
+// state != nullptr (VTPTrainer(skip_nonfinite=True)): the guarded tail.  state = int32 {applied_steps, skipped_steps, skip_now, pad}.
+// skip = !isfinite(total_norm), tested on the REPORTED f32 norm (a finite fp64 sum whose scaled root overflows f32 skips too; a NaN
+// or inf gradient element reaches the sum through the fp64 fma chain of sumsq_partials_kernel, and squares cannot cancel).  A skipped
+// step leaves hyper[7] alone and counts in skipped_steps; an applied one folds coef in and counts in applied_steps.  Adam's step count
+// is the DEVICE counter: hyper[5] = 1 - b1^t and hyper[6] = sqrt(1 - b2^t) with t = applied_steps after the increment (applied_steps
+// + 1 on a skipped step: unused), in fp64 with the power by squaring (exact wherever b^t is representable).  One thread, plain stores.
 __global__ __launch_bounds__(GN_FIN_THREADS) void sum_partials_kernel(const double* __restrict__ partials, int count,
                                                                       double* __restrict__ sum_out, float* __restrict__ hyper,
-                                                                      float* __restrict__ norm_out, float* __restrict__ coef_out) {
+                                                                      float* __restrict__ norm_out, float* __restrict__ coef_out,
+                                                                      int* __restrict__ state, double b1, double b2) {
   __shared__ double sh[GN_FIN_THREADS];
   const int t = threadIdx.x;
   double s = 0.0;
@@ -76,7 +91,22 @@ __global__ __launch_bounds__(GN_FIN_THREADS) void sum_partials_kernel(const doub
   const float coef = c > 1.f ? 1.f : c;  // torch.clamp(max=1): NaN stays NaN (fminf(NaN, 1) would return 1)
   norm_out[0] = total;
   coef_out[0] = coef;
-  hyper[7] = gs * coef;
+  if (!state) {
+    hyper[7] = gs * coef;
+    return;
+  }
+  const bool skip = (__float_as_uint(total) & 0x7f800000u) == 0x7f800000u;  // inf or NaN
+  int applied = state[0];
+  if (skip) {
+    state[1] += 1;
+  } else {
+    hyper[7] = gs * coef;
+    state[0] = ++applied;
+  }
+  state[2] = skip ? 1 : 0;
+  const int adam_t = skip ? applied + 1 : applied;
+  hyper[5] = (float)(1.0 - pow_by_squaring(b1, adam_t));
+  hyper[6] = (float)sqrt(1.0 - pow_by_squaring(b2, adam_t));
 }
 
 }  // namespace vtp
@@ -95,13 +125,24 @@ extern "C" int vtp_sumsq_partials(const float* g, long n, double* partials, void
 extern "C" int vtp_sum_partials(const double* partials, int count, double* sum, void* stream) {
   VTP_REQUIRE(partials && sum && count >= 1, "vtp_sum_partials: bad argument (count >= 1)");
   hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(GN_FIN_THREADS), 0, (hipStream_t)stream, partials, count, sum,
-                     (float*)nullptr, (float*)nullptr, (float*)nullptr);
+                     (float*)nullptr, (float*)nullptr, (float*)nullptr, (int*)nullptr, 0.0, 0.0);
   return check_launch("sum_partials");
 }
 
 extern "C" int vtp_grad_clip_finalize(const double* partials, int count, float* hyper, float* total_norm, float* coef, void* stream) {
   VTP_REQUIRE(partials && hyper && total_norm && coef && count >= 1, "vtp_grad_clip_finalize: bad argument (count >= 1)");
   hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(GN_FIN_THREADS), 0, (hipStream_t)stream, partials, count, (double*)nullptr,
-                     hyper, total_norm, coef);
+                     hyper, total_norm, coef, (int*)nullptr, 0.0, 0.0);
   return check_launch("grad_clip_finalize");
+}
+
+extern "C" int vtp_grad_clip_finalize_guarded(const double* partials, int count, float* hyper, float* total_norm, float* coef,
+                                              int* state, const double* betas, void* stream) {
+  VTP_REQUIRE(partials && hyper && total_norm && coef && state && betas && count >= 1,
+              "vtp_grad_clip_finalize_guarded: bad argument (count >= 1)");
+  const double b1 = betas[0], b2 = betas[1];  // HOST memory: read here, passed as launch arguments
+  VTP_REQUIRE(b1 >= 0.0 && b1 < 1.0 && b2 >= 0.0 && b2 < 1.0, "vtp_grad_clip_finalize_guarded: betas must lie in [0, 1)");
+  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(GN_FIN_THREADS), 0, (hipStream_t)stream, partials, count, (double*)nullptr,
+                     hyper, total_norm, coef, state, b1, b2);
+  return check_launch("grad_clip_finalize_guarded");
 }

@@ -542,6 +542,34 @@ def grad_clip_finalize(partials, count, hyper, total_norm, coef):
     _lib.check(_lib_().vtp_grad_clip_finalize(_p(partials), count, _p(hyper), _p(total_norm), _p(coef), _s()), "vtp_grad_clip_finalize")
 
 
+# ---- skipping a step whose gradient norm is not finite (VTPTrainer(skip_nonfinite=True)) -----------------------------------------
+def grad_clip_finalize_guarded(partials, count, hyper, total_norm, coef, state, betas):
+    """grad_clip_finalize, then the decision on the device.  state: device int32 [4] {applied_steps, skipped_steps, skip_now, -}: a
+    non-finite total_norm leaves hyper[7] alone and counts as skipped; hyper[5:7] get the bias corrections of Adam step
+    t = applied_steps (after the increment).  betas: (beta1, beta2), host numbers"""
+    import ctypes
+    b = (ctypes.c_double * 2)(float(betas[0]), float(betas[1]))
+    _lib.check(_lib_().vtp_grad_clip_finalize_guarded(_p(partials), count, _p(hyper), _p(total_norm), _p(coef), _p(state), b, _s()),
+               "vtp_grad_clip_finalize_guarded")
+
+
+def adamw_dev_guarded(p, g, m, v, p_bf16, n, hyper, skip, idx4=None, group_tab=None, ngroups=0):
+    """adamw_dev (group_tab None; idx4 = nodecay4 or None) or adamw_dev_grouped (idx4 = group4) that stores nothing when the device
+    int32 skip[0] is not zero"""
+    _lib.check(_lib_().vtp_adamw_dev_guarded(_p(p), _p(g), _p(m), _p(v), _p(p_bf16), _p(idx4), _p(group_tab), ngroups, n, _p(hyper),
+                                             _p(skip), _s()), "vtp_adamw_dev_guarded")
+
+
+def adamw_ema_dev_guarded(p, g, m, v, teacher, n, hyper, skip, idx4=None, group_tab=None, ngroups=0):
+    """adamw_ema_dev / adamw_ema_dev_grouped that store nothing when skip[0] is not zero (see adamw_dev_guarded)"""
+    _lib.check(_lib_().vtp_adamw_ema_dev_guarded(_p(p), _p(g), _p(m), _p(v), _p(teacher), _p(idx4), _p(group_tab), ngroups, n,
+                                                 _p(hyper), _p(skip), _s()), "vtp_adamw_ema_dev_guarded")
+
+
+def ema_dev_guarded(t, s, n, momentum_dev, skip):
+    _lib.check(_lib_().vtp_ema_dev_guarded(_p(t), _p(s), n, _p(momentum_dev), _p(skip), _s()), "vtp_ema_dev_guarded")
+
+
 # ---- LPIPS (vtp_amd/csrc/lpips.hip, conv mode of gemm.hip) ---------------------------------------------------------------
 def _f3(v):
     import ctypes

@@ -263,6 +263,16 @@ def _max_norm_value(value) -> float:
     return f
 
 
+def _skip_nonfinite_value(value, max_grad_norm) -> bool:
+    """VTPTrainer(skip_nonfinite=...): a bool; True needs the clipping machinery (the norm is known before any bucket is updated)"""
+    if not isinstance(value, bool):
+        raise ValueError(f"skip_nonfinite must be True or False, got {value!r}")
+    if value and max_grad_norm is None:
+        raise ValueError("skip_nonfinite=True needs max_grad_norm to be a number: the decision is taken on the global gradient norm "
+                         "(max_grad_norm=float('inf') measures it without clipping)")
+    return value
+
+
 MAX_PARAM_GROUPS = 128  # one table row per (group, decay-exempt) pair, 256 rows at most (csrc/elementwise.hip)
 
 
@@ -387,14 +397,20 @@ class VTPTrainer:
                  clip_drop_rate: Optional[float] = None, ssl_drop_rate: Optional[float] = None, rec_drop_rate: Optional[float] = None,
                  drop_seed: int = 0, centering: str = "softmax", koleo_weight: float = 0.0, sk_iterations: int = 3,
                  shard_optimizer: Optional[bool] = None, grad_dtype: str = "fp32", no_decay="default",
-                 force_collectives: bool = False, max_grad_norm: Optional[float] = None, param_groups=None):
+                 force_collectives: bool = False, max_grad_norm: Optional[float] = None, param_groups=None,
+                 skip_nonfinite: bool = False):
         """lpips: a vtp_amd.LPIPS module (frozen, weights loaded by the caller) -- with perceptual_weight > 0 the
         reconstruction objective is rec_weight * L1 + perceptual_weight * mean_b LPIPS(decoded_b, image_b).
         max_grad_norm: global gradient-norm clipping in front of AdamW (torch.nn.utils.clip_grad_norm_, norm_type 2); the step's
         pre-clip norm and coefficient land in self.grad_norm / self.grad_clip_coef (device tensors).  None: no clipping.
         param_groups: per-group learning-rate / weight-decay scales (resolve_param_groups; layerwise_lr_decay builds DINOv2's list):
         group g runs AdamW with lr * lr_scale and weight_decay * wd_scale.  self.param_groups lists them; its scales are read at
-        every step() (a scheduler may mutate them; no re-capture).  None: one lr / weight decay for every parameter."""
+        every step() (a scheduler may mutate them; no re-capture).  None: one lr / weight decay for every parameter.
+        skip_nonfinite: a step whose global gradient norm is inf or NaN runs to completion but updates nothing (parameters, moments,
+        bf16 copies, EMA teacher and Adam's step count keep their values); decided on the device, no host sync.  Needs max_grad_norm
+        (float("inf"): no clipping).  self.step_skipped / self.skipped_steps (device int32 [1]) report the last step / the total.
+        With it on, self.betas must keep the constructor's values (step() raises otherwise)."""
+        self._skip = _skip_nonfinite_value(skip_nonfinite, max_grad_norm)
         self.model = model
         # stochastic depth (block.py:207-289): the student trunk's rate per objective (clip_drop_rate / ssl_drop_rate / rec_drop_rate,
         # vtp.py:205-207; `drop_rate` sets all three) and the pixel decoder's drop_path_rate.  The objectives are items of ONE list
@@ -422,6 +438,7 @@ class VTPTrainer:
         if self.decoder is None:
             raise RuntimeError("VTPTrainer needs train_reconstruction=True")
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
+        self._skip_betas = (float(betas[0]), float(betas[1]))  # the guarded finalize bakes them into its launch: fixed at construction
         self.clip_weight, self.rec_weight = clip_weight, rec_weight
         self.dino_weight, self.ibot_weight = dino_weight, ibot_weight
         self.student_temp, self.teacher_temp = student_temp, teacher_temp
@@ -531,6 +548,18 @@ class VTPTrainer:
             cap = ops.sumsq_partials_count(st.numel) + len(st.offsets)
             self._clip_partials = torch.zeros(cap, dtype=torch.float64, device=st.device)
             self._clip_sum = torch.zeros(1, dtype=torch.float64, device=st.device)  # sharded optimizer: this rank's sum, all-reduced
+        # SKIPPING A STEP WHOSE GRADIENT NORM IS NOT FINITE (skip_nonfinite): the clip finalize decides on the device (the step is a
+        # replayed hipGraph: the host cannot look at the norm without a sync) and every update kernel of the step reads the decision,
+        # skip_now, and stores nothing when it is set.  Adam's step count lives in the same device block -- a skipped step must not
+        # advance it, and the host does not know which steps were skipped: the finalize overwrites the host-computed bias
+        # corrections hyper[5:7] (_set_hyper) from it, in front of the step's first AdamW launch.  self.step_no stays the number of
+        # ATTEMPTED steps.  Out of scope: the SSL centres follow the teacher's outputs, which do not depend on this step's gradients,
+        # and the loss accumulators of a bad step read NaN -- the signal a user wants.
+        self._skip_state = self.step_skipped = self.skipped_steps = None
+        if self._skip:
+            self._skip_state = torch.zeros(4, dtype=torch.int32, device=st.device)  # {applied_steps, skipped_steps, skip_now, -}
+            self.skipped_steps = self._skip_state[1:2]  # steps skipped since construction / load_state_dict
+            self.step_skipped = self._skip_state[2:3]   # 1 after a skipped step, else 0
         self._hyper_ring = None
         self.use_graphs = use_graphs
         self._graphs = {}
@@ -563,6 +592,11 @@ class VTPTrainer:
                              "max_grad_norm=None or with a number")
         self._max_grad_norm = None if value is None else _max_norm_value(value)
 
+    @property
+    def skip_nonfinite(self) -> bool:
+        """decided at construction, like clipping: the guard is part of the captured step"""
+        return self._skip
+
     def sync_replicas(self):
         """Data-parallel replicas must start from identical state (what DDP's constructor does with its parameter / buffer
         broadcast): rank 0's fp32 masters (student AND EMA teacher), Adam moments and SSL centres go to every rank."""
@@ -570,6 +604,8 @@ class VTPTrainer:
             return
         dist, st = self.bucketer.dist, self.store
         bufs = [st.flat_p, self.m, self.v]
+        if self._skip:
+            bufs.append(self._skip_state)
         if self.ssl_head is not None:
             bufs += [self.center_dino, self.center_ibot]
         for b in bufs:
@@ -864,12 +900,19 @@ class VTPTrainer:
         tab = self.group_tab
         for a, b, tl in pieces:
             teacher = None if tl is None else st.flat_p[tl:tl + b - a]
-            if tab is not None:
+            if self._skip:
+                idx4 = self._group4 if tab is not None else self.nodecay4
+                ops.adamw_ema_dev_guarded(st.flat_p[a:b], st.flat_g[a:b], self.m[a:b], self.v[a:b], teacher, b - a, self.hyper,
+                                          self.step_skipped, None if idx4 is None else idx4[a // 4:b // 4], tab,
+                                          0 if tab is None else tab.shape[0])
+            elif tab is not None:
                 ops.adamw_ema_dev_grouped(st.flat_p[a:b], st.flat_g[a:b], self.m[a:b], self.v[a:b], teacher, b - a, self.hyper,
                                           self._group4[a // 4:b // 4], tab, tab.shape[0])
             else:
                 ops.adamw_ema_dev(st.flat_p[a:b], st.flat_g[a:b], self.m[a:b], self.v[a:b], teacher,
                                   b - a, self.hyper, None if self.nodecay4 is None else self.nodecay4[a // 4:b // 4])
+        # (skip_nonfinite: the refresh of the bf16 copies and the weight-norm hooks below need no guard -- on a skipped step they
+        # re-derive the same bits from unchanged parameters)
         st.prep_runs(runs)
         # derived weights that depend only on what this bucket updated (the DINO heads' weight-normed last layers, student and -- through
         # the fused EMA -- teacher): re-derived here, beside the backward, not in the serial tail
@@ -883,7 +926,11 @@ class VTPTrainer:
     def _adamw(self, lo, hi, g):
         """AdamW over flat elements [lo, hi) (4-element aligned) with the gradient g: grouped when param_groups were given"""
         st, tab = self.store, self.group_tab
-        if tab is not None:
+        if self._skip:
+            idx4 = self._group4 if tab is not None else self.nodecay4
+            ops.adamw_dev_guarded(st.flat_p[lo:hi], g, self.m[lo:hi], self.v[lo:hi], None, hi - lo, self.hyper, self.step_skipped,
+                                  None if idx4 is None else idx4[lo // 4:hi // 4], tab, 0 if tab is None else tab.shape[0])
+        elif tab is not None:
             ops.adamw_dev_grouped(st.flat_p[lo:hi], g, self.m[lo:hi], self.v[lo:hi], None, hi - lo, self.hyper,
                                   self._group4[lo // 4:hi // 4], tab, tab.shape[0])
         else:
@@ -937,10 +984,23 @@ class VTPTrainer:
             ops.sumsq_partials(g, n, self._clip_partials[base:])
 
     def _clip_finalize(self, partials=None, count=None):
-        """grad_norm, grad_clip_coef and the clipped gradient multiplier hyper[7] from this step's partials"""
+        """grad_norm, grad_clip_coef and the clipped gradient multiplier hyper[7] from this step's partials; with skip_nonfinite
+        also the step's decision, the counters and the bias corrections hyper[5:7] of the device step count.  Ranks decide alike: in
+        all-reduce mode each holds the same reduced gradient, in sharded mode the all-reduced sum feeds the finalize."""
         if partials is None:
             partials, count = self._clip_partials, self._clip_cursor
-        ops.grad_clip_finalize(partials, count, self.hyper, self.grad_norm, self.grad_clip_coef)
+        if self._skip:
+            ops.grad_clip_finalize_guarded(partials, count, self.hyper, self.grad_norm, self.grad_clip_coef, self._skip_state,
+                                           self._skip_betas)
+        else:
+            ops.grad_clip_finalize(partials, count, self.hyper, self.grad_norm, self.grad_clip_coef)
+
+    def _ema(self, t, s, n):
+        """EMA teacher update of one range (guarded with skip_nonfinite)"""
+        if self._skip:
+            ops.ema_dev_guarded(t, s, n, self.momentum_dev, self.step_skipped)
+        else:
+            ops.ema_dev(t, s, n, self.momentum_dev)
 
     def _clip_shards(self, recs):
         """sharded optimizer: partials over this rank's fp32 chunks, their sum all-reduced over the group (a collective event of the
@@ -1179,6 +1239,7 @@ class VTPTrainer:
                         rec.g32.copy_(rec.g_out)
                     self._adamw(rec.a, rec.b, rec.g32)
                     rec.p_send[:n].copy_(st.flat_p[rec.a:rec.b])
+            # (skip_nonfinite: the all-gather needs no guard -- every rank took the same decision, a skipped step gathers unchanged chunks)
             yield lambda: self.bucketer.all_gather_params(st.flat_p, recs)
             for rec in recs:
                 st.flat_p[rec.lo:rec.hi].copy_(rec.p_recv[:rec.hi - rec.lo])
@@ -1203,6 +1264,8 @@ class VTPTrainer:
                 self._clip_finalize()
             for lo, hi in ranges:
                 self._adamw(lo, hi, st.flat_g[lo:hi])
+        # skip_nonfinite: what follows the updates needs no guard.  The clamp, the bf16 refresh and the weight-norm hooks are
+        # idempotent on unchanged parameters (logit_scale was clamped by the previous applied step, or starts below the bound).
         if text is not None:
             st.p("logit_scale").clamp_(max=math.log(100.0))  # OpenCLIP training-loop convention
         if self.overlap_opt:  # EMA and the weight refresh rode along bucket by bucket
@@ -1216,7 +1279,7 @@ class VTPTrainer:
                     (tlo, thi), (slo, shi) = _range(st, t_pref), _range(st, s_pref)
                     for a, b in uncovered(slo, shi, done):
                         ta = tlo + (a - slo)
-                        ops.ema_dev(st.flat_p[ta:ta + b - a], st.flat_p[a:b], b - a, self.momentum_dev)
+                        self._ema(st.flat_p[ta:ta + b - a], st.flat_p[a:b], b - a)
                         st.prep_runs(st.desc_runs([(ta, ta + b - a)]))
             st.mark_prepped(self._hooks_done)
             return
@@ -1224,7 +1287,7 @@ class VTPTrainer:
             from .vtp import _range
             for t_pref, s_pref in self.model.ema_pairs():  # trunk, proj (legacy teacher_proj, vtp.py:396-398), dino_head
                 (tlo, thi), (slo, shi) = _range(st, t_pref), _range(st, s_pref)
-                ops.ema_dev(st.flat_p[tlo:thi], st.flat_p[slo:shi], thi - tlo, self.momentum_dev)
+                self._ema(st.flat_p[tlo:thi], st.flat_p[slo:shi], thi - tlo)
         st.prep()
 
     # feature exchange: RCCL all-gather / reduce-scatter; on backends without them (gloo, used by the single-GPU
@@ -1309,6 +1372,9 @@ class VTPTrainer:
 
     def _set_hyper(self):
         tab = None if self.param_groups is None else group_table(self.param_groups)  # (a bad scale raises before anything moves)
+        if self._skip and (float(self.betas[0]), float(self.betas[1])) != self._skip_betas:
+            raise ValueError(f"betas cannot change with skip_nonfinite=True: the bias corrections are formed on the device from the "
+                             f"betas of the constructor {self._skip_betas}, got {tuple(self.betas)!r}")
         self.step_no += 1
         b1, b2 = self.betas
         vals = [self.lr, b1, b2, self.eps, self.wd, 1.0 - b1 ** self.step_no, (1.0 - b2 ** self.step_no) ** 0.5,
@@ -1425,6 +1491,9 @@ class VTPTrainer:
         (`if rank == 0: trainer.state_dict()` would hang); save from rank 0 afterwards."""
         st = self.store
         sd = {"step": self.step_no, "exp_avg": {}, "exp_avg_sq": {}}
+        if self._skip:  # Adam's step count is the device counter (a sync, at checkpoint time); step_no counts attempted steps
+            applied, skipped = self._skip_state[:2].tolist()
+            sd["step"], sd["skipped_steps"] = int(applied), int(skipped)
         m, v = self._gather_moments()
         for name, (o, k) in st.offsets.items():
             sd["exp_avg"][name] = m[o:o + k].detach().clone().view(st.params[name].shape).cpu()
@@ -1454,6 +1523,10 @@ class VTPTrainer:
                 for g, (ls, ws) in zip(self.param_groups, scales):
                     g["lr_scale"], g["wd_scale"] = ls, ws
         self.step_no = int(sd["step"])
+        if self._skip:  # a checkpoint written without the guard: every step was applied
+            skipped = int(sd.get("skipped_steps", 0))
+            self._skip_state.copy_(torch.tensor([self.step_no, skipped, 0, 0], dtype=torch.int32))
+            self.step_no += skipped
         for name, (o, k) in st.offsets.items():
             self.m[o:o + k].copy_(sd["exp_avg"][name].reshape(-1))
             self.v[o:o + k].copy_(sd["exp_avg_sq"][name].reshape(-1))
@@ -1498,6 +1571,7 @@ class VTPTrainer:
                 static_ssl["global"], static_ssl["local"] = ssl["global"].clone(), ssl["local"].clone()
             snap = (st.flat_p.clone(), self.m.clone(), self.v.clone())
             hyper0 = self.hyper.clone() if self._clip else None  # the clip finalize rewrites hyper[7]
+            skip0 = self._skip_state.clone() if self._skip else None  # ... and, guarded, counts the warm-up as a step
             if ssl is not None:
                 snap = snap + (self.center_dino.clone(), self.center_ibot.clone())
             # warm-up in eager mode on a side stream (allocates every workspace buffer, sets kernel attributes); the
@@ -1515,6 +1589,8 @@ class VTPTrainer:
             self.v.copy_(snap[2])
             if hyper0 is not None:
                 self.hyper.copy_(hyper0)
+            if skip0 is not None:
+                self._skip_state.copy_(skip0)
             if ssl is not None:
                 self.center_dino.copy_(snap[3])
                 self.center_ibot.copy_(snap[4])
