@@ -66,7 +66,8 @@ int vtp_gemm_tn(const void* A, int lda, const void* B, int ldb, void* C, int ldc
  * reduce over the same K token rows (nn.Linear backward dW = dY^T X of attn.qkv / attn.proj / mlp.w1|w2 / mlp.w3, block.py:290-296),
  * (sum of 256 x 256 tiles) x splits workgroups; the K slices of a tile are combined inside the launch by the last-arriving
  * workgroup, which applies the epilogue (accumulate or overwrite, SwiGLU row de-interleave c_grp = -1, bias-gradient column sums).
- * probs: device array of nprob records of 16 int64 {A, B, C, colsum | lda, ldb, ldc | M, N | c_grp, c_pre | tile0 | accumulate | 0 0 0};
+ * probs: device array of nprob records of 16 int64 {A, B, C, colsum | lda, ldb, ldc | M, N | c_grp, c_pre | tile0 | accumulate | K 0 0}
+ * (K: the problem's own token count in an item-list launch, 0 = the launch's K; the uniform-grid launch takes one K for all);
  * part: ntiles * splits_eff * 65536 floats, ticket: ntiles ints, zero before the first launch (the kernel leaves them zero). */
 int vtp_gemm_tn_grouped(const void* probs, int nprob, int ntiles, int K, int splits, void* part, void* ticket, void* stream);
 /* the same launch on the one-wave-per-SIMD kernel with the hand-scheduled k loop (K % 8 == 0; bit-identical results per K slice), from an
@@ -126,6 +127,15 @@ int vtp_gather_image_rows(const float* src, const int* img_idx, float* dst, void
                           void* stream);
 int vtp_scatter_image_rows(const float* src, const int* img_idx, float* dst, int n_img, long N, int D, float alpha, int accumulate,
                            void* stream);
+/* Tail rows of the last block: everything behind its attention is row-wise and runs on the Mc = L + T rows a consumer reads.  Compact
+ * row j < L is full row j; compact row L + t is full row L + idx[t] (idx int32 [T], -1 = padding: an all-zero compact row).
+ *   vtp_gather_tail_rows : o_c bf16 / x_c f32 [L + T, D] = those rows of o / x [M, D], one launch (either pair may be null)
+ *   vtp_tail_row_map     : map int32 [M] = full row -> compact row, -1 where no compact row reads it (reads no host-side count)
+ *   vtp_expand_rows_bf16 : dst[r, :] = map[r] >= 0 ? src[map[r], :] : 0 for all M rows of dst in one pass (src bf16 [Mc, D]) */
+int vtp_gather_tail_rows(const void* o, const float* x, const int* idx, void* o_c, float* x_c, int T, int L, int M, int D,
+                         void* stream);
+int vtp_tail_row_map(const int* idx, int* map, int T, int L, int M, void* stream);
+int vtp_expand_rows_bf16(const void* src, const int* map, void* dst, int M, int Mc, int D, void* stream);
 int vtp_layerscale_wgrad(const float* G, const float* W, const float* bias, const float* colsum, const float* gamma, float* dW,
                          float* db, float* dgamma, int N, int K, void* stream);
 int vtp_scaled_transpose(const float* W, const float* gamma, void* dstT, int N, int K, void* stream);
@@ -152,6 +162,11 @@ int vtp_norm_bwd(const void* dy, const float* x, const float* w, const float* st
 int vtp_norm_bwd_pvec(const void* dy, const float* x, const float* w, const float* stats, const float* dres, float* dx,
                       void* dx_bf16, float* dw, float* db, float* dx_colsum, const float* pvec, int prow0, int pB, int pN, int M,
                       int D, int kind, void* stream);
+/* vtp_norm_bwd whose residual gradient lives in a compact buffer dres f32 [dres_M, D]: row r adds dres[dres_rows[r]], or nothing when
+ * the entry is -1 (dres_rows int32 [M]; null: exactly vtp_norm_bwd).  With a row map: D <= 1024. */
+int vtp_norm_bwd_rows(const void* dy, const float* x, const float* w, const float* stats, const float* dres, const int* dres_rows,
+                      int dres_M, float* dx, void* dx_bf16, float* dw, float* db, float* dx_colsum, int M, int D, int kind,
+                      void* stream);
 /* out f32 [B, D] = scale * sum_{t=1}^{N-1} x[b*N + t] over the bf16 token rows x [B*N, D] of one list item (row 0 of every image is
  * its cls token and is skipped); scale = 1 / (N - 1) is the mean of the patch tokens.  N >= 2, D % 4 == 0. */
 int vtp_pool_patch_rows(const void* x, float* out, int B, int N, int D, float scale, void* stream);

@@ -18,6 +18,11 @@ SHAPES = [  # (tag, M, N, K, kind)
     ("proj f32res D", 8192, 768, 768, "f32"), ("w3 f32res D", 8192, 768, 2048, "f32"), ("qkv+rope D", 8192, 2304, 768, "rope"),
     ("w12 swiglu D", 8192, 4096, 768, "swiglu"), ("w3 dgrad+swiglu D", 8192, 2048, 768, "dsw"), ("w12 dgrad D", 8192, 768, 4096, "bf16"),
     ("qkv dgrad D", 8192, 768, 2304, "bf16"), ("proj dgrad D", 8192, 768, 768, "bf16"),
+    # tail rows: the last trunk block runs proj / w12 / w3 (and their dgrads) on the rows the losses read -- 11 040 of the student's
+    # 34 144 and 2 560 of the teacher's 16 448 at the benchmark geometry; the other 11 blocks keep the shapes above
+    ("proj f32res tail", 11040, 768, 768, "f32"), ("w12 swiglu tail", 11040, 4096, 768, "swiglu"), ("w3 f32res tail", 11040, 768, 2048, "f32"),
+    ("w3 dgrad+swiglu tail", 11040, 2048, 768, "dsw"), ("w12 dgrad tail", 11040, 768, 4096, "bf16"), ("proj dgrad tail", 11040, 768, 768, "bf16"),
+    ("proj f32res tail T", 2560, 768, 768, "f32"), ("w12 swiglu tail T", 2560, 4096, 768, "swiglu"), ("w3 f32res tail T", 2560, 768, 2048, "f32"),
     ("text c_fc gelu", 2464, 3072, 768, "gelu"), ("text c_proj f32res", 2464, 768, 3072, "f32"), ("text qkv", 2464, 2304, 768, "bf16"),
     ("text out f32res", 2464, 768, 768, "f32"), ("text c_fc dgrad", 2464, 768, 3072, "bf16"), ("text c_proj dgrad", 2464, 3072, 768, "bf16"),
 ]
@@ -61,6 +66,7 @@ def main():
         tot += t
         print(f"[{tag}] {name:22s} M={M:6d} N={N:5d} K={K:5d}  {t:7.1f} us  {2.0 * M * N * K / t / 1e6:7.1f} TF/s", flush=True)
     print(f"[{tag}] sum {tot:.1f} us")
+    print(f"[{tag}] note: per step the M = 34 144 / 16 448 block shapes run 11 times and the 'tail' shapes (M = 11 040 / 2 560) once")
 
 
 if __name__ == "__main__":

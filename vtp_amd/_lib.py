@@ -16,6 +16,7 @@ SIGNATURES = {
     "vtp_norm_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],  # dy x w stats dres dx dxb dw db dxsum M D kind stream
     # ... + pvec prow0 pB pN in front of M
     "vtp_norm_bwd_pvec": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "vtp_norm_bwd_rows": [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P],  # ... dres dres_rows dres_M dx ...
     "vtp_pool_patch_rows": [_P, _P, _I, _I, _I, _F, _P],
     "vtp_rope_qk": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vtp_attn_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _L, _L, _L, _L, _F, _I, _P],
@@ -53,6 +54,9 @@ SIGNATURES = {
     "vtp_colsum_bf16_rows": [_P, _I, _P, _P, _I, _I, _P],
     "vtp_gather_image_rows": [_P, _P, _P, _P, _I, _L, _I, _F, _P],
     "vtp_scatter_image_rows": [_P, _P, _P, _I, _L, _I, _F, _I, _P],
+    "vtp_gather_tail_rows": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "vtp_tail_row_map": [_P, _P, _I, _I, _I, _P],
+    "vtp_expand_rows_bf16": [_P, _P, _P, _I, _I, _I, _P],
     "vtp_layerscale_wgrad": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
     "vtp_scaled_transpose": [_P, _P, _P, _I, _I, _P],
     "vtp_qk_norm_fwd": [_P, _P, _P, _P, _P, _L, _I, _F, _P],

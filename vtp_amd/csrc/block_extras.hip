@@ -172,6 +172,62 @@ __global__ __launch_bounds__(256) void qk_norm_bwd_kernel(bf16* __restrict__ dqk
   }
 }
 
+// ---- tail rows of the last block (engine.py Stack.forward: everything behind the attention is row-wise and runs only on the rows a
+// consumer reads).  Compact row j < L is full row j (the lead items); compact row L + t is full row L + idx[t] -- idx int32 [T], the
+// head's rows relative to the first SSL row, -1 = padding (the compact row is all zero and no full row maps to it).
+
+// o_c / x_c [L + T, D] = the rows of o (bf16) / x (f32) [M, D], one launch for both; a row of work = D/8 bf16 chunks + D/4 f32 chunks
+__global__ __launch_bounds__(256) void gather_tail_rows_kernel(const bf16* __restrict__ o, const float* __restrict__ x,
+                                                               const int* __restrict__ idx, bf16* __restrict__ o_c,
+                                                               float* __restrict__ x_c, int T, int L, int M, int D) {
+  const int cb = o ? D / 8 : 0, cpr = cb + (x ? D / 4 : 0);
+  const long total = (long)(L + T) * cpr;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256L) {
+    const int j = (int)(i / cpr), c = (int)(i - (long)j * cpr);
+    int r = j;
+    if (j >= L) {
+      r = idx[j - L];
+      r = (r >= 0 && r < M - L) ? r + L : -1;
+    }
+    if (c < cb) {
+      bf16x8 v = bf16x8{};
+      if (r >= 0) v = *(const bf16x8*)(o + (long)r * D + 8 * c);
+      *(bf16x8*)(o_c + (long)j * D + 8 * c) = v;
+    } else {
+      const int c4 = c - cb;
+      f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
+      if (r >= 0) v = *(const f32x4*)(x + (long)r * D + 4 * c4);
+      *(f32x4*)(x_c + (long)j * D + 4 * c4) = v;
+    }
+  }
+}
+
+// map[r] (full row -> compact row): r for r < L, -1 behind it; the second launch then writes map[L + idx[t]] = L + t for idx[t] >= 0
+__global__ __launch_bounds__(256) void tail_row_map_fill_kernel(int* __restrict__ map, int L, int M) {
+  for (int r = blockIdx.x * 256 + threadIdx.x; r < M; r += gridDim.x * 256) map[r] = r < L ? r : -1;
+}
+__global__ __launch_bounds__(256) void tail_row_map_set_kernel(const int* __restrict__ idx, int* __restrict__ map, int T, int L, int M) {
+  for (int t = blockIdx.x * 256 + threadIdx.x; t < T; t += gridDim.x * 256) {
+    const int r = idx[t];
+    if (r >= 0 && r < M - L) map[L + r] = L + t;
+  }
+}
+
+// dst[r, :] = map[r] >= 0 ? src[map[r], :] : 0 over all M rows of dst in one pass (every 128-B line of dst is written whole: 16 B per
+// lane, consecutive lanes): replaces a fill of dst plus a scatter of the Mc source rows
+__global__ __launch_bounds__(256) void expand_rows_bf16_kernel(const bf16* __restrict__ src, const int* __restrict__ map,
+                                                               bf16* __restrict__ dst, int M, int Mc, int D) {
+  const int d8 = D / 8;
+  const long total = (long)M * d8;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256L) {
+    const int r = (int)(i / d8), c = (int)(i - (long)r * d8);
+    const int j = map[r];
+    bf16x8 v = bf16x8{};
+    if (j >= 0 && j < Mc) v = *(const bf16x8*)(src + (long)j * D + 8 * c);
+    *(bf16x8*)(dst + (long)r * D + 8 * c) = v;
+  }
+}
+
 }  // namespace vtp
 using namespace vtp;
 
@@ -226,4 +282,30 @@ extern "C" int vtp_qk_norm_bwd(void* dqkv, const void* qkv, const float* inv, co
   hipLaunchKernelGGL(qk_norm_bwd_kernel, dim3((int)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, (hipStream_t)stream, (bf16*)dqkv,
                      (const bf16*)qkv, inv, wq, wk, dwq, dwk, M, D);
   return check_launch("qk_norm_bwd");
+}
+
+extern "C" int vtp_gather_tail_rows(const void* o, const float* x, const int* idx, void* o_c, float* x_c, int T, int L, int M, int D,
+                                    void* stream) {
+  VTP_REQUIRE((o || x) && (!o || o_c) && (!x || x_c) && (idx || T == 0), "vtp_gather_tail_rows: null pointer");
+  VTP_REQUIRE(T >= 0 && L >= 0 && L + T > 0 && L <= M && D > 0 && D % 8 == 0,
+              "vtp_gather_tail_rows: need L <= M, L + T > 0, D %% 8 == 0 (T=%d L=%d M=%d D=%d)", T, L, M, D);
+  const long items = (long)(L + T) * ((o ? D / 8 : 0) + (x ? D / 4 : 0));
+  hipLaunchKernelGGL(gather_tail_rows_kernel, dim3(extras_grid(items)), dim3(256), 0, (hipStream_t)stream, (const bf16*)o, x, idx,
+                     (bf16*)o_c, x_c, T, L, M, D);
+  return check_launch("gather_tail_rows");
+}
+
+extern "C" int vtp_tail_row_map(const int* idx, int* map, int T, int L, int M, void* stream) {
+  VTP_REQUIRE(map && (idx || T == 0) && T >= 0 && L >= 0 && L <= M && M > 0, "vtp_tail_row_map: bad argument (T=%d L=%d M=%d)", T, L, M);
+  hipLaunchKernelGGL(tail_row_map_fill_kernel, dim3(extras_grid(M)), dim3(256), 0, (hipStream_t)stream, map, L, M);
+  if (T > 0)
+    hipLaunchKernelGGL(tail_row_map_set_kernel, dim3(extras_grid(T)), dim3(256), 0, (hipStream_t)stream, idx, map, T, L, M);
+  return check_launch("tail_row_map");
+}
+
+extern "C" int vtp_expand_rows_bf16(const void* src, const int* map, void* dst, int M, int Mc, int D, void* stream) {
+  VTP_REQUIRE(src && map && dst && M > 0 && Mc > 0 && D > 0 && D % 8 == 0, "vtp_expand_rows_bf16: bad argument (D %% 8 == 0)");
+  hipLaunchKernelGGL(expand_rows_bf16_kernel, dim3(extras_grid((long)M * D / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16*)src,
+                     map, (bf16*)dst, M, Mc, D);
+  return check_launch("expand_rows_bf16");
 }

@@ -100,12 +100,15 @@ __device__ __forceinline__ void w4t_segment(const GroupArgs& ga, int tile, int k
   GemmArgs p{};
   p.A = w4t_uni(pr.A); p.B = w4t_uni(pr.B); p.C = w4t_uni(pr.C); p.resid = w4t_uni(pr.accumulate) ? (const float*)p.C : nullptr;
   p.colsum = w4t_uni(pr.colsum);
-  p.M = w4t_uni(pr.M); p.N = w4t_uni(pr.N); p.K = ga.K; p.lda = w4t_uni(pr.lda); p.ldb = w4t_uni(pr.ldb); p.ldc = w4t_uni(pr.ldc);
+  p.M = w4t_uni(pr.M); p.N = w4t_uni(pr.N); p.K = w4t_uni(pr.K) > 0 ? w4t_uni(pr.K) : ga.K; p.lda = w4t_uni(pr.lda); p.ldb = w4t_uni(pr.ldb); p.ldc = w4t_uni(pr.ldc);
   p.c_grp = w4t_uni(pr.c_grp); p.c_pre = w4t_uni(pr.c_pre); p.k_split = ga.k_split; p.alpha = 1.f;
   p.xcd_swizzle = 2;  // (bit 1: the LDS-staged store path of the shared epilogue)
   const int lt = tile - w4t_uni(pr.tile0), tiles_n = (p.N + 255) >> 8;
   const int n0 = (lt % tiles_n) << 8, m0 = (lt / tiles_n) << 8;
-  const unsigned nk2 = (unsigned)((kcount + 127) >> 7);  // pairs of k-tiles (an odd count is padded with an all-zero k-tile)
+  // the problem's own token count bounds the range (a problem of a mixed launch has fewer rows than GroupArgs.K): rows behind it are
+  // never staged
+  kcount = max(0, min(kcount, p.K - kbeg));
+  const unsigned nk2 = (unsigned)max(1, (kcount + 127) >> 7);  // pairs of k-tiles (an odd count is padded with an all-zero k-tile)
 
   // ---------------------------------------------------------------- staging: wave w = A sub-image w and B sub-image w of every k-tile
   // piece i (0..7) = k rows 8 i + (lane >> 3) of the k-tile; the lane's 16-B chunk slot lane & 7 holds source chunk

@@ -15,7 +15,8 @@ struct GroupProblem {  // 64-bit fields: written by the host as an int64 tensor
   long c_grp, c_pre;
   long tile0;       // first tile of this problem in the launch's tile list
   long accumulate;  // 1: C += result, 0: C = result
-  long pad[3];
+  long K;           // token rows of THIS problem (item-list launches only: its items cut [0, K)); 0 = GroupArgs.K
+  long pad[2];
 };
 struct GroupItem {  // one workgroup of an item-list launch (vtp_gemm_tn_grouped_items): 8 x int32, written by the host
   int tile;           // index in the launch's tile list

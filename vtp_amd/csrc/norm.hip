@@ -89,14 +89,16 @@ __global__ __launch_bounds__(256) void norm_fwd_kernel(const float* __restrict__
 
 // PV: the rows prow0 + b*pN + t (b < pB, 1 <= t < pN) -- the patch rows of one list item -- take pvec[b] (f32 [pB, D]) on top of
 // dy, added in f32 before anything reads dy (the gradient of a mean-pooled feature, spread over the rows it averaged)
-template <int KIND, int NC, bool PV = false>
+// MAPPED: dres is a COMPACT buffer and row r adds dres[dres_rows[r]] (zero when the entry is -1 or out of range): the residual gradient
+// of the rows the last block's tail ran on (engine.py), without an expanded f32 copy
+template <int KIND, int NC, bool PV = false, bool MAPPED = false>
 __global__ __launch_bounds__(256, 2) void norm_bwd_kernel(const bf16* __restrict__ dy, const float* __restrict__ x,
                                                        const float* __restrict__ w, const float* __restrict__ stats,
                                                        const float* __restrict__ dres, float* __restrict__ dx,
                                                        bf16* __restrict__ dxb, float* __restrict__ dw, float* __restrict__ db,
                                                        float* __restrict__ dxsum, int M, int D,
                                                        const float* __restrict__ pvec = nullptr, int prow0 = 0, int pB = 0,
-                                                       int pN = 1) {
+                                                       int pN = 1, const int* __restrict__ dres_rows = nullptr, int dres_M = 0) {
   constexpr int R = NC <= 3 ? 2 : 1;  // rows in flight per wave: the x / dy loads of all R rows are issued before the first reduction
   const int lane = threadIdx.x & 63;
   const int wv_id = threadIdx.x >> 6;
@@ -123,6 +125,11 @@ __global__ __launch_bounds__(256, 2) void norm_bwd_kernel(const bf16* __restrict
       const int row = min(row0 + r, M - 1);
       mean[r] = stats[2 * row];
       rstd[r] = stats[2 * row + 1];
+      int drow = row;
+      if constexpr (MAPPED && PRE) {
+        drow = dres_rows[row];
+        if (drow >= dres_M) drow = -1;
+      }
 #pragma unroll
       for (int c = 0; c < NC; ++c) {
         const int col = (c * 64 + lane) * 4;
@@ -130,7 +137,8 @@ __global__ __launch_bounds__(256, 2) void norm_bwd_kernel(const bf16* __restrict
           xv[r][c] = *(const f32x4*)(x + (size_t)row * D + col);
           gy[r][c] = *(const bf16x4*)(dy + (size_t)row * D + col);
           if constexpr (PRE) {
-            if (dres) dr[r][c] = *(const f32x4*)(dres + (size_t)row * D + col);
+            if constexpr (MAPPED) dr[r][c] = drow >= 0 ? *(const f32x4*)(dres + (size_t)drow * D + col) : (f32x4){0.f, 0.f, 0.f, 0.f};
+            else if (dres) dr[r][c] = *(const f32x4*)(dres + (size_t)row * D + col);
           }
         }
       }
@@ -176,7 +184,10 @@ __global__ __launch_bounds__(256, 2) void norm_bwd_kernel(const bf16* __restrict
           for (int e = 0; e < 4; ++e) o[e] = rstd[r] * (g[c][e] - s1 - xh[c][e] * s2);
           if (dres) {
             if constexpr (PRE) o += dr[r][c];
-            else o += *(const f32x4*)(dres + (size_t)row * D + col);
+            else if constexpr (MAPPED) {
+              const int drow = dres_rows[row];
+              o += (drow >= 0 && drow < dres_M) ? *(const f32x4*)(dres + (size_t)drow * D + col) : (f32x4){0.f, 0.f, 0.f, 0.f};
+            } else o += *(const f32x4*)(dres + (size_t)row * D + col);
           }
           *(f32x4*)(dx + (size_t)row * D + col) = o;
           if (dxb) {
@@ -348,6 +359,38 @@ extern "C" int vtp_norm_bwd_pvec(const void* dy, const float* x, const float* w,
     launch_norm_bwd_pvec<1>(grid, (hipStream_t)stream, (const bf16*)dy, x, w, stats, dres, dx, (bf16*)dx_bf16, dw, db, dx_colsum, M, D,
                             pvec, prow0, pB, pN);
   return check_launch("norm_bwd_pvec");
+}
+
+extern "C" int vtp_norm_bwd_rows(const void* dy, const float* x, const float* w, const float* stats, const float* dres,
+                                 const int* dres_rows, int dres_M, float* dx, void* dx_bf16, float* dw, float* db, float* dx_colsum,
+                                 int M, int D, int kind, void* stream) {
+  if (!dres_rows)
+    return vtp_norm_bwd(dy, x, w, stats, dres, dx, dx_bf16, dw, db, dx_colsum, M, D, kind, stream);
+  VTP_REQUIRE(dy && x && w && stats && dx && dres, "vtp_norm_bwd_rows: null pointer (a row map needs dres)");
+  VTP_REQUIRE(!dx_colsum || dx_bf16, "vtp_norm_bwd_rows: dx_colsum sums the bf16 output and needs dx_bf16");
+  VTP_REQUIRE(M > 0 && dres_M > 0 && D > 0 && D % 4 == 0 && D <= 1024,
+              "vtp_norm_bwd_rows: need 0 < D <= 1024, D %% 4 == 0, dres_M > 0 (D=%d dres_M=%d)", D, dres_M);
+  VTP_REQUIRE(kind == 0 || kind == 1, "vtp_norm_bwd_rows: kind must be 0 or 1");
+  dim3 grid(norm_bwd_blocks(M, D)), block(256);
+  const bf16* dyb = (const bf16*)dy;
+  bf16* dxb = (bf16*)dx_bf16;
+  const int nc = cdiv(D, 256);
+#define NORM_ROWS(KIND, NC)                                                                                                         \
+  hipLaunchKernelGGL((norm_bwd_kernel<KIND, NC, false, true>), grid, block, 0, (hipStream_t)stream, dyb, x, w, stats, dres, dx, dxb, dw, \
+                     db, dx_colsum, M, D, (const float*)nullptr, 0, 0, 1, dres_rows, dres_M)
+  // (no NC = 8 variant, as for the pooled-vector entry: the wide rows leave no registers for the mapped read)
+#define NORM_ROWS_KIND(KIND)           \
+  do {                                 \
+    if (nc <= 1) NORM_ROWS(KIND, 1);   \
+    else if (nc == 2) NORM_ROWS(KIND, 2); \
+    else if (nc == 3) NORM_ROWS(KIND, 3); \
+    else NORM_ROWS(KIND, 4);           \
+  } while (0)
+  if (kind == 0) NORM_ROWS_KIND(0);
+  else NORM_ROWS_KIND(1);
+#undef NORM_ROWS_KIND
+#undef NORM_ROWS
+  return check_launch("norm_bwd_rows");
 }
 
 extern "C" int vtp_pool_patch_rows(const void* x, float* out, int B, int N, int D, float scale, void* stream) {

@@ -396,6 +396,18 @@ def linear_bwd(ws: Workspace, tag: str, L, dy_b, x_b, M: int, d_in, *, need_dx: 
                     a_remap=dy_remap, c_remap=dx_remap)
 
 
+class WgradGroups:
+    """several ops.WgradGroup launched back to back (the weight gradients of a block whose problems sum over different token counts,
+    where one launch cannot take them)"""
+
+    def __init__(self, parts):
+        self.parts = parts
+
+    def launch(self):
+        for g in self.parts:
+            g.launch()
+
+
 # =====================================================================================================================
 # a run of SelfAttentionBlocks (block.py:137-308) -- shared by the ViT trunk and the pixel decoder
 # =====================================================================================================================
@@ -417,6 +429,10 @@ class BlockSaved(NamedTuple):
     st2: torch.Tensor       # f32 [M, 2]
     pre: torch.Tensor       # bf16 [M, 2H] (SwiGLU, 8|8 interleaved) or [M, H] (GELU): the FFN pre-activations
     hid: torch.Tensor       # bf16 [M, H]
+    # tail rows (the last block of a pass with a row plan, Stack.forward): ffn_in .. hid above have Mc rows, o keeps all M rows for the
+    # attention backward, and these two are set
+    o_c: Optional[torch.Tensor] = None      # bf16 [Mc, D]: the rows of o the projection ran on
+    row_map: Optional[torch.Tensor] = None  # int32 [M]: full row -> compact row, -1 where nothing reads the row
 
 
 ATTN_SCALE = 1.0 / math.sqrt(64.0)  # head_dim 64
@@ -677,8 +693,9 @@ class Stack:
             ops.attn_fwd(q_s, q_s[:, D:], q_s[:, 2 * D:], o_s, lse[r0 * heads:], Bs, Ns, heads, Ns * 3 * D, 3 * D, Ns * D, D,
                          ATTN_SCALE, self.causal)
 
-    def _attn_fwd(self, ws: Workspace, t: str, i: int, x, out, resid, M: int, rows, prefix_tokens: int, rope_plan):
-        """out = (resid +) proj(attn(rope(qkv(norm1(x)))));  returns (xn1, st1, qkv, o, lse)"""
+    def _attn_fwd(self, ws: Workspace, t: str, i: int, x, out, resid, M: int, rows, prefix_tokens: int, rope_plan, proj: bool = True):
+        """out = (resid +) proj(attn(rope(qkv(norm1(x)))));  returns (xn1, st1, qkv, o, lse).  proj=False: stops behind the attention
+        (the caller projects a subset of the rows of o)"""
         D, heads, b = self.D, self.heads, self.blocks[i]
         xn1, st1 = ws.get(t + "xn1", (M, D), BF), ws.get(t + "st1", (M, 2), F32)
         qkv, o = ws.get(t + "qkv", (M, 3 * D), BF), ws.get(t + "o", (M, D), BF)
@@ -695,7 +712,8 @@ class Stack:
         else:
             ops.gemm_nt(xn1, b.qkv.w, qkv, M=M, N=3 * D, K=D, bias=b.qkv.bias, epi=EPI_BF16)
         self._attention(qkv, o, lse, rows, i, prefix_tokens, rope_plan is None)
-        ops.gemm_nt(o, b.proj.w, out, M=M, N=D, K=D, bias=b.proj.bias, gamma=b.ls1, resid=resid, epi=EPI_F32)
+        if proj:
+            ops.gemm_nt(o, b.proj.w, out, M=M, N=D, K=D, bias=b.proj.bias, gamma=b.ls1, resid=resid, epi=EPI_F32)
         return xn1, st1, qkv, o, lse
 
     def _ffn_fwd(self, ws: Workspace, t: str, i: int, x, out, resid, M: int, train: bool):
@@ -735,12 +753,23 @@ class Stack:
     def _attn_bwd(self, ws: Workspace, t: str, i: int, s: BlockSaved, dy, dy_b, dx, dx_b, M: int, bt: str, dqkv, rows,
                   prefix_tokens: int, *, bias_done: bool = False, probs=None, join: bool = False, dx_colsum=None):
         """_ffn_bwd of the attention branch.  join: wait for the side stream before norm1's backward (which overwrites the dy
-        operand of the previous block's grouped weight gradients)"""
+        operand of the previous block's grouped weight gradients).  With tail rows (s.row_map set) dy / dy_b are the COMPACT [Mc, D]
+        gradients: the projection's dgrad and weight gradient run on them, d_o is expanded to all M rows for the attention backward
+        (every row is a key / value), and norm1's backward picks its residual gradient through the row map."""
         D, heads, b = self.D, self.heads, self.blocks[i]
         d_o, dxn = ws.get(bt + "do", (M, D), BF), ws.get(bt + "dxn", (M, D), BF)
         delta = ws.get(bt + "delta", (M * heads,), F32)
-        linear_bwd(ws, "proj", b.proj, dy_b, s.o, M, d_o, bias_grad_done=bias_done, ls=(b.ls1, b.gls1) if b.ls1 is not None else None,
-                   defer=probs)
+        if s.row_map is not None:
+            Mc = s.o_c.shape[0]
+            d_o_c = ws.get(bt + "do", (Mc, D), BF)
+            linear_bwd(ws, "proj", b.proj, dy_b, s.o_c, Mc, d_o_c, bias_grad_done=bias_done, defer=probs)
+            if probs is not None:
+                for pr in probs:  # what has been recorded so far (w3, w12, proj) sums over the compact rows
+                    pr["Ktok"] = Mc
+            ops.expand_rows_bf16(d_o_c, s.row_map, d_o, M, Mc, D)
+        else:
+            linear_bwd(ws, "proj", b.proj, dy_b, s.o, M, d_o, bias_grad_done=bias_done,
+                       ls=(b.ls1, b.gls1) if b.ls1 is not None else None, defer=probs)
         for r0, Bs, Ns, rp in rows:
             r1 = r0 + Bs * Ns
             q_s, dq_s = s.qkv[r0:r1], dqkv[r0:r1]
@@ -754,16 +783,32 @@ class Stack:
         linear_bwd(ws, "qkv", b.qkv, dqkv, s.xn1, M, dxn, defer=probs)
         if join:
             OVERLAP.join()
-        ops.norm_bwd(dxn, s.attn_in, b.n1w, s.st1, dy, dx, dx_b, b.gn1w, b.gn1b, M, D, self.kind, dx_colsum=dx_colsum)
+        if s.row_map is not None:
+            ops.norm_bwd_rows(dxn, s.attn_in, b.n1w, s.st1, dy, s.row_map, dx, dx_b, b.gn1w, b.gn1b, M, D, self.kind, dx_colsum=dx_colsum)
+        else:
+            ops.norm_bwd(dxn, s.attn_in, b.n1w, s.st1, dy, dx, dx_b, b.gn1w, b.gn1b, M, D, self.kind, dx_colsum=dx_colsum)
 
     # x: f32 [M, D] input residual.  Returns the output residual (f32 [M, D]).
-    def forward(self, ws: Workspace, x, segs, prefix_tokens: int, train: bool):
+    def tail_rows_ok(self, train: bool) -> bool:
+        """may forward() take a tail row plan?  Not under stochastic depth (the branches already run on gathered rows), not on the fp8
+        forward or its calibration pass, not with LayerScale; VTP_TAIL_ROWS=0 keeps the full path (same-box A/B runs)"""
+        return (_env_flag("VTP_TAIL_ROWS") and self.style == "vit" and not (train and self.drop_plan is not None)
+                and getattr(self, "fp8", None) is None and self.D % 8 == 0 and self.D <= 1024
+                and self.blocks[-1].ls1 is None and self.blocks[-1].ls2 is None)
+
+    def forward(self, ws: Workspace, x, segs, prefix_tokens: int, train: bool, tail=None):
         """`segs` = [(B_i, N_i, rope_i)]: several batches of different sequence length concatenated along the token-row
         axis (the reference's list path, block.py:235-298 / utils.py:14-25 cat_keep_shapes): every linear / norm runs once
         over all rows, RoPE and attention run per segment on its row range.  In training with a drop plan set (stochastic depth)
-        `x` is updated IN PLACE block after block and each branch runs on the gathered rows of its kept images."""
+        `x` is updated IN PLACE block after block and each branch runs on the gathered rows of its kept images.
+        tail = (idx int32 [T] on the device, T, L): only rows [0, L) and L + idx[t] of the output are read (idx[t] = -1: padding).  The
+        LAST block then runs everything behind its attention -- proj, norm2, the FFN: all row-wise -- on those Mc = L + T rows alone
+        (its attention still sees every row: all of them are keys and values) and the output has Mc rows: [0, L) unchanged, L + t =
+        full row L + idx[t], zero-input rows for the padding.  The kept rows are bit-identical to the full pass."""
         D = self.D
         M = sum(b * n for b, n, _ in segs)
+        if tail is not None and not self.tail_rows_ok(train):
+            raise RuntimeError("Stack.forward: a tail row plan was passed to a pass that cannot take one (tail_rows_ok)")
         fp8 = getattr(self, "fp8", None)
         if fp8 is not None and fp8["ready"] and not train:
             return self._forward_fp8(ws, x, segs, prefix_tokens, M)
@@ -789,16 +834,28 @@ class Stack:
                 self._scatter(delta, x, segs, csegs, i, 1, scales, accumulate=True)
             else:
                 t = f"{i}." if train else ""
-                x1, x2 = x, ws.get(t + "xmid", (M, D), F32)  # the block input (previous block's xout) is kept for norm1 backward
-                xout = ws.get((f"{i}.xout" if train else f"xout{i & 1}"), (M, D), F32)
-                a = self._attn_fwd(ws, t, i, x1, x2, x1, M, rows, prefix_tokens, rope_plan)
-                f = self._ffn_fwd(ws, t, i, x2, xout, x2, M, train)
+                tl = tail if i == self.depth - 1 else None
+                Mo = M if tl is None else tl[2] + tl[1]  # rows behind the attention
+                x1, x2 = x, ws.get(t + "xmid", (Mo, D), F32)  # the block input (previous block's xout) is kept for norm1 backward
+                xout = ws.get((f"{i}.xout" if train else f"xout{i & 1}"), (Mo, D), F32)
+                a = self._attn_fwd(ws, t, i, x1, x2, x1, M, rows, prefix_tokens, rope_plan, proj=tl is None)
+                if tl is not None:
+                    idx, T, L = tl
+                    o_c, x_c = ws.get(t + "o_c", (Mo, D), BF), ws.get(t + "x_c", (Mo, D), F32)
+                    ops.gather_tail_rows(a[3], x1, idx, o_c, x_c, T, L, M, D)
+                    b = self.blocks[i]
+                    ops.gemm_nt(o_c, b.proj.w, x2, M=Mo, N=D, K=D, bias=b.proj.bias, resid=x_c, epi=EPI_F32)
+                    if train:
+                        row_map = ws.get(t + "row_map", (M,), torch.int32)
+                        ops.tail_row_map(idx, row_map, T, L, M)
+                        extra_saved = (o_c, row_map)
+                f = self._ffn_fwd(ws, t, i, x2, xout, x2, Mo, train)
                 if calib is not None:  # fp8 calibration pass: amax of the four GEMM inputs of this block
                     for j, tns in enumerate((a[0], a[3], f[0], f[3])):
                         ops.amax(tns, calib[i, j:j + 1])
                 x = xout
             if train:
-                saved_all.append(BlockSaved(x1, *a, x2, *f))
+                saved_all.append(BlockSaved(x1, *a, x2, *f, *(extra_saved if (not drop and tl is not None) else ())))
         self.last_saved = saved_all  # per-call context: several forward passes may be in flight before their backward
         return x
 
@@ -881,10 +938,13 @@ class Stack:
         hold_last (grouped weight gradients only): block 0's group is neither launched nor announced here but left in self.held =
         (0, group) -- the caller launches it and yields ("block", 0) -- and extra_last, a list of problem records {x, gw, gb, N, K,
         swiglu_h} over the same token rows whose dy is this stack's input gradient (TrunkEngine: the patch-embed weight gradient),
-        rides in that launch."""
+        rides in that launch.
+        Tail rows (the forward ran with a row plan: saved[-1].row_map is set): dy / dy_b have the Mc compact rows, and the last block's
+        FFN half, its projection and their weight gradients (K = Mc token rows) run on them -- see _attn_bwd."""
         D, H = self.D, self.H
         M = sum(b * n for b, n, _ in segs)
         saved = self.last_saved if saved is None else saved
+        tail_Mc = saved[-1].o_c.shape[0] if saved and saved[-1].row_map is not None else None
         drop = self.drop_plan is not None
         if drop:
             csegs, Mb = self._drop_segs(segs)
@@ -939,13 +999,17 @@ class Stack:
                 continue
             dxo = ws.get(f"b.dx{i & 1}", (M, D), F32)
             dxo_b = ws.get(f"b.dx_b{i & 1}", (M, D), BF)
-            dmid_b = ws.get("b.dmid_b" + par(i), (M, D), BF)
+            Mf = tail_Mc if (tail_Mc is not None and i == self.depth - 1) else M  # rows of the block's FFN half
+            if Mf != M:
+                dpre = ws.get(bt + "dx12" + par(i), (Mf, 2 * H if self.swiglu else H), BF)
+            dmid = ws.get("b.dmid", (Mf, D), F32)
+            dmid_b = ws.get("b.dmid_b" + par(i), (Mf, D), BF)
             probs = [] if grouped else None
             if grouped:
                 launch_pending()  # dW of block i + 1, beside this block's kernels
             # the norm backward kernels also sum the columns of their bf16 output = the bias gradient of the linear layer that
             # takes it as dy (proj after the FFN branch; the previous block's w3 after the attention branch)
-            self._ffn_bwd(ws, i, s, dy, dy_b, dmid, dmid_b, M, bt, dpre, fused=self.swiglu and b.ls2 is None,
+            self._ffn_bwd(ws, i, s, dy, dy_b, dmid, dmid_b, Mf, bt, dpre, fused=self.swiglu and b.ls2 is None,
                           bias_done=dy_colsum_done if i == self.depth - 1 else self.w3_colsum_target(i) is not None, probs=probs,
                           dx_colsum=b.proj.gb if b.ls1 is None else None)
             # grouped: dW of block i + 1 is done before norm1's backward overwrites the dy operand it read (b.dx_b, same parity)
@@ -957,13 +1021,23 @@ class Stack:
                 yield ("block", i)
                 continue
             extra = [dict(pr, dy=dy_b) for pr in extra_last] if (i == 0 and hold_last and extra_last) else []
-            gkey = (i, bool(self.wgrad_overwrite), len(extra))
+            gkey = (i, bool(self.wgrad_overwrite), len(extra), Mf)
             grp = groups.get(gkey)
             if grp is None:
-                grp = ops.WgradGroup(M)
-                for pr in probs + extra:
-                    grp.add(pr["dy"], pr["x"], pr["gw"], pr["gb"], pr["N"], pr["K"], pr["swiglu_h"], accumulate=not self.wgrad_overwrite)
-                groups[gkey] = grp.finalize(self.store.device, scratch)
+                # problems over different token counts (tail rows: proj / w12 / w3 over Mc rows beside qkv over all M) share the
+                # launch where the item-list kernel runs it, cut per problem; otherwise one group per token count, back to back
+                counts = sorted({pr.get("Ktok", M) for pr in probs + extra}, reverse=True)
+                if len(counts) > 1 and ops.wgrad_group_mixed_ok(counts):
+                    counts = [None]
+                parts = []
+                for kt in counts:
+                    g = ops.WgradGroup(M if kt is None else kt)
+                    for pr in probs + extra:
+                        if kt is None or pr.get("Ktok", M) == kt:
+                            g.add(pr["dy"], pr["x"], pr["gw"], pr["gb"], pr["N"], pr["K"], pr["swiglu_h"],
+                                  accumulate=not self.wgrad_overwrite, Ktok=pr.get("Ktok"))
+                    parts.append(g.finalize(self.store.device, scratch))
+                grp = groups[gkey] = parts[0] if len(parts) == 1 else WgradGroups(parts)
             if pending is not None:
                 yield ("block", pending[0])  # its weight gradients are complete (joined above)
             pending = (i, grp)
@@ -1183,11 +1257,18 @@ class TrunkEngine:
         flight at the same time with the same shape; self.ctx() returns the handle backward() needs for such passes."""
         return self.forward_list([(img, masks)], train, tag, rope_aug=rope_aug)
 
-    def forward_list(self, items, train: bool, tag: str = "", rope_aug: Optional[bool] = None):
+    def tail_rows_ok(self, train: bool) -> bool:
+        """may forward_list() take a tail row plan on this pass (Stack.tail_rows_ok)"""
+        return self.stack.tail_rows_ok(train)
+
+    def forward_list(self, items, train: bool, tag: str = "", rope_aug: Optional[bool] = None, tail=None):
         """items = [(img f32 [B_i,3,H_i,W_i], masks_i or None)]: the reference's list forward (forward_features_list,
         vision_transformer.py:221-258): batches of different resolution go through the blocks as ONE row-concatenated
         token buffer (one GEMM / norm launch per layer for all of them, attention + RoPE per segment).  Returns xnf bf16
-        [sum_i B_i*N_i, D]; ctx().segs[i].row0 is the first row of item i."""
+        [sum_i B_i*N_i, D]; ctx().segs[i].row0 is the first row of item i.
+        tail = (idx int32 [T] on the device, T, L): a row plan for the last block (Stack.forward) -- xnf then has the Mc = L + T rows
+        [0, L) | L + idx[t] only (ctx().Mc; ctx().M stays the row count of the list), and so have d_xnf_buffer() and the final-norm
+        backward.  Rows [0, L) keep their places: the items in front of row L are read as before."""
         st = self.store
         D = self.D
         segs, r0, p0 = [], 0, 0
@@ -1221,12 +1302,14 @@ class TrunkEngine:
             ops.gemm_nt(pt, self.pe.w, xs, M=g.B * g.hw, N=D, K=768, bias=self.pe.bias, epi=EPI_F32, a_remap=(g.hw, 1), c_remap=(g.hw, 1))
             ops.assemble_tokens(xs, st.p(self.prefix + "cls_token"), st.p(self.prefix + "mask_token"), g.masks, g.B, g.N, D)
         stack_segs = [(g.B, g.N, g.rope) for g in segs]
-        xl = self.stack.forward(ws, x0, stack_segs, 1, train)
-        xnf = ws.get("xnf", (M, D), BF)
-        stf = ws.get("stf", (M, 2), F32)
+        xl = self.stack.forward(ws, x0, stack_segs, 1, train, tail=tail)
+        Mc = M if tail is None else tail[2] + tail[1]
+        xnf = ws.get("xnf", (Mc, D), BF)
+        stf = ws.get("stf", (Mc, 2), F32)
         ops.norm_fwd(xl, st.p(self.prefix + "norm.weight"), st.p(self.prefix + "norm.bias") if self.kind == ops.NORM_LN else None, xnf, stf,
-                     M, D, self.eps, self.kind)
+                     Mc, D, self.eps, self.kind)
         c = TrunkCtx()
+        c.Mc = Mc
         c.ws, c.segs, c.M, c.xl, c.xnf, c.stf, c.patches, c.stack_saved, c.x0, c.stack_segs = \
             ws, segs, M, xl, xnf, stf, patches, self.stack.last_saved, x0, stack_segs
         self._ctx = c
@@ -1262,7 +1345,7 @@ class TrunkEngine:
         rows of the latent item are written by backward() (bottleneck dgrad); every other row must be written (or zeroed)
         by the heads before backward()."""
         c = self._ctx if ctx is None else ctx
-        return c.ws.get("b.d_xnf", (c.M, self.D), BF, zero=True)
+        return c.ws.get("b.d_xnf", (c.Mc, self.D), BF, zero=True)
 
     def backward(self, d_lat: Optional[torch.Tensor], ctx=None, lat_seg: int = 0, want_dimg: bool = False, pool=None):
         """d_lat: bf16 [B*hw, 64] grad of latents(seg=lat_seg), or None.  Accumulates every trunk parameter gradient into
@@ -1278,7 +1361,7 @@ class TrunkEngine:
         if ctx is not None:
             self._ctx = ctx
         c = self._ctx
-        ws, M, D = c.ws, c.M, self.D
+        ws, M, D = c.ws, c.Mc, self.D  # (with a tail row plan: the compact rows; the stack's backward widens to c.M behind the last FFN)
         d_xnf = ws.get("b.d_xnf", (M, D), BF, zero=True)  # rows stay zero unless a head wrote them before backward()
         wgrads, self.bott_wgrads = self.bott_wgrads, []
         for dz, x, R in wgrads:

@@ -64,6 +64,12 @@ def norm_bwd_pvec(dy, x, w, stats, dres, dx, dxb, dw, db, M, D, kind, pvec, row0
                                          _p(pvec), row0, B, N, M, D, kind, _s()), "vtp_norm_bwd_pvec")
 
 
+def norm_bwd_rows(dy, x, w, stats, dres, dres_rows, dx, dxb, dw, db, M, D, kind, dx_colsum=None):
+    """norm_bwd whose residual gradient is the COMPACT buffer dres f32 [Mc, D]: row r adds dres[dres_rows[r]] (int32 [M], -1: nothing)"""
+    _lib.check(_lib_().vtp_norm_bwd_rows(_p(dy), _p(x), _p(w), _p(stats), _p(dres), _p(dres_rows), dres.shape[0], _p(dx), _p(dxb), _p(dw),
+                                         _p(db), _p(dx_colsum), M, D, kind, _s()), "vtp_norm_bwd_rows")
+
+
 def pool_patch_rows(x, out, B, N, D, scale=None):
     """out f32 [B, D] = scale * sum of the patch rows 1..N-1 of every image of the bf16 token rows x [B*N, D]; default scale 1/(N-1): the
     mean pooling of vision_clip_feat = 'pooled'"""
@@ -253,18 +259,55 @@ def wgrad_group_items(rows, Ktok: int, base_splits: int, cus: int = None):
         for lt in range(((N + 255) // 256) * tn):
             tiles.append((tile0 + lt, pi, gb != 0 and lt % tn == 0))
     ncs = sum(1 for t in tiles if t[2])
-    more = ncs > 0 and len(tiles) * base_splits + ncs <= cus and Ktok // (base_splits + 1) >= 1024
+    # token rows per problem (record slot 13; 0 = Ktok).  Problems over different row counts (the last trunk block: qkv over every row,
+    # proj / w12 / w3 over the tail rows) are cut per problem, so that the workgroup counts follow the work (wgrad_mixed_splits)
+    Ks = [int(r[13]) or int(Ktok) for r in rows]
+    if len(set(Ks)) > 1:
+        per = wgrad_mixed_splits([sum(1 for t in tiles if t[1] == pi) for pi in range(len(rows))], Ks, cus)
+    else:
+        per = [base_splits] * len(rows)
+    n_items = sum(per[t[1]] for t in tiles)
     items, slots = [], 1
     for pi in range(len(rows)):
+        more = ncs > 0 and n_items + ncs <= cus and Ks[pi] // (per[pi] + 1) >= 1024
         for heavy in (True, False):
             grp = [t for t in tiles if t[1] == pi and t[2] == heavy]
             if not grp:
                 continue
-            cs = wgrad_k_cuts(Ktok, base_splits + 1 if (heavy and more) else base_splits)
+            cs = wgrad_k_cuts(Ks[pi], per[pi] + 1 if (heavy and more) else per[pi])
             slots = max(slots, len(cs))
             for z, (kb, kc) in enumerate(cs):
                 items += [[t[0], kb, kc, len(cs), z, 0, 0, 0] for t in grp]
     return items, slots
+
+
+def wgrad_mixed_splits(ntiles, Ks, cus: int):
+    """K slices per tile for each problem of a grouped launch whose problems have DIFFERENT token counts Ks (ntiles: their tile counts).
+    One round of the CUs runs every workgroup at once, so the launch lasts as long as its longest K slice: starting from one slice per
+    tile, the problems that share the longest slice are cut once more, as long as the launch still fits `cus` workgroups and every
+    slice keeps >= 16 k-tiles."""
+    n = len(Ks)
+    per = [1] * n
+    length = lambda p: ((Ks[p] + per[p] - 1) // per[p] + 63) // 64 * 64
+    while True:
+        top = max(length(p) for p in range(n))
+        grp = [p for p in range(n) if length(p) == top]
+        total = sum(per[p] * ntiles[p] for p in range(n))
+        if total + sum(ntiles[p] for p in grp) > cus or any(Ks[p] // (per[p] + 1) < 1024 for p in grp):
+            return per
+        for p in grp:
+            per[p] += 1
+
+
+def wgrad_group_mixed_ok(Ks) -> bool:
+    """may problems over the token counts Ks share ONE grouped launch?  Only the item-list kernel cuts each problem's own K range: the
+    counts must allow its 8-row staging pieces and the kernel must be the measured choice for every one of them (wgrad_group_kernel);
+    otherwise the caller launches one group per token count"""
+    import os
+    e = os.environ.get("VTP_GEMM4W_TN")
+    if e == "0" or any(k % 8 for k in Ks):
+        return False
+    return e == "1" or min(Ks) >= W4_TN_MIN_SLICE
 
 
 def wgrad_group_uniform_items(ntiles: int, Ktok: int, splits: int):
@@ -288,17 +331,19 @@ class WgradGroup:
         self.table = self.part = self.ticket = None
         self._uniform = {}  # splits -> (items, nitems, slots): uniform lists of a forced launch(kernel=1)
 
-    def add(self, dy, x, gw, gb, N: int, K: int, swiglu_h: int = 0, accumulate: bool = True):
+    def add(self, dy, x, gw, gb, N: int, K: int, swiglu_h: int = 0, accumulate: bool = True, Ktok: int = None):
         """dy bf16 [Ktok, N] (row stride dy.stride(0)), x bf16 [Ktok, K], gw f32 [N * K], gb f32 [N] or None (bias gradient =
         column sums of dy, fused).  swiglu_h: dy's columns are the 8|8-interleaved w1|w2 pre-activation gradients; the rows of gw
-        (and gb) are w1's H rows followed by w2's."""
+        (and gb) are w1's H rows followed by w2's.  Ktok: token rows of THIS problem when they differ from the group's (item-list
+        kernel only: finalize() refuses a mixed group it cannot run there)."""
         # limits of BOTH grouped kernels (16-B staging pieces, clamped tail columns): checked here because the kernels read the records
         # from device memory and cannot refuse them (ADVICE r4) -- e.g. ffn_layer="mlp" with an odd int(D * ratio) takes the per-layer path
         if N % 8 or K % 8 or dy.stride(0) % 8 or x.stride(0) % 8 or N < 8 or K < 8:
             raise ValueError(f"WgradGroup.add: N = {N}, K = {K} and the leading dimensions ({dy.stride(0)}, {x.stride(0)}) must be multiples "
                              "of 8 (use the per-layer weight-gradient path: linear_bwd without `defer`)")
         self.rows.append([dy.data_ptr(), x.data_ptr(), gw.data_ptr(), 0 if gb is None else gb.data_ptr(), dy.stride(0), x.stride(0), K,
-                          N, K, -1 if swiglu_h else 0, swiglu_h, self.ntiles, int(accumulate), 0, 0, 0])
+                          N, K, -1 if swiglu_h else 0, swiglu_h, self.ntiles, int(accumulate), 0 if Ktok is None or int(Ktok) == self.Ktok else int(Ktok),
+                          0, 0])
         self.ntiles += ((N + 255) // 256) * ((K + 255) // 256)
         self.keep += [dy, x, gw, gb]
 
@@ -307,12 +352,21 @@ class WgradGroup:
         the groups that never run concurrently (one partial-sum / ticket buffer for all of them)."""
         import torch
         assert 1 <= len(self.rows) <= 8
-        if not wgrad_group_fits(self.Ktok, max(max(r[4], r[5]) for r in self.rows)):
+        Ks = [r[13] or self.Ktok for r in self.rows]
+        self.mixed = len(set(Ks)) > 1
+        if not self.mixed and Ks[0] != self.Ktok:  # one count after all: it is the group's (the uniform-grid kernel reads only that)
+            self.Ktok = Ks[0]
+            for r in self.rows:
+                r[13] = 0
+        if self.mixed and any(k % 8 or k < 8 for k in Ks):
+            raise ValueError(f"WgradGroup: problems over different token counts {Ks} need multiples of 8 (the item-list kernel); "
+                             "launch one group per token count")
+        if not all(wgrad_group_fits(k, max(r[4], r[5])) for k, r in zip(Ks, self.rows)):
             raise ValueError("WgradGroup: token rows x leading dimension exceed the 32-bit staging offsets of vtp_gemm_tn_grouped; "
                              "use the per-layer weight-gradient path (linear_bwd without `defer`)")
         _, self.splits = wgrad_group_splits(self.ntiles, self.Ktok)
         self.table = torch.tensor(self.rows, dtype=torch.int64, device=device)
-        self.kernel = wgrad_group_kernel(self.ntiles, self.splits, self.Ktok)
+        self.kernel = 1 if self.mixed else wgrad_group_kernel(self.ntiles, self.splits, self.Ktok)
         self.items, self.nitems, self.slots = None, None, self.splits
         if self.kernel == 1:  # uneven cut: the tiles with bias-gradient work get one slice more (wgrad_group_items)
             items, self.slots = wgrad_group_items(self.rows, self.Ktok, self.splits)
@@ -334,6 +388,8 @@ class WgradGroup:
         current self.splits written as a list -- None = the measured choice made by finalize() (ops.wgrad_group_kernel)"""
         if kernel is None:
             kernel = self.kernel
+        if kernel == 0 and self.mixed:
+            raise ValueError("WgradGroup.launch: the 8-phase kernel takes one token count for every problem")
         if kernel == 0:
             _lib.check(_lib_().vtp_gemm_tn_grouped(_p(self.table), len(self.rows), self.ntiles, self.Ktok, self.splits, _p(self.part),
                                                    _p(self.ticket), _s()), "vtp_gemm_tn_grouped")
@@ -366,6 +422,22 @@ def gather_image_rows(src, idx, dst, dst_bf16, n_img, N, D, scale=1.0):
 def scatter_image_rows(src, idx, dst, n_img, N, D, alpha=1.0, accumulate=True):
     _lib.check(_lib_().vtp_scatter_image_rows(_p(src), _p(idx), _p(dst), n_img, N, D, alpha, int(accumulate), _s()),
                "vtp_scatter_image_rows")
+
+
+def gather_tail_rows(o, x, idx, o_c, x_c, T, L, M, D):
+    """compact rows of the last block's tail: o_c bf16 / x_c f32 [L + T, D] = rows [0, L) of o / x [M, D] followed by rows L + idx[t]
+    (idx int32 [T] on the device, -1: an all-zero row); either pair may be None"""
+    _lib.check(_lib_().vtp_gather_tail_rows(_p(o), _p(x), _p(idx), _p(o_c), _p(x_c), T, L, M, D, _s()), "vtp_gather_tail_rows")
+
+
+def tail_row_map(idx, row_map, T, L, M):
+    """row_map int32 [M]: full row -> compact row of gather_tail_rows (-1: no compact row reads it), built on the device"""
+    _lib.check(_lib_().vtp_tail_row_map(_p(idx), _p(row_map), T, L, M, _s()), "vtp_tail_row_map")
+
+
+def expand_rows_bf16(src, row_map, dst, M, Mc, D):
+    """dst bf16 [M, D]: row r = src[row_map[r]] (src [Mc, D]) or zero where row_map[r] < 0 -- one pass, no fill + scatter"""
+    _lib.check(_lib_().vtp_expand_rows_bf16(_p(src), _p(row_map), _p(dst), M, Mc, D, _s()), "vtp_expand_rows_bf16")
 
 
 def layerscale_wgrad(G, W, bias, colsum, gamma, dW, db, dgamma, N, K):

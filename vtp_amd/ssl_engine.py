@@ -152,5 +152,31 @@ def build_ssl_indices(masks: np.ndarray, B: int, hw: int, n_local: int, hw_local
     t0[m0:m0 + n_masked] = 2 * B + np.arange(n_masked)
     w[m0:m0 + n_masked] = ibot_weight * mw / B
     student_global_src = np.concatenate([np.arange(2 * B, dtype=np.int32) * N, masked_rows, pad])
-    return dict(n_masked=n_masked, Tm=Tm, Ts=Ts, teacher_src=teacher_src, student_local_src=local_src,
-                student_global_src=student_global_src, t0=t0, t1=t1, w=w)
+    out = dict(n_masked=n_masked, Tm=Tm, Ts=Ts, teacher_src=teacher_src, student_local_src=local_src,
+               student_global_src=student_global_src, t0=t0, t1=t1, w=w)
+    out.update(tail_row_plan(out, 2 * B * N))
+    return out
+
+
+def tail_row_plan(plan, global_rows: int):
+    """Row plan of the trunk's last block (engine.Stack.forward, `tail`): the token rows the SSL head reads, in the head's own order
+    [local cls | global cls | masked patches padded to Tm], as row numbers of the student's list forward RELATIVE to its first SSL row
+    (the global crops' first row; the local crops follow `global_rows` later).  The lead items in front stay a contiguous prefix, so the
+    plan does not depend on them: compact row L + t = full row L + student_tail_src[t].  Padding stays -1.
+      student_tail_src  int32 [Ts]   rows the head reads (relative), -1 = padding
+      student_tail_keep int32 [Ts]   t where the entry is a row, -1 where it is padding: the head's gather / the scatter of its input
+                                     gradient over the compact tail (padded rows reach the head as zeros and send nothing back)
+      teacher_keep      int32 [Tt]   the same for teacher_src (which is the teacher's plan as it is: L = 0)"""
+    tail = np.concatenate([np.asarray(plan["student_local_src"], np.int32) + np.int32(global_rows),
+                           plan["student_global_src"]]).astype(np.int32)
+    keep = lambda src: np.where(src >= 0, np.arange(src.shape[0]), -1).astype(np.int32)
+    return dict(student_tail_src=tail, student_tail_keep=keep(tail), teacher_keep=keep(plan["teacher_src"]))
+
+
+def tail_row_map(tail_src, L: int, M: int):
+    """host restatement of the device row map (ops.tail_row_map): int32 [M], full row -> compact row, -1 where no compact row reads it"""
+    m = np.full(M, -1, np.int32)
+    m[:L] = np.arange(L, dtype=np.int32)
+    t = np.flatnonzero(np.asarray(tail_src) >= 0)
+    m[L + np.asarray(tail_src)[t]] = L + t
+    return m

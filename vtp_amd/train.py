@@ -669,7 +669,8 @@ class VTPTrainer:
         into the trunk's d_xnf rows.  The trunk backward itself is run once by the caller, over all items.  Returns the
         ssl_forward() dict."""
         from .vtp import ssl_forward
-        out = ssl_forward(self.model, P["global"], P["local"], P["masks"], P["plan"], P["dev"], train=True, lead_images=lead_images)
+        out = ssl_forward(self.model, P["global"], P["local"], P["masks"], P["plan"], P["dev"], train=True, lead_images=lead_images,
+                          tail_rows="student_tail_src" in P["dev"])
         self._zero_join()  # the gradient buffer was zeroed under the forward passes; the head backward below is its first writer
         if not (self.head_overlap and not self.collectives and OVERLAP.enabled):
             yield from self._ssl_tail(out, P)
@@ -743,6 +744,10 @@ class VTPTrainer:
         d_xnf = self.trunk.d_xnf_buffer(ctx)
         if zero_dxnf:
             d_xnf.zero_()
+        if out["tail"] is not None:
+            # tail rows: d_xnf holds the lead items' rows and then the head's own, in the head's order -- a copy (padding rows: zeros)
+            ops.gather_token_rows(dX, P["dev"]["student_tail_keep"], d_xnf[out["tail"]:], Ts, D)
+            return
         seg_g, seg_l = ctx.segs[-2], ctx.segs[-1]
         ops.scatter_token_rows(dX, P["dev"]["student_local_src"], d_xnf[seg_l.row0:], nl, D)
         ops.scatter_token_rows(dX[nl:], P["dev"]["student_global_src"], d_xnf[seg_g.row0:], Ts - nl, D)
@@ -815,7 +820,9 @@ class VTPTrainer:
         # one pinned, non-blocking upload for every per-step array (index plan + masks): the host never waits for the GPU here
         if self._stager is None:
             self._stager = HostStager(self.store.device)
-        arrays = {k: plan[k].astype(np.int32, copy=False) for k in ("teacher_src", "student_local_src", "student_global_src", "t0", "t1")}
+        from .vtp import TAIL_KEYS
+        arrays = {k: plan[k].astype(np.int32, copy=False)
+                  for k in ("teacher_src", "student_local_src", "student_global_src", "t0", "t1") + TAIL_KEYS}
         arrays["w"] = plan["w"].astype(np.float32, copy=False)
         arrays["n_masked_i"] = np.array([plan["n_masked"]], np.int32)
         arrays["n_masked_f"] = np.array([float(plan["n_masked"])], np.float32)

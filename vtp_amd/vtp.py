@@ -242,9 +242,12 @@ def _range(st, prefix):
     return lo, hi
 
 
+TAIL_KEYS = ("student_tail_src", "student_tail_keep", "teacher_keep")  # ssl_engine.tail_row_plan
+
+
 def plan_to_device(plan, device):
     """int32 / f32 index tensors of one SSL batch on the device (done outside any graph capture)."""
-    d = {k: torch.as_tensor(plan[k], device=device) for k in ("teacher_src", "student_local_src", "student_global_src", "t0", "t1")}
+    d = {k: torch.as_tensor(plan[k], device=device) for k in ("teacher_src", "student_local_src", "student_global_src", "t0", "t1") + TAIL_KEYS}
     d["w"] = torch.as_tensor(plan["w"], device=device)
     # the masked-token count travels in device memory: kernels read it there, so one captured graph serves every mask draw
     # that fits the same padded buffers
@@ -254,12 +257,16 @@ def plan_to_device(plan, device):
 
 
 def ssl_forward(model: "VTP", global_crops, local_crops, masks_u8, plan, dev_plan=None, train: bool = False,
-                lead_images=None):
+                lead_images=None, tail_rows: bool = False):
     """Teacher + student forward of one SSL batch (vtp.py:410-484).  Returns a dict with the head logits and the
     context the backward needs.  masks_u8: uint8 [2B, hw] on the device; plan: build_ssl_indices() output.
     The student's passes (masked global crops, local crops and -- when `lead_images` is given -- the clean images of the
     rec / clip objectives, which use the same trunk weights) go through the trunk as ONE list forward (item order:
-    lead, global, local)."""
+    lead, global, local).
+    tail_rows: the last block of both trunks runs its row-wise half only on the rows something reads (ssl_engine.tail_row_plan): the
+    lead items' rows and the head's own for the student, teacher_src for the teacher.  out["xnf"] then holds those rows only (the lead
+    items first, at their usual places) and out["tail"] is the number of rows in front of the head's.  Each trunk takes the plan where
+    its pass allows one (TrunkEngine.tail_rows_ok) and the full path otherwise."""
     st = model._store
     B2 = global_crops.shape[0]
     hw = (global_crops.shape[-2] // 16) * (global_crops.shape[-1] // 16)
@@ -280,9 +287,17 @@ def ssl_forward(model: "VTP", global_crops, local_crops, masks_u8, plan, dev_pla
     Dh = model.dino_cfg["in_dim"]
     bott = Dh != D
 
+    t_tail = tail_rows and model._t_trunk.tail_rows_ok(False)
+    s_tail = tail_rows and model._trunk.tail_rows_ok(train)
+
     def teacher():
-        xnf_t = model._t_trunk.forward(global_crops, train=False, tag="teacher", rope_aug=train)  # (teacher_trunk is in training mode too)
-        ops.gather_token_rows(xnf_t, idx["teacher_src"], Xt, Tt, D)
+        if t_tail:  # the compact rows ARE the head's, in its order: the gather only blanks the padding
+            xnf_t = model._t_trunk.forward_list([(global_crops, None)], train=False, tag="teacher", rope_aug=train,
+                                                tail=(idx["teacher_src"], Tt, 0))
+            ops.gather_token_rows(xnf_t, idx["teacher_keep"], Xt, Tt, D)
+        else:
+            xnf_t = model._t_trunk.forward(global_crops, train=False, tag="teacher", rope_aug=train)  # (teacher_trunk is in training mode too)
+            ops.gather_token_rows(xnf_t, idx["teacher_src"], Xt, Tt, D)
         Ht = model._t_trunk.bott_rows(Xt, Tt, ws.get("Zt", (Tt, Dh), BF)) if bott else Xt
         return model._t_head.forward(Ht, Tt, tag="teacher")[0]
 
@@ -297,18 +312,24 @@ def ssl_forward(model: "VTP", global_crops, local_crops, masks_u8, plan, dev_pla
     # lead_images: one tensor, or a list of tensors (separate clip / reconstruction inputs, vtp.py:323-338): one list item each
     leads = [] if lead_images is None else (list(lead_images) if isinstance(lead_images, (list, tuple)) else [lead_images])
     items = [(im, None) for im in leads] + [(global_crops, masks_u8), (local_crops, None)]
-    xnf = model._trunk.forward_list(items, train=train, tag="ssl")
+    lead_rows = sum(im.shape[0] * ((im.shape[-2] // 16) * (im.shape[-1] // 16) + 1) for im in leads)
+    xnf = model._trunk.forward_list(items, train=train, tag="ssl", tail=(idx["student_tail_src"], Ts, lead_rows) if s_tail else None)
     ctx = model._trunk.ctx()
     seg_g, seg_l = ctx.segs[-2], ctx.segs[-1]
+    assert seg_g.row0 == lead_rows
     nl = int(plan["student_local_src"].shape[0])
     Xs = ws.get("Xs", (Ts, D), BF)
-    ops.gather_token_rows(xnf[seg_l.row0:], idx["student_local_src"], Xs, nl, D)
-    ops.gather_token_rows(xnf[seg_g.row0:], idx["student_global_src"], Xs[nl:], Ts - nl, D)
+    if s_tail:
+        ops.gather_token_rows(xnf[lead_rows:], idx["student_tail_keep"], Xs, Ts, D)
+    else:
+        ops.gather_token_rows(xnf[seg_l.row0:], idx["student_local_src"], Xs, nl, D)
+        ops.gather_token_rows(xnf[seg_g.row0:], idx["student_global_src"], Xs[nl:], Ts - nl, D)
     Hs = model._trunk.bott_rows(Xs, Ts, ws.get("Zs", (Ts, Dh), BF)) if bott else Xs  # the head's input rows
     s_logits, head_ctx = model._head.forward(Hs, Ts, tag="student")
     OVERLAP.join()  # teacher logits complete
     return dict(teacher_logits=t_logits, student_logits=s_logits, head_ctx=head_ctx, ctx=ctx, xnf=xnf, idx=idx,
-                Xs=Xs, Hs=Hs, bott=bott, student_global_cls=Hs[nl:nl + B2], Tt=Tt, Ts=Ts, Tm=Tm, nl=nl, B2=B2, N=N, ws=ws)
+                Xs=Xs, Hs=Hs, bott=bott, student_global_cls=Hs[nl:nl + B2], Tt=Tt, Ts=Ts, Tm=Tm, nl=nl, B2=B2, N=N, ws=ws,
+                tail=lead_rows if s_tail else None)
 
 
 def ssl_head_input_bwd(model: "VTP", out, dH):
