@@ -643,7 +643,7 @@ def test_gemm_tn_remaps_and_colsum():
 
 
 # ----------------------------------------------------------------------------------------------------------- fused qkv + RoPE
-@pytest.mark.parametrize("cfg", [-1, 0, 4, 5, 8])
+@pytest.mark.parametrize("cfg", [-1, 0, 3, 4, 5, 7, 8, 21])
 def test_gemm_qkv_rope_bit_identical_to_gemm_then_rope(cfg):
     """vtp_gemm_qkv_rope (apply_rope in the GEMM epilogue; list forward: two resolutions + cls prefix in ONE launch) must be
     bit-identical to vtp_gemm_nt followed by vtp_rope_qk per segment -- for every tile configuration that can run it."""
