@@ -462,6 +462,27 @@ int vtp_maxpool2_bwd(const void* Y, const void* dP, const void* tap, void* dY, i
 int vtp_lpips_tap(const void* f0, const void* f1, const float* w, float* val, void* df0, int n, int H, int W, int C,
                   float gscale, void* stream);
 
+/* ---- linear probing (probe.hip; reference: tools/test_linear_probing_hf.py) ----------------------------------------------
+ * Every classifier of a feature group in one fused step, fp32 in and out on the f32-input MFMA (the reference keeps this
+ * arithmetic in fp32, outside its autocast context).  Heads are stacked: W f32 [N = H*C, K] row-major, bias f32 [N].
+ * K % 4 == 0, ldx % 4 == 0, ldx >= K, X and W 16-byte aligned (X is a column slice of a wider matrix); B, C >= 1 arbitrary.
+ *
+ * logits[b, n] = sum_k X[b, k] * W[n, k] + bias[n]   (LinearClassifier.forward, :164-170, for every head of the group at once) */
+int vtp_probe_logits(const float* X, int ldx, const float* W, const float* bias, float* logits, int ldl, int B, int N, int K,
+                     void* stream);
+/* per head h < H and row b < B: CrossEntropyLoss(mean) of logits[b, h*C : (h+1)*C] against labels[b] in [0, C)  (:285, :489)
+ *   loss[h]    += sum_b CE * inv_rows
+ *   correct[h] += #{b : argmax == labels[b]}, lowest index on ties (torch.argmax; :327-328)   -- NULL: not counted
+ *   dlogits[b, h*C + c] = (softmax - onehot) * inv_rows  (row stride ldl)                      -- NULL: evaluation, not written */
+int vtp_probe_ce(const float* logits, int ldl, const long* labels, int B, int H, int C, float inv_rows, float* loss, int* correct,
+                 float* dlogits, void* stream);
+/* torch.optim.SGD(momentum, weight_decay 0, dampening 0) step of every head from dlogits and X; dW is never stored (:487, :288-290):
+ *   dW[n, k] = sum_b dlogits[b, n] * X[b, k];  db[n] = sum_b dlogits[b, n]
+ *   mW = fmaf(momentum, mW, dW);  W = fmaf(-lr[n / C], mW, W)      (the same for mb / bias; lr f32 [H] in DEVICE memory)
+ * Zeroed momentum buffers make the first step torch's (buf = grad).  Each element of W, mW, bias, mb has exactly one writer. */
+int vtp_probe_sgd(float* W, float* bias, float* mW, float* mb, const float* dlogits, int ldl, const float* X, int ldx, const float* lr,
+                  int B, int H, int C, int K, float momentum, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

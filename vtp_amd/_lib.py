@@ -115,6 +115,9 @@ SIGNATURES = {
     "vtp_koleo": [_P, _P, _P, _P, _I, _I, _F, _F, _P],
     "vtp_sinkhorn_knopp": [_P, _F, _P, _P, _P, _P, _I, _I, _F, _P, _P, _I, _I, _P],
     "vtp_clip_loss": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "vtp_probe_logits": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P],  # X ldx W bias logits ldl B N K stream
+    "vtp_probe_ce": [_P, _I, _P, _I, _I, _I, _F, _P, _P, _P, _P],  # logits ldl labels B H C inv_rows loss correct dlogits stream
+    "vtp_probe_sgd": [_P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _F, _P],  # W bias mW mb dlogits ldl X ldx lr B H C K momentum stream
 }
 
 _lib = None

@@ -1,0 +1,242 @@
+// Linear probing (reference: tools/test_linear_probing_hf.py): every classifier of a feature group as ONE fused fp32 step --
+//   vtp_probe_logits : logits = X W_all^T + bias          (LinearClassifier.forward :164-170 for all heads of the group)
+//   vtp_probe_ce     : CrossEntropyLoss(mean) per head, top-1 counts, dlogits                             (:285, :327-328)
+//   vtp_probe_sgd    : torch.optim.SGD(momentum) step of every head; dW lives in the MFMA accumulators only     (:487, :288-290)
+// The reference does this arithmetic in fp32 outside its autocast context, so all three kernels are fp32 in and out on the
+// f32-input MFMA v_mfma_f32_32x32x2_f32: bit-for-bit a k-ordered fmaf chain per output element (one rounding per product).
+//   operand maps (one f32 VGPR each): lane l holds A[i = l & 31][k = l >> 5] and B[k = l >> 5][j = l & 31];
+//   C/D: column j = l & 31, row i = (reg & 3) + 8 (reg >> 2) + 4 (l >> 5), reg in [0, 16).
+// Every output element has exactly one writer and a reduction order that depends on neither its tile nor its position in it: two
+// heads with equal parameters stay bit-identical, and so do data-parallel replicas that run the same full-batch step.
+#include "common.h"
+#include "vtp_hip.h"
+
+#include <limits.h>
+
+namespace vtp {
+
+__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ int acc_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
+
+// ---------------------------------------------------------------------------------------------------------------- logits
+// One wave = 64 rows x 32 columns of the output over the whole of K; no LDS, no barrier.  Waves that share a column strip sit
+// next to each other (the row pair is the fast task index), so a W strip comes from HBM once and X (<= 2 MB) from L2.
+// A k unit is 32 wide: per 8-wide chunk c the lane half h = l >> 5 loads the 16 bytes at k0 + 8 c + 4 h of its row and the four
+// elements feed four MFMAs -- A and B use the same (h, element) -> k map, so the product only permutes the order of the sum.
+// Chunks past K load zeros (K % 4 == 0 keeps a 16-byte load inside its row).  The next unit is loaded before the current one's
+// 32 MFMAs (2048 cycles) are issued: one wave per SIMD has to cover the HBM latency by itself.
+struct ProbeUnit {
+  f32x4 w[4], x0[4], x1[4];
+};
+
+__device__ __forceinline__ void probe_load_unit(ProbeUnit& u, const float* __restrict__ wp, const float* __restrict__ xp0,
+                                                const float* __restrict__ xp1, int k0, int half, int K) {
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const int k = k0 + 8 * c + 4 * half;
+    const int kc = k < K ? k : K - 4;
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 w = *(const f32x4*)(wp + kc), a = *(const f32x4*)(xp0 + kc), b = *(const f32x4*)(xp1 + kc);
+    u.w[c] = k < K ? w : z;
+    u.x0[c] = k < K ? a : z;
+    u.x1[c] = k < K ? b : z;
+  }
+}
+
+__global__ __launch_bounds__(256) void probe_logits_kernel(const float* __restrict__ X, int ldx, const float* __restrict__ W,
+                                                          const float* __restrict__ bias, float* __restrict__ logits, int ldl, int B,
+                                                          int N, int K, int row_pairs, int tasks) {
+  const int lane = threadIdx.x & 63, r = lane & 31, half = lane >> 5;
+  const int task = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (task >= tasks) return;
+  const int n0 = (task / row_pairs) * 32, b0 = (task % row_pairs) * 64;
+  const int n = n0 + r, nc = n < N ? n : N - 1;
+  const int ba = b0 + r, bb = b0 + 32 + r;
+  const float* wp = W + (long)nc * K;
+  const float* xp0 = X + (long)(ba < B ? ba : B - 1) * ldx;  // rows past B: a valid row, results never stored
+  const float* xp1 = X + (long)(bb < B ? bb : B - 1) * ldx;
+  const float bn = bias[nc];
+  f32x16 acc0, acc1;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acc0[i] = acc1[i] = bn;  // the bias opens the chain: K + 1 roundings per element
+  ProbeUnit cur, nxt;
+  probe_load_unit(cur, wp, xp0, xp1, 0, half, K);
+  for (int k0 = 0; k0 < K; k0 += 32) {
+    probe_load_unit(nxt, wp, xp0, xp1, k0 + 32, half, K);  // past K: clamped addresses, zeros (never used after the last unit)
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        acc0 = mfma32(cur.x0[c][e], cur.w[c][e], acc0);
+        acc1 = mfma32(cur.x1[c][e], cur.w[c][e], acc1);
+      }
+    cur = nxt;
+  }
+  if (n >= N) return;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int b = b0 + acc_row(i, half);
+    if (b < B) logits[(long)b * ldl + n] = acc0[i];
+    if (b + 32 < B) logits[(long)(b + 32) * ldl + n] = acc1[i];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- cross-entropy
+// One workgroup per (row b, head h).  Three passes over the C logits of the row (L2-resident): maximum with its lowest index,
+// sum of exponentials, gradient.  Reductions run in a fixed order, so dlogits does not depend on the launch.
+__global__ __launch_bounds__(256) void probe_ce_kernel(const float* __restrict__ logits, int ldl, const long* __restrict__ labels,
+                                                      int C, float inv_rows, float* __restrict__ loss, int* __restrict__ correct,
+                                                      float* __restrict__ dlogits) {
+  __shared__ float red_v[4];
+  __shared__ int red_i[4];
+  __shared__ float red_s[4];
+  const int b = blockIdx.x, h = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const float* z = logits + (long)b * ldl + (long)h * C;
+  float m = -INFINITY;
+  int mi = INT_MAX;
+  for (int c = tid; c < C; c += 256) {
+    const float v = z[c];
+    if (v > m || mi == INT_MAX) m = v, mi = c;  // strict >: the first (lowest) index of a thread's maximum stays
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float om = __shfl_xor(m, o, 64);
+    const int oi = __shfl_xor(mi, o, 64);
+    if (oi != INT_MAX && (mi == INT_MAX || om > m || (om == m && oi < mi))) m = om, mi = oi;
+  }
+  if (lane == 0) red_v[w] = m, red_i[w] = mi;
+  __syncthreads();
+  m = red_v[0], mi = red_i[0];
+#pragma unroll
+  for (int i = 1; i < 4; ++i) {
+    const float om = red_v[i];
+    const int oi = red_i[i];
+    if (oi != INT_MAX && (mi == INT_MAX || om > m || (om == m && oi < mi))) m = om, mi = oi;
+  }
+  float s = 0.f;
+  for (int c = tid; c < C; c += 256) s += expf(z[c] - m);
+  s = block_sum<4>(s, red_s);
+  const long lab = labels[b];
+  const bool lab_ok = lab >= 0 && lab < C;  // labels are class indices in [0, C); anything else contributes no target term
+  if (tid == 0) {
+    const float zl = lab_ok ? z[lab] : m;
+    atomicAdd(loss + h, (logf(s) - (zl - m)) * inv_rows);
+    if (correct && lab_ok && mi == (int)lab) atomicAdd(correct + h, 1);
+  }
+  if (!dlogits) return;
+  float* d = dlogits + (long)b * ldl + (long)h * C;
+  const float inv_s = 1.f / s;
+  for (int c = tid; c < C; c += 256) {
+    const float p = expf(z[c] - m) * inv_s;
+    d[c] = ((lab_ok && c == (int)lab) ? p - 1.f : p) * inv_rows;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- SGD step
+// One wave = a 64 (rows n) x 64 (columns k) tile of W: dW = dlogits^T X over the batch in four independent 32x32 accumulators
+// (A = dlogits^T: lane l reads dlogits[b + (l >> 5)][n0 + (l & 31)], B = X[b + (l >> 5)][k0 + (l & 31)], both 128-byte rows from L2),
+// then one read-modify-write of mW and W in the accumulator layout -- 16 bytes of HBM traffic per parameter, dW never stored.
+// Rows of the batch past B are zeros (the MFMA k step is 2).  The waves of k tile 0 also form db and update bias / mb.
+// The learning rate is looked up per output row n / C: 1000 classes are no multiple of 64, so a tile straddles heads.
+__global__ __launch_bounds__(256) void probe_sgd_kernel(float* __restrict__ W, float* __restrict__ bias, float* __restrict__ mW,
+                                                       float* __restrict__ mb, const float* __restrict__ dl, int ldl,
+                                                       const float* __restrict__ X, int ldx, const float* __restrict__ lr, int B, int N,
+                                                       int C, int K, float momentum, int k_tiles, int tasks) {
+  const int lane = threadIdx.x & 63, r = lane & 31, half = lane >> 5;
+  const int task = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (task >= tasks) return;
+  const int n0 = (task / k_tiles) * 64, k0 = (task % k_tiles) * 64;
+  const int na = n0 + r, nb = n0 + 32 + r, ka = k0 + r, kb = k0 + 32 + r;
+  const float* dpa = dl + (na < N ? na : N - 1);
+  const float* dpb = dl + (nb < N ? nb : N - 1);
+  const float* xpa = X + (ka < K ? ka : K - 1);
+  const float* xpb = X + (kb < K ? kb : K - 1);
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acc[0][0][i] = acc[0][1][i] = acc[1][0][i] = acc[1][1][i] = 0.f;
+#pragma unroll 4
+  for (int b0 = 0; b0 < B; b0 += 2) {
+    const int b = b0 + half;
+    const long bc = b < B ? b : B - 1;
+    float a0 = dpa[bc * ldl], a1 = dpb[bc * ldl], x0 = xpa[bc * ldx], x1 = xpb[bc * ldx];
+    a0 = (b < B && na < N) ? a0 : 0.f;
+    a1 = (b < B && nb < N) ? a1 : 0.f;
+    x0 = (b < B && ka < K) ? x0 : 0.f;
+    x1 = (b < B && kb < K) ? x1 : 0.f;
+    acc[0][0] = mfma32(a0, x0, acc[0][0]);
+    acc[0][1] = mfma32(a0, x1, acc[0][1]);
+    acc[1][0] = mfma32(a1, x0, acc[1][0]);
+    acc[1][1] = mfma32(a1, x1, acc[1][1]);
+  }
+#pragma unroll
+  for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int n = n0 + 32 * ti + acc_row(i, half);
+      if (n >= N) continue;
+      const float nlr = -lr[n / C];
+#pragma unroll
+      for (int tj = 0; tj < 2; ++tj) {
+        const int k = k0 + 32 * tj + r;
+        if (k >= K) continue;
+        const long idx = (long)n * K + k;
+        const float m = fmaf(momentum, mW[idx], acc[ti][tj][i]);
+        mW[idx] = m;
+        W[idx] = fmaf(nlr, m, W[idx]);
+      }
+    }
+  if (k0 == 0) {
+    const int n = n0 + lane;
+    if (n < N) {
+      float db = 0.f;
+      for (int b = 0; b < B; ++b) db += dl[(long)b * ldl + n];
+      const float m = fmaf(momentum, mb[n], db);
+      mb[n] = m;
+      bias[n] = fmaf(-lr[n / C], m, bias[n]);
+    }
+  }
+}
+
+}  // namespace vtp
+
+using namespace vtp;
+
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+extern "C" int vtp_probe_logits(const float* X, int ldx, const float* W, const float* bias, float* logits, int ldl, int B, int N,
+                                int K, void* stream) {
+  VTP_REQUIRE(X && W && bias && logits, "vtp_probe_logits: null pointer");
+  VTP_REQUIRE(B >= 1 && N >= 1 && K >= 4 && K % 4 == 0, "vtp_probe_logits: bad shape (B, N >= 1, K %% 4 == 0)");
+  VTP_REQUIRE(ldx >= K && ldx % 4 == 0 && ldl >= N, "vtp_probe_logits: bad leading dimension (ldx >= K, ldx %% 4 == 0, ldl >= N)");
+  VTP_REQUIRE(aligned16(X) && aligned16(W), "vtp_probe_logits: X and W must be 16-byte aligned");
+  const long row_pairs = cdiv(B, 64), tasks = row_pairs * cdiv(N, 32);
+  VTP_REQUIRE(tasks <= INT_MAX, "vtp_probe_logits: too many tiles");
+  hipLaunchKernelGGL(probe_logits_kernel, dim3(cdiv(tasks, 4)), dim3(256), 0, (hipStream_t)stream, X, ldx, W, bias, logits, ldl, B, N,
+                     K, (int)row_pairs, (int)tasks);
+  return check_launch("probe_logits");
+}
+
+extern "C" int vtp_probe_ce(const float* logits, int ldl, const long* labels, int B, int H, int C, float inv_rows, float* loss,
+                            int* correct, float* dlogits, void* stream) {
+  VTP_REQUIRE(logits && labels && loss, "vtp_probe_ce: null pointer");
+  VTP_REQUIRE(B >= 1 && H >= 1 && H <= 65535 && C >= 1 && (long)H * C <= INT_MAX, "vtp_probe_ce: bad shape (B, H, C >= 1)");
+  VTP_REQUIRE(ldl >= (long)H * C, "vtp_probe_ce: bad leading dimension (ldl >= H * C)");
+  hipLaunchKernelGGL(probe_ce_kernel, dim3(B, H), dim3(256), 0, (hipStream_t)stream, logits, ldl, labels, C, inv_rows, loss, correct,
+                     dlogits);
+  return check_launch("probe_ce");
+}
+
+extern "C" int vtp_probe_sgd(float* W, float* bias, float* mW, float* mb, const float* dlogits, int ldl, const float* X, int ldx,
+                             const float* lr, int B, int H, int C, int K, float momentum, void* stream) {
+  VTP_REQUIRE(W && bias && mW && mb && dlogits && X && lr, "vtp_probe_sgd: null pointer");
+  VTP_REQUIRE(B >= 1 && H >= 1 && C >= 1 && (long)H * C <= INT_MAX && K >= 4 && K % 4 == 0,
+              "vtp_probe_sgd: bad shape (B, H, C >= 1, K %% 4 == 0)");
+  VTP_REQUIRE(ldx >= K && ldx % 4 == 0 && ldl >= (long)H * C,
+              "vtp_probe_sgd: bad leading dimension (ldx >= K, ldx %% 4 == 0, ldl >= H * C)");
+  const int N = H * C;
+  const long k_tiles = cdiv(K, 64), tasks = k_tiles * cdiv(N, 64);
+  VTP_REQUIRE(tasks <= INT_MAX, "vtp_probe_sgd: too many tiles");
+  hipLaunchKernelGGL(probe_sgd_kernel, dim3(cdiv(tasks, 4)), dim3(256), 0, (hipStream_t)stream, W, bias, mW, mb, dlogits, ldl, X, ldx,
+                     lr, B, N, C, K, momentum, (int)k_tiles, (int)tasks);
+  return check_launch("probe_sgd");
+}

@@ -730,3 +730,27 @@ def gemm_nt_fp8(a8, b8, c, *, M, N, K, alpha, lda=None, ldb=None, ldc=None, c2=N
     rp = (None, None, None, 0) if rope is None else rope
     _lib.check(_lib_().vtp_gemm_nt_fp8(_p(a8), lda, _p(b8), ldb, _p(c), ldc, _p(c2), ldc2, _p(bias), _p(resid), M, N, K, epi, float(alpha),
                                        _p(rp[0]), _p(rp[1]), _p(rp[2]), rp[3], _s()), "vtp_gemm_nt_fp8")
+
+
+def probe_logits(x, w, bias, logits, B, N, K):
+    """logits f32 [B, N] = x[B, K] @ w[N, K]^T + bias, exact fp32 (every head of a linear-probe feature group at once);
+    x may be a column slice of a wider matrix (row stride x.stride(0))"""
+    _lib.check(_lib_().vtp_probe_logits(_p(x), x.stride(0), _p(w), _p(bias), _p(logits), logits.stride(0), B, N, K, _s()),
+               "vtp_probe_logits")
+
+
+def probe_ce(logits, labels, B, H, C, inv_rows, loss, correct=None, dlogits=None):
+    """per-head mean cross-entropy (loss f32 [H] accumulated), top-1 counts (correct i32 [H] accumulated, optional) and
+    dlogits = (softmax - onehot) * inv_rows (optional: None = evaluation); labels int64 [B]"""
+    ldl = logits.stride(0)
+    if dlogits is not None and dlogits.stride(0) != ldl:
+        raise ValueError("probe_ce: dlogits must have the row stride of logits")
+    _lib.check(_lib_().vtp_probe_ce(_p(logits), ldl, _p(labels), B, H, C, inv_rows, _p(loss), _p(correct), _p(dlogits), _s()),
+               "vtp_probe_ce")
+
+
+def probe_sgd(w, bias, mw, mb, dlogits, x, lr, B, H, C, K, momentum):
+    """SGD-with-momentum step of all H heads (w [H*C, K], bias [H*C] and their momentum buffers, updated in place) from dlogits
+    [B, H*C] and x [B, K]; lr f32 [H] on the device, one rate per head"""
+    _lib.check(_lib_().vtp_probe_sgd(_p(w), _p(bias), _p(mw), _p(mb), _p(dlogits), dlogits.stride(0), _p(x), x.stride(0), _p(lr),
+                                     B, H, C, K, momentum, _s()), "vtp_probe_sgd")
