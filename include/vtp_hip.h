@@ -483,6 +483,29 @@ int vtp_probe_ce(const float* logits, int ldl, const long* labels, int B, int H,
 int vtp_probe_sgd(float* W, float* bias, float* mW, float* mb, const float* dlogits, int ldl, const float* X, int ldx, const float* lr,
                   int B, int H, int C, int K, float momentum, void* stream);
 
+/* ---- zero-shot classification (zeroshot.hip; reference: tools/test_zero_shot_hf.py at precision 'fp32') ------------------
+ * The tool's own arithmetic, fp32 in and out, products on the f32-input MFMA.  D % 4 == 0, leading dimensions % 4 == 0 and
+ * >= D, feat / F / Wt 16-byte aligned.  The classifier is kept as Wt f32 [C, D] (one row per class); the tool's [D, C]
+ * classifier is its transposed view.
+ *
+ * Wt[c] = normalize(mean_t feat[c*T + t]) : the sum runs over t = 0..T-1 in order and is divided by T, then the row is divided
+ * by max(||row||_2, eps) (F.normalize; :383-385).  An all-zero class gives a zero row.  Rows are independent of each other and
+ * of C, so class batches may fill one Wt call by call. */
+int vtp_zs_class_mean(const float* feat, int ldf, float* Wt, int ldw, int C, int T, int D, float eps, void* stream);
+/* z[b, c] = sum_k (scale * F[b, k]) * Wt[c, k] (the feature scaled and rounded first: (100.0 * f) @ classifier, :436; one
+ * sequential chain over k per element) and accuracy(z, targets, (1, 5)) (:312-316) in ONE launch, no host synchronisation:
+ *   rank[b] = #{c : z[b,c] > z[b,t]} + #{c < t : z[b,c] == z[b,t]}, t = targets[b] (the lower index wins a tie);
+ *             t outside [0, C) reads nothing, gets rank C and counts as a miss
+ *   counts    int64 [3]   += #{rank < 1}, #{rank < 5}, B
+ *   per_class int32 [2,C] += rows seen / top-1 hits per target class (targets in range only)        -- may be NULL
+ *   rank      int32 [B]                                                                              -- may be NULL
+ *   pred      int32 [B,5]  the five best classes by (logit descending, index ascending)              -- may be NULL
+ *   logits    f32 [B,C], row stride ldl: exactly the values the ranks were computed from             -- may be NULL
+ * counts may be NULL as well; a NULL output changes no other output.  B >= 1, C >= 5 (any size: a row block's logits are
+ * kept in LDS 1024 classes at a time).  Only integer atomics: counts and ranks are reproducible bit for bit. */
+int vtp_zs_topk(const float* F, int ldf, const float* Wt, int ldw, const long* targets, float scale, int B, int C, int D,
+                long* counts, int* per_class, int* rank, int* pred, float* logits, int ldl, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -118,6 +118,9 @@ SIGNATURES = {
     "vtp_probe_logits": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P],  # X ldx W bias logits ldl B N K stream
     "vtp_probe_ce": [_P, _I, _P, _I, _I, _I, _F, _P, _P, _P, _P],  # logits ldl labels B H C inv_rows loss correct dlogits stream
     "vtp_probe_sgd": [_P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _F, _P],  # W bias mW mb dlogits ldl X ldx lr B H C K momentum stream
+    "vtp_zs_class_mean": [_P, _I, _P, _I, _I, _I, _I, _F, _P],  # feat ldf Wt ldw C T D eps stream
+    # F ldf Wt ldw targets scale B C D counts per_class rank pred logits ldl stream
+    "vtp_zs_topk": [_P, _I, _P, _I, _P, _F, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P],
 }
 
 _lib = None

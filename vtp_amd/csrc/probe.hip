@@ -9,14 +9,12 @@
 // Every output element has exactly one writer and a reduction order that depends on neither its tile nor its position in it: two
 // heads with equal parameters stay bit-identical, and so do data-parallel replicas that run the same full-batch step.
 #include "common.h"
+#include "mfma_f32.h"
 #include "vtp_hip.h"
 
 #include <limits.h>
 
 namespace vtp {
-
-__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ int acc_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
 
 // ---------------------------------------------------------------------------------------------------------------- logits
 // One wave = 64 rows x 32 columns of the output over the whole of K; no LDS, no barrier.  Waves that share a column strip sit

@@ -754,3 +754,16 @@ def probe_sgd(w, bias, mw, mb, dlogits, x, lr, B, H, C, K, momentum):
     [B, H*C] and x [B, K]; lr f32 [H] on the device, one rate per head"""
     _lib.check(_lib_().vtp_probe_sgd(_p(w), _p(bias), _p(mw), _p(mb), _p(dlogits), dlogits.stride(0), _p(x), x.stride(0), _p(lr),
                                      B, H, C, K, momentum, _s()), "vtp_probe_sgd")
+
+
+def zs_class_mean(feat, wt, C, T, D, eps=1e-12):
+    """wt[c] f32 [C, D] = F.normalize(mean over t of feat[c * T + t]) (feat f32 [C * T, D], template t of class c in row c * T + t);
+    feat and wt may be row / column slices of wider matrices (row strides taken from the tensors)"""
+    _lib.check(_lib_().vtp_zs_class_mean(_p(feat), feat.stride(0), _p(wt), wt.stride(0), C, T, D, eps, _s()), "vtp_zs_class_mean")
+
+
+def zs_topk(f, wt, targets, scale, B, C, D, counts, per_class=None, rank=None, pred=None, logits=None):
+    """logits = (scale * f[B, D]) @ wt[C, D]^T and the top-1 / top-5 statistics of targets int64 [B] in one launch: counts int64 [3]
+    += (top-1 hits, top-5 hits, rows); optional per_class i32 [2, C] (accumulated), rank i32 [B], pred i32 [B, 5], logits f32 [B, C]"""
+    _lib.check(_lib_().vtp_zs_topk(_p(f), f.stride(0), _p(wt), wt.stride(0), _p(targets), scale, B, C, D, _p(counts), _p(per_class),
+                                   _p(rank), _p(pred), _p(logits), 0 if logits is None else logits.stride(0), _s()), "vtp_zs_topk")
