@@ -506,6 +506,32 @@ int vtp_zs_class_mean(const float* feat, int ldf, float* Wt, int ldw, int C, int
 int vtp_zs_topk(const float* F, int ldf, const float* Wt, int ldw, const long* targets, float scale, int B, int C, int D,
                 long* counts, int* per_class, int* rank, int* pred, float* logits, int ldl, void* stream);
 
+/* ---- reconstruction evaluation (recon_eval.hip; reference: tools/test_reconstruction_hf.py:360-409) -----------------------
+ * images / recon f32 [B,3,H,W], ImageNet-normalised as get_latents_decoded_images returns them; H, W >= 11, W % 4 == 0, both
+ * 16-byte aligned.  sub3 / div3: HOST float[3], fp32(-mean/std) and fp32(1/std) (transform_rev, :265-268).  Every output is
+ * formed from d = clamp((x - sub[c]) / div[c], 0, 1) (:371-376), a subtraction, an IEEE division and the clamp:
+ *   ref_u8 / rec_u8  uint8 [B,H,W,3] = (uint8) trunc(d * 255.0f), bit-identical to (:401-402)               -- may be NULL
+ *   ref_lp / rec_lp  f32 [B,3,H,W]   = d * 2 - 1, bit-identical to (:381-382)                                -- may be NULL
+ *   scratch          f64 [B, tiles, 2]: per tile of an image the sum of (o*255 - r*255)^2 over the pixels the tile owns (every
+ *                    pixel of the image has exactly one owner; :395-397) and the sum of the SSIM map over its window positions
+ * SSIM: 11x11 Gaussian window (sigma 1.5, sum 1), c1 = 1e-4, c2 = 9e-4, var = max(E[x^2] - mu^2, 0) for both variances, the
+ * covariance unclamped, ssim = ((2 mu_p mu_t + c1)(2 cov + c2)) / ((mu_p^2 + mu_t^2 + c1)(var_p + var_t + c2)) at each of the
+ * (H-10) x (W-10) window positions of each channel: StructuralSimilarityIndexMeasure(data_range=1.0), whose reflect-pad,
+ * convolution and crop is this valid convolution (:392).  Windowed sums in fp64.  No atomics: results repeat bit for bit.
+ * vtp_recon_scratch_doubles returns the number of doubles scratch must hold (2 * B * tiles), or -1. */
+int vtp_recon_scratch_doubles(long B, int H, int W);
+int vtp_recon_metrics(const float* images, const float* recon, long B, int H, int W, const float* sub3, const float* div3,
+                      void* ref_u8, void* rec_u8, float* ref_lp, float* rec_lp, double* scratch, long scratch_len, void* stream);
+/* One small launch after vtp_recon_metrics (and after LPIPS, if its values are passed): per image b, tiles summed in order,
+ *   psnr[b] = 20 log10(255 / sqrt(sse / (3 H W))), +inf when sse == 0 (calculate_psnr, :49-63);  ssim[b] = sum / (3 (H-10)(W-10))
+ *   sse[b]  (f64) the squared error itself                                                                    -- may be NULL
+ * and adds to acc, f64 [8] on the device (the tool averages PSNR over images, SSIM and LPIPS over batch means: :386, :392,
+ * :395-397, :428-430; both kinds of sum are kept):
+ *   acc[0] sum of psnr   acc[1] images   acc[2] images with sse == 0   acc[3] sum of ssim   acc[4] sum of per-batch mean ssim
+ *   acc[5] batches       acc[6] sum of per-batch mean lpips            acc[7] sum of lpips   (6, 7 only with lpips f32 [B]) */
+int vtp_recon_finalize(const double* scratch, long scratch_len, long B, int H, int W, float* psnr, float* ssim, double* sse,
+                       const float* lpips, double* acc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -121,6 +121,10 @@ SIGNATURES = {
     "vtp_zs_class_mean": [_P, _I, _P, _I, _I, _I, _I, _F, _P],  # feat ldf Wt ldw C T D eps stream
     # F ldf Wt ldw targets scale B C D counts per_class rank pred logits ldl stream
     "vtp_zs_topk": [_P, _I, _P, _I, _P, _F, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P],
+    "vtp_recon_scratch_doubles": [_L, _I, _I],  # B H W -> doubles of scratch, or -1
+    # images recon B H W sub3 div3 ref_u8 rec_u8 ref_lp rec_lp scratch scratch_len stream
+    "vtp_recon_metrics": [_P, _P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _L, _P],
+    "vtp_recon_finalize": [_P, _L, _L, _I, _I, _P, _P, _P, _P, _P, _P],  # scratch scratch_len B H W psnr ssim sse lpips acc stream
 }
 
 _lib = None

@@ -767,3 +767,28 @@ def zs_topk(f, wt, targets, scale, B, C, D, counts, per_class=None, rank=None, p
     += (top-1 hits, top-5 hits, rows); optional per_class i32 [2, C] (accumulated), rank i32 [B], pred i32 [B, 5], logits f32 [B, C]"""
     _lib.check(_lib_().vtp_zs_topk(_p(f), f.stride(0), _p(wt), wt.stride(0), _p(targets), scale, B, C, D, _p(counts), _p(per_class),
                                    _p(rank), _p(pred), _p(logits), 0 if logits is None else logits.stride(0), _s()), "vtp_zs_topk")
+
+
+def recon_scratch_size(B, H, W):
+    """number of f64 elements the scratch of recon_metrics / recon_finalize must hold for a [B, 3, H, W] batch (two per tile of
+    window positions); ValueError for a shape the kernels refuse (H or W below 11, W % 4 != 0, B < 1)"""
+    n = _lib_().vtp_recon_scratch_doubles(B, H, W)
+    if n < 0:
+        raise ValueError(_lib_().vtp_last_error().decode(errors="replace"))
+    return n
+
+
+def recon_metrics(images, recon, sub, div, scratch, ref_u8=None, rec_u8=None, ref_lp=None, rec_lp=None):
+    """one launch over images / recon f32 [B, 3, H, W] (contiguous): with d = clamp((x - sub[c]) / div[c], 0, 1), optional byte
+    images uint8 [B, H, W, 3] = trunc(d * 255) and LPIPS inputs f32 [B, 3, H, W] = d * 2 - 1, and the per-tile squared-error and
+    SSIM partials in scratch (f64, recon_scratch_size elements)"""
+    B, _, H, W = images.shape
+    _lib.check(_lib_().vtp_recon_metrics(_p(images), _p(recon), B, H, W, _f3(sub), _f3(div), _p(ref_u8), _p(rec_u8), _p(ref_lp),
+                                         _p(rec_lp), _p(scratch), scratch.numel(), _s()), "vtp_recon_metrics")
+
+
+def recon_finalize(scratch, B, H, W, psnr, ssim, acc, sse=None, lpips=None):
+    """psnr / ssim f32 [B] (and sse f64 [B]) from the partials of recon_metrics, tiles summed in a fixed order; acc f64 [8] +=
+    (sum psnr, images, images with sse == 0, sum ssim, sum of batch-mean ssim, batches, sum of batch-mean lpips, sum lpips)"""
+    _lib.check(_lib_().vtp_recon_finalize(_p(scratch), scratch.numel(), B, H, W, _p(psnr), _p(ssim), _p(sse), _p(lpips), _p(acc), _s()),
+               "vtp_recon_finalize")
