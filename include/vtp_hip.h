@@ -532,6 +532,25 @@ int vtp_recon_metrics(const float* images, const float* recon, long B, int H, in
 int vtp_recon_finalize(const double* scratch, long scratch_len, long B, int H, int W, float* psnr, float* ssim, double* sse,
                        const float* lpips, double* acc, void* stream);
 
+/* ---- SSL crops (augment.hip): the DINO multi-crop augmentation from decoded byte images, two launches, no host synchronisation
+ * src_u8 uint8 [B,Hs,Ws,3] (RGB, 4-byte aligned, Ws % 4 == 0) -> out f32 [N,3,S,S], N = views * B, crop n from image n % B
+ * (view-major).  table f32 [N,16] on the DEVICE, 16-byte aligned, one row per crop:
+ *   0..3 y0 x0 h w (the box)   4 flags (1 flip | 2 colour jitter | 4 grayscale | 8 solarize)
+ *   5..8 the jitter's operations in the order they run (0 brightness, 1 contrast, 2 saturation, 3 hue, -1 none)
+ *   9..12 the factors (brightness, contrast, saturation, hue)   13 sigma of the blur (<= 0: none)   14, 15 unused
+ * In fp32 on x = u8 / 255:  crop the box and resize it to S x S as F.interpolate(mode="bicubic", antialias=True,
+ * align_corners=False) does (a = -0.5, support 2 max(box / S, 1), taps outside the box dropped and the rest renormalised), clamp
+ * to [0, 1]; flip; the jitter with blend(a, b, f) = clamp(f a + (1 - f) b, 0, 1), gray = 0.2989 r + 0.587 g + 0.114 b (brightness
+ * blend(x, 0, f); contrast blend(x, mean of gray over the crop as it stands, f); saturation blend(x, gray, f); hue by
+ * torchvision's _rgb2hsv, h = (h + f) % 1, _hsv2rgb); grayscale; a 9 x 9 Gaussian blur (weights exp(-0.5 (t / sigma)^2) / sum,
+ * reflect padding by 4, separable); solarize (x >= 128/255 ? 1 - x : x); (x - mean3[c]) / std3[c].  mean3 / std3: HOST float[3].
+ * A box is clamped into the image and to 8 S per axis (the host refuses such a table).  S >= 5.  The contrast mean comes from
+ * per-tile fp64 sums added in a fixed order: no float atomics, results repeat bit for bit.  Every output element is written once.
+ * vtp_augment_scratch_floats returns the number of floats scratch must hold (the resampled crops and the tile sums), or -1. */
+int vtp_augment_scratch_floats(long N, int S);
+int vtp_augment_crops(const void* src_u8, long B, int Hs, int Ws, const float* table, long N, int S, const float* mean3,
+                      const float* std3, float* out, float* scratch, long scratch_len, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

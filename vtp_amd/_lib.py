@@ -125,6 +125,9 @@ SIGNATURES = {
     # images recon B H W sub3 div3 ref_u8 rec_u8 ref_lp rec_lp scratch scratch_len stream
     "vtp_recon_metrics": [_P, _P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _L, _P],
     "vtp_recon_finalize": [_P, _L, _L, _I, _I, _P, _P, _P, _P, _P, _P],  # scratch scratch_len B H W psnr ssim sse lpips acc stream
+    "vtp_augment_scratch_floats": [_L, _I],  # N S -> floats of scratch, or -1
+    # src_u8 B Hs Ws table N S mean3 std3 out scratch scratch_len stream
+    "vtp_augment_crops": [_P, _L, _I, _I, _P, _L, _I, _P, _P, _P, _P, _L, _P],
 }
 
 _lib = None

@@ -792,3 +792,21 @@ def recon_finalize(scratch, B, H, W, psnr, ssim, acc, sse=None, lpips=None):
     (sum psnr, images, images with sse == 0, sum ssim, sum of batch-mean ssim, batches, sum of batch-mean lpips, sum lpips)"""
     _lib.check(_lib_().vtp_recon_finalize(_p(scratch), scratch.numel(), B, H, W, _p(psnr), _p(ssim), _p(sse), _p(lpips), _p(acc), _s()),
                "vtp_recon_finalize")
+
+
+def augment_scratch_size(N, S):
+    """number of f32 elements the scratch of augment_crops must hold for N crops of S x S (the resampled crops and the per-tile
+    gray sums); ValueError for a shape the kernels refuse (N < 1, S < 5)"""
+    n = _lib_().vtp_augment_scratch_floats(N, S)
+    if n < 0:
+        raise ValueError(_lib_().vtp_last_error().decode(errors="replace"))
+    return n
+
+
+def augment_crops(u8_nhwc, table, out, mean, std, scratch):
+    """uint8 [B, Hs, Ws, 3] -> out f32 [N, 3, S, S] (N = views * B, crop n from image n % B), one row of table f32 [N, 16] (device)
+    per crop: resized crop, flip, colour jitter, grayscale, blur, solarize, normalise (csrc/augment.hip); two launches"""
+    B, Hs, Ws, _ = u8_nhwc.shape
+    N, _, S, _ = out.shape
+    _lib.check(_lib_().vtp_augment_crops(_p(u8_nhwc), B, Hs, Ws, _p(table), N, S, _f3(mean), _f3(std), _p(out), _p(scratch),
+                                         scratch.numel(), _s()), "vtp_augment_crops")
