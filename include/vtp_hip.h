@@ -551,6 +551,27 @@ int vtp_augment_scratch_floats(long N, int S);
 int vtp_augment_crops(const void* src_u8, long B, int Hs, int Ws, const float* table, long N, int S, const float* mean3,
                       const float* std3, float* out, float* scratch, long scratch_len, void* stream);
 
+/* ---- Preprocessing (preprocess.hip): PIL's 8-bit Image.resize (BOX / BILINEAR / BICUBIC), crop, flip and ToTensor + Normalize over
+ * a ragged batch of decoded byte images, bit for bit -- one launch per pass over the whole batch, no host synchronisation.
+ * src_u8: the images' bytes (RGB, [H_i, W_i, 3] each) back to back, src_len bytes, on the device.  scratch: scratch_len bytes for
+ * the uint8 intermediates (may be NULL when there is one launch).  jobs int64 [n, 16] on the DEVICE, 8-byte aligned, one row per
+ * pass of one image:
+ *   0 src byte offset (source buffer, or scratch with flag 1)   1 dst byte offset in scratch; last launch: the image's index
+ *   2, 3 output height, width of the pass   4, 5 source bytes per output row, column   6 bytes between two taps
+ *   7 index in tab of the pass's first (min, n) pair   8 index in tab of its first coefficient   9 coefficients per entry
+ *   10 subtracted from min   11 flags (1 source in scratch | 2 the table runs along y | 4 flip)   12 first block in its launch
+ *   13..15 unused
+ * tab int32 on the DEVICE: (min, n) pairs and 22-bit fixed-point coefficients, formed on the host in float64 as PIL's Resample.c
+ * does.  Per pixel and channel acc = 2^21 + sum_j K[j] src[min + j] in int32, dst = clamp(acc >> 22, 0, 255).
+ * launches: HOST int [n_launches, 3] = (first job, jobs, blocks); a block is 256 consecutive output pixels of one job; the last
+ * launch has one job per image, Ho x Wo each, and writes out f32 [B,3,Ho,Wo] = (float(u8) / 255 - mean3[c]) / std3[c] (the expression
+ * of vtp_u8_to_images) and, unless NULL, out_u8 uint8 [B,Ho,Wo,3].  mean3 / std3: HOST float[3].
+ * The job rows cannot be checked here: the caller guarantees that every offset lies inside its buffer (vtp_amd.preprocess.check_jobs).
+ * Every output element is written exactly once, without atomics: results repeat bit for bit. */
+int vtp_preprocess(const void* src_u8, long src_len, void* scratch, long scratch_len, const long* jobs, const int* tab,
+                   const int* launches, int n_launches, long B, int Ho, int Wo, const float* mean3, const float* std3, float* out,
+                   void* out_u8, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

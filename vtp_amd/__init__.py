@@ -1,7 +1,7 @@
 """vtp_amd -- MI355X-native (gfx950 / CDNA4) VTP training hot path.
 
 Public surface mirrors the reference (`from vtp.models.vtp_hf import VTPConfig, VTPModel`):
-    from vtp_amd import VTPConfig, VTPModel, VTPTrainer, LinearProbe, ZeroShot, ReconEval, MultiCrop
+    from vtp_amd import VTPConfig, VTPModel, VTPTrainer, LinearProbe, ZeroShot, ReconEval, MultiCrop, Preprocess
 Everything below the Python API is hand-written HIP in libvtp_hip.so (C ABI: include/vtp_hip.h)."""
 from .config import VTPConfig  # noqa: F401
 
@@ -37,4 +37,7 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name == "MultiCrop":
         from .augment import MultiCrop
         return MultiCrop
+    if name == "Preprocess":
+        from .preprocess import Preprocess
+        return Preprocess
     raise AttributeError(name)

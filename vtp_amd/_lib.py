@@ -128,6 +128,8 @@ SIGNATURES = {
     "vtp_augment_scratch_floats": [_L, _I],  # N S -> floats of scratch, or -1
     # src_u8 B Hs Ws table N S mean3 std3 out scratch scratch_len stream
     "vtp_augment_crops": [_P, _L, _I, _I, _P, _L, _I, _P, _P, _P, _P, _L, _P],
+    # src_u8 src_len scratch scratch_len jobs tab launches n_launches B Ho Wo mean3 std3 out out_u8 stream
+    "vtp_preprocess": [_P, _L, _P, _L, _P, _P, _P, _I, _L, _I, _I, _P, _P, _P, _P, _P],
 }
 
 _lib = None

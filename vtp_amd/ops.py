@@ -810,3 +810,17 @@ def augment_crops(u8_nhwc, table, out, mean, std, scratch):
     N, _, S, _ = out.shape
     _lib.check(_lib_().vtp_augment_crops(_p(u8_nhwc), B, Hs, Ws, _p(table), N, S, _f3(mean), _f3(std), _p(out), _p(scratch),
                                          scratch.numel(), _s()), "vtp_augment_crops")
+
+
+def preprocess(src_u8, scratch, jobs, tab, launches, out, out_u8, mean, std):
+    """PIL's 8-bit resize / crop / flip + ToTensor + Normalize over a ragged batch (csrc/preprocess.hip): src_u8 uint8 [bytes] and
+    scratch uint8 [bytes] on the device, jobs int64 [n * 16] and tab int32 on the device, launches int32 [L, 3] numpy on the host
+    -> out f32 [B, 3, Ho, Wo] (and out_u8 uint8 [B, Ho, Wo, 3] unless None); one launch per row of launches.  The job rows must have
+    passed vtp_amd.preprocess.check_jobs: the kernels cannot refuse a bad offset."""
+    import ctypes
+    import numpy as np
+    ln = np.ascontiguousarray(launches, dtype=np.int32)
+    B, _, Ho, Wo = out.shape
+    _lib.check(_lib_().vtp_preprocess(_p(src_u8), src_u8.numel(), _p(scratch), 0 if scratch is None else scratch.numel(), _p(jobs),
+                                      _p(tab), ln.ctypes.data_as(ctypes.c_void_p), len(ln), B, Ho, Wo, _f3(mean), _f3(std), _p(out),
+                                      _p(out_u8), _s()), "vtp_preprocess")

@@ -2,8 +2,9 @@
 latent-shard extraction of generation/tools/extract_features_vtp.py:22-128, with the same names, arguments, file names and
 safetensors layout, so the LightningDiT side (ImgLatentDataset) reads what this writes.
 
-What runs where: PIL decode / `center_crop_arr` stay on the host (vtp/utils/image_utils.py:5-33, restated in
-`center_crop_arr`); ToTensor + Normalize + horizontal flip, the encode / decode towers, the uint8 image packing and the
+What runs where: PIL decode stays on the host; `center_crop_arr` (vtp/utils/image_utils.py:5-33, restated in `center_crop_arr`)
+runs on the host through `crop_to_u8` and has a device path, bit-identical, through `images_from_decoded`
+(vtp_amd.Preprocess.center_crop, preprocess.hip); ToTensor + Normalize + horizontal flip, the encode / decode towers, the uint8 image packing and the
 per-channel latent statistics are gfx950 kernels (tokenizer.hip, the engines).  No CPU compute path: without the HIP library
 every entry point raises.
 """
@@ -106,6 +107,18 @@ class VTP_Tokenizer:
         out = torch.empty(t.shape[0], 3, t.shape[1], t.shape[2], dtype=torch.float32, device=self.device)
         ops.u8_to_images(t, out, self.norm_mean, self.norm_std, flip)
         return out
+
+    def images_from_decoded(self, images, flip: bool = False) -> torch.Tensor:
+        """decoded RGB images (a sequence of uint8 [H_i, W_i, 3] arrays / CPU tensors, any sizes) -> normalised f32 [B, 3, S, S] on
+        the device: what `images_from_u8(np.stack([crop_to_u8(im) for im in images]), flip)` returns, bit for bit, with
+        center_crop_arr on the device (vtp_amd.Preprocess.center_crop)."""
+        pp = getattr(self, "_preprocess", {}).get(bool(flip))
+        if pp is None:
+            from .preprocess import Preprocess
+            self._preprocess = getattr(self, "_preprocess", {})
+            pp = self._preprocess[bool(flip)] = Preprocess.center_crop(self.img_size, flip=flip, mean=self.norm_mean,
+                                                                        std=self.norm_std, device=self.device)
+        return pp(images)
 
     # ---- the reference's two methods
     def encode_images(self, images: torch.Tensor) -> torch.Tensor:
