@@ -70,6 +70,9 @@ int vtp_gemm_tn(const void* A, int lda, const void* B, int ldb, void* C, int ldc
  * (K: the problem's own token count in an item-list launch, 0 = the launch's K; the uniform-grid launch takes one K for all);
  * part: ntiles * splits_eff * 65536 floats, ticket: ntiles ints, zero before the first launch (the kernel leaves them zero). */
 int vtp_gemm_tn_grouped(const void* probs, int nprob, int ntiles, int K, int splits, void* part, void* ticket, void* stream);
+/* the same launch over the token rows [0, min(K, *k_rows)) (k_rows: device int): always ONE K slice per tile (no ticket is ever waited on,
+ * no scratch), and no operand row >= *k_rows is read */
+int vtp_gemm_tn_grouped_limit(const void* probs, int nprob, int ntiles, int K, const int* k_rows, void* stream);
 /* the same launch on the one-wave-per-SIMD kernel with the hand-scheduled k loop (K % 8 == 0; bit-identical results per K slice), from an
  * explicit work-item list, so that the tiles need not be cut alike: items = device array of nitems records of 8 int32 {tile, kbeg, kcount,
  * nparts, part, 0, 0, 0}, one workgroup each; the items of a tile partition [0, K) (kbeg multiples of 64); slots = the largest nparts;
@@ -256,6 +259,26 @@ int vtp_gemm_dgrad_swiglu(const void* A, int lda, const void* WT, int ldb, const
 int vtp_gelu_bwd(const void* dy, const void* pre, void* dx, long n, void* stream);
 /* dx = dy * QuickGELU'(pre)  (x sigmoid(1.702 x), layers/activation.py:5-12); bf16, n % 8 == 0 */
 int vtp_quick_gelu_bwd(const void* dy, const void* pre, void* dx, long n, void* stream);
+/* Device row limits: m_rows points to a DEVICE int, and the kernels below work on the rows [0, min(M, *m_rows)) of their [M, .] operands
+ * -- rows beyond are neither read nor written, and add nothing to the sums -- while the launch geometry stays that of the static M (one
+ * captured graph serves every count).  GELU / QuickGELU backward over [M, H] (quick != 0: QuickGELU); the norms as vtp_norm_fwd /
+ * vtp_norm_bwd; vtp_gemm_nt_limit as vtp_gemm_nt with one K slice and no row remaps, on the ring kernel only (the persistent 256-wide
+ * kernels take no limit: their shapes run the ring configuration of the dispatch table; a forced configuration >= 8 is refused). */
+int vtp_gelu_bwd_limit(const void* dy, const void* pre, void* dx, int M, int H, int quick, const int* m_rows, void* stream);
+int vtp_norm_fwd_limit(const float* x, const float* w, const float* b, void* y, float* stats, int M, int D, float eps, int kind,
+                       const int* m_rows, void* stream);
+int vtp_norm_bwd_limit(const void* dy, const float* x, const float* w, const float* stats, const float* dres, float* dx, void* dx_bf16,
+                       float* dw, float* db, float* dx_colsum, int M, int D, int kind, const int* m_rows, void* stream);
+int vtp_gemm_nt_limit(const void* A, int lda, const void* B, int ldb, void* C, int ldc, void* C2, int ldc2, const float* bias,
+                      const float* gamma, const float* resid, int M, int N, int K, int epilogue, float alpha, const int* m_rows,
+                      void* stream);
+/* The causal tiled attention kernels over packed captions: batch b = rows [cu[b], cu[b + 1]) (at most Nmax) of the packed qkv / o buffers
+ * (token strides sn_qkv / sn_o); grid and the [B, heads, Nmax] lse / delta layout are the padded launch's. */
+int vtp_attn_fwd_varlen(const void* q, const void* k, const void* v, void* o, float* lse, const int* cu, int B, int Nmax, int heads,
+                        long sn_qkv, long sn_o, float scale, void* stream);
+int vtp_attn_bwd_varlen(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse, float* delta,
+                        void* dq, void* dk, void* dv, const int* cu, int B, int Nmax, int heads, long sn_qkv, long sn_o, float scale,
+                        void* stream);
 
 /* PixelShuffle(16) (pixel_decoder.py:160): t bf16 [B*h*w, 768] token-major -> img f32 [B,3,16h,16w]. */
 int vtp_pixel_shuffle16(const void* t, float* img, int B, int h, int w, void* stream);
@@ -346,6 +369,17 @@ int vtp_embed_tokens_bwd(const long* ids, const float* dx, float* d_table, float
 /* out f32 [B, D] = x[b*T + idx[b]] ; scatter: dx f32 [B*T, D] (and optional bf16 copy) = 0 except those rows = dy. */
 int vtp_gather_rows(const float* x, const int* idx, float* out, int B, int T, int D, void* stream);
 int vtp_scatter_rows(const float* dy, const int* idx, float* dx, void* dx_bf16, int B, int T, int D, void* stream);
+/* Packed captions (causal text tower with arg-max pooling: the rows behind a caption's EOT are dead).  vtp_text_row_plan builds, on the
+ * device, eot[b] = argmax_t ids[b, t] (first maximum), cu int32 [B + 1] = exclusive prefix sum of eot + 1 and rows[0] = cu[B]; caption b
+ * is then the rows [cu[b], cu[b + 1]) of every packed token buffer (row cu[b] + t = its token t).  The packed variants of the four
+ * kernels above read / write live rows only: the pooled row is cu[b + 1] - 1, and the scatter zeroes live rows only. */
+int vtp_text_row_plan(const long* ids, int* eot, int* cu, int* rows, int B, int T, void* stream);
+int vtp_embed_tokens_packed(const long* ids, const float* table, const float* pos, float* x, const int* cu, int B, int T, int D,
+                            void* stream);
+int vtp_embed_tokens_bwd_packed(const long* ids, const float* dx, float* d_table, float* d_pos, const int* cu, int B, int T, int D,
+                                void* stream);
+int vtp_gather_rows_packed(const float* x, const int* cu, float* out, int B, int D, void* stream);
+int vtp_scatter_rows_packed(const float* dy, const int* cu, float* dx, void* dx_bf16, int B, int T, int D, void* stream);
 /* F.normalize(x, dim=-1, eps) (modeling_vtp.py:276,310): y = x * inv_norm, inv_norm = 1 / max(||x||, eps); and its backward. */
 int vtp_l2norm_fwd(const float* x, float* y, float* inv_norm, int B, int D, float eps, void* stream);
 int vtp_l2norm_bwd(const float* dy, const float* y, const float* inv_norm, float* dx, int B, int D, void* stream);

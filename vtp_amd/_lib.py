@@ -106,6 +106,19 @@ SIGNATURES = {
     "vtp_embed_tokens_bwd": [_P, _P, _P, _P, _I, _I, _I, _P],
     "vtp_gather_rows": [_P, _P, _P, _I, _I, _I, _P],
     "vtp_scatter_rows": [_P, _P, _P, _P, _I, _I, _I, _P],
+    "vtp_text_row_plan": [_P, _P, _P, _P, _I, _I, _P],  # ids eot cu rows B T stream
+    "vtp_embed_tokens_packed": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "vtp_embed_tokens_bwd_packed": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "vtp_gather_rows_packed": [_P, _P, _P, _I, _I, _P],
+    "vtp_scatter_rows_packed": [_P, _P, _P, _P, _I, _I, _I, _P],
+    # device row limits (m_rows: device int in front of the stream)
+    "vtp_gelu_bwd_limit": [_P, _P, _P, _I, _I, _I, _P, _P],
+    "vtp_norm_fwd_limit": [_P, _P, _P, _P, _P, _I, _I, _F, _I, _P, _P],
+    "vtp_norm_bwd_limit": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P],
+    "vtp_gemm_nt_limit": [_P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P],
+    "vtp_attn_fwd_varlen": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _L, _L, _F, _P],
+    "vtp_attn_bwd_varlen": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _L, _L, _F, _P],
+    "vtp_gemm_tn_grouped_limit": [_P, _I, _I, _I, _P, _P],
     "vtp_l2norm_fwd": [_P, _P, _P, _I, _I, _F, _P],
     "vtp_l2norm_bwd": [_P, _P, _P, _P, _I, _I, _P],
     "vtp_clip_logits": [_P, _P, _P, _P, _I, _I, _I, _P],

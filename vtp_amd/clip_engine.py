@@ -8,7 +8,7 @@ from typing import Dict, Optional
 import torch
 
 from . import ops
-from .engine import BF, F32, OVERLAP, ParamStore, Stack, Workspace, linear_bwd
+from .engine import BF, F32, OVERLAP, ParamStore, Stack, Workspace, _env_flag, linear_bwd
 from .ops import EPI_BF16, EPI_F32
 
 I32 = torch.int32
@@ -27,6 +27,12 @@ class TextEngine:
         self.stack.causal = not cfg.text_no_causal_mask
         self.stack.quick_gelu = bool(cfg.text_quick_gelu)  # act_layer = QuickGELU (modeling_vtp.py:139)
         self.pool = cfg.text_pool_type
+        # Packed captions: under the causal mask no row up to a caption's EOT depends on a row behind it, and arg-max pooling reads the EOT
+        # row alone -- so the rows behind it are dead in the forward and receive exact zeros in the backward.  The tower then runs on the
+        # live rows only, stored back to back; their count stays on the device (ops.text_row_plan), so launch shapes and a captured graph
+        # are those of B * T rows.  Every other variant (no causal mask, first / last / none pooling, text_embed_cls) keeps all rows;
+        # VTP_TEXT_VARLEN=0 forces that path (same-box A/B runs).
+        self.packed = self.stack.causal and self.pool == "argmax" and not cfg.text_embed_cls
         # text_projection is stored [width, output_dim] and applied as x @ P (modeling_vtp.py:308): as a Lin with
         # N = width, K = output_dim its bf16 copy `w` is P and `wT` is P^T (the K-contiguous operand of the forward GEMM)
         self.proj = store.lin("text_projection", None, self.D, self.Dout)
@@ -46,6 +52,18 @@ class TextEngine:
         ws = self.workspace(B)
         x0 = ws.get("x0", (B * T, D), F32)
         eot = ws.get("eot", (B,), I32)
+        plan = None
+        if self.packed and _env_flag("VTP_TEXT_VARLEN") and self.stack.varlen_ok(B * T):
+            plan = (ws.get("cu", (B + 1,), I32), ws.get("rows", (1,), I32))
+        self.stack.varlen = plan
+        if plan is not None:
+            cu, rows = plan
+            ops.text_row_plan(ids, eot, cu, rows, B, T)
+            ops.embed_tokens_packed(ids, st.p("token_embedding.weight"), st.p("positional_embedding"), x0, cu, B, T, D)
+            xl = self.stack.forward(ws, x0, [(B, T, None)], 0, train)
+            pooled = ws.get("pooled", (B, D), F32)
+            ops.gather_rows_packed(xl, cu, pooled, B, D)
+            return self._head(ws, ids, B, T, eot, pooled, plan)
         ops.embed_tokens(ids, st.p("token_embedding.weight"), st.p("positional_embedding"), x0, eot, B, T, D)
         if self.pool in ("first", "last"):  # the kernel wrote the arg-max position of every row; 'first' / 'last' pool a fixed position
             eot.fill_(0 if self.pool == "first" else T - 1)
@@ -56,24 +74,30 @@ class TextEngine:
             ops.norm_fwd(xl, st.p("ln_final.weight"), st.p("ln_final.bias"), xn, stf, B * T, D, 1e-5, ops.NORM_LN)
             feat = ws.get("all_feat", (B * T, self.Dout), F32)
             ops.gemm_nt(xn, self.proj.wT, feat, M=B * T, N=self.Dout, K=D, epi=EPI_F32)
-            self._ctx = (ws, ids, B, T, None, xl, xn, stf)
+            self._ctx = (ws, ids, B, T, None, xl, xn, stf, None)
             return feat
         pooled = ws.get("pooled", (B, D), F32)
         ops.gather_rows(xl, eot, pooled, B, T, D)  # ln_final is row-wise: pool first, normalise B rows instead of B*T
+        return self._head(ws, ids, B, T, eot, pooled, None)
+
+    def _head(self, ws, ids, B, T, eot, pooled, plan):
+        """ln_final and the projection of the B pooled rows"""
+        st, D = self.store, self.D
         pn = ws.get("pooled_n", (B, D), BF)
         stf = ws.get("stf", (B, 2), F32)
         ops.norm_fwd(pooled, st.p("ln_final.weight"), st.p("ln_final.bias"), pn, stf, B, D, 1e-5, ops.NORM_LN)
         feat = ws.get("feat", (B, self.Dout), F32)
         ops.gemm_nt(pn, self.proj.wT, feat, M=B, N=self.Dout, K=D, epi=EPI_F32)
-        self._ctx = (ws, ids, B, T, eot, pooled, pn, stf)
+        self._ctx = (ws, ids, B, T, eot, pooled, pn, stf, plan)
         return feat
 
     def backward(self, d_feat: torch.Tensor):
         """d_feat f32 [B, Dout].  Generator (see Stack.backward): yields "tail" then ("block", i); parameter gradients
         accumulate into store.flat_g."""
         st = self.store
-        ws, ids, B, T, eot, pooled, pn, stf = self._ctx
+        ws, ids, B, T, eot, pooled, pn, stf, plan = self._ctx
         D = self.D
+        self.stack.varlen = plan  # (the forward's: another forward may have run since)
         if eot is None:  # text_pool_type = "none": the same head over all B * T rows, no pooling scatter
             R = B * T
             d_feat_b = ws.get("b.all_d_feat_b", (R, self.Dout), BF)
@@ -103,11 +127,17 @@ class TextEngine:
                      st.g("ln_final.bias"), B, D, ops.NORM_LN)
         dx = ws.get("b.dxt", (B * T, D), F32)
         dx_b = ws.get("b.dxt_b", (B * T, D), BF)
-        ops.scatter_rows(d_pooled, eot, dx, dx_b, B, T, D)
+        if plan is not None:
+            ops.scatter_rows_packed(d_pooled, plan[0], dx, dx_b, B, T, D)
+        else:
+            ops.scatter_rows(d_pooled, eot, dx, dx_b, B, T, D)
         OVERLAP.join()
         yield "tail"
         dx0, _ = yield from self.stack.backward(ws, dx, dx_b, [(B, T, None)], 0)
-        ops.embed_tokens_bwd(ids, dx0, st.g("token_embedding.weight"), st.g("positional_embedding"), B, T, D)
+        if plan is not None:
+            ops.embed_tokens_bwd_packed(ids, dx0, st.g("token_embedding.weight"), st.g("positional_embedding"), plan[0], B, T, D)
+        else:
+            ops.embed_tokens_bwd(ids, dx0, st.g("token_embedding.weight"), st.g("positional_embedding"), B, T, D)
         OVERLAP.join()
 
 

@@ -37,6 +37,10 @@ struct AttnArgs {
   long sb, sn;    // q/k/v (and dq/dk/dv) batch / token strides in elements
   long sbo, sno;  // o / d_o strides
   float scale;
+  // VARLEN kernels (packed captions of different length, causal): batch b is the rows [cu[b], cu[b + 1]) of the packed q / k / v / o
+  // buffers (token strides sn / sno; sb / sbo unused), N is the LONGEST length the grid and the [B, heads, N] lse / delta layout are
+  // built for, and workgroups whose query / key tile lies beyond their batch's length return
+  const int* cu;
 };
 
 __device__ __forceinline__ bf16x8 cat4(bf16x4 a, bf16x4 b) {
@@ -86,24 +90,33 @@ __device__ __forceinline__ void zero16(f32x16& a) {
 }
 
 // ------------------------------------------------------------------------------------------------ forward
-template <bool CAUSAL>
+template <bool CAUSAL, bool VARLEN = false>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnArgs p) {
   __shared__ __attribute__((aligned(16))) bf16 Ks[KT * RS];
   __shared__ __attribute__((aligned(16))) bf16 Vr[KT * RT];   // V row-major, read transposed (tr16)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, hi = lane >> 5;
   const int b = blockIdx.z, h = blockIdx.y;
+  int N = p.N;
+  long boff = (long)b * p.sb, booff = (long)b * p.sbo;
+  if constexpr (VARLEN) {
+    const int r0 = p.cu[b];
+    N = min(p.cu[b + 1] - r0, p.N);
+    boff = (long)r0 * p.sn;
+    booff = (long)r0 * p.sno;
+    if ((int)blockIdx.x * 128 >= N) return;  // (the whole workgroup, ahead of every barrier)
+  }
   const int qw0 = blockIdx.x * 128;
   const int q0 = qw0 + wave * 32;
   const int qi = q0 + (lane & 31);
-  const bool wave_active = q0 < p.N;
-  const bf16* qb = p.q + (long)b * p.sb + h * 64;
-  const bf16* kb_ = p.k + (long)b * p.sb + h * 64;
-  const bf16* vb = p.v + (long)b * p.sb + h * 64;
+  const bool wave_active = q0 < N;
+  const bf16* qb = p.q + boff + h * 64;
+  const bf16* kb_ = p.k + boff + h * 64;
+  const bf16* vb = p.v + boff + h * 64;
   const float sc2 = p.scale * LOG2E;
 
   bf16x8 qf[4];
   {
-    const bf16* qr = qb + (long)min(qi, p.N - 1) * p.sn + hi * 8;
+    const bf16* qr = qb + (long)min(qi, N - 1) * p.sn + hi * 8;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) qf[ks] = *(const bf16x8*)(qr + ks * 16);
   }
@@ -112,12 +125,12 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnArgs p) {
   zero16(oacc[1]);
   float m_i = -1e30f, l_i = 0.f;
 
-  const int kend = CAUSAL ? min(p.N, qw0 + 128) : p.N;
+  const int kend = CAUSAL ? min(N, qw0 + 128) : N;
   const int ntiles = (kend + KT - 1) / KT;
   for (int t = 0; t < ntiles; ++t) {
     __syncthreads();
-    stage_tile2<RS, 0>(kb_, p.sn, t * KT, p.N, Ks, nullptr);
-    stage_tile2<RT, 0>(vb, p.sn, t * KT, p.N, Vr, nullptr);
+    stage_tile2<RS, 0>(kb_, p.sn, t * KT, N, Ks, nullptr);
+    stage_tile2<RT, 0>(vb, p.sn, t * KT, N, Vr, nullptr);
     __syncthreads();
     if (!wave_active) continue;
     const int nkb = min(2, (kend - t * KT + 31) / 32);
@@ -133,7 +146,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnArgs p) {
       for (int r = 0; r < 16; ++r) {
         const int key = key0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
         float x = s[r] * sc2;
-        if (key >= p.N || (CAUSAL && key > qi)) x = -INFINITY;
+        if (key >= N || (CAUSAL && key > qi)) x = -INFINITY;
         s[r] = x;
         mx = fmaxf(mx, x);
       }
@@ -162,9 +175,9 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnArgs p) {
       }
     }
   }
-  if (!wave_active || qi >= p.N) return;
+  if (!wave_active || qi >= N) return;
   const float inv = 1.f / l_i;
-  bf16* orow = p.out + (long)b * p.sbo + (long)qi * p.sno + h * 64;
+  bf16* orow = p.out + booff + (long)qi * p.sno + h * 64;
 #pragma unroll
   for (int db = 0; db < 2; ++db)
 #pragma unroll
@@ -178,6 +191,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnArgs p) {
 }
 
 // ------------------------------------------------------------------------------------------------ delta = rowsum(dO * O)
+template <bool VARLEN = false>
 __global__ __launch_bounds__(256) void attn_delta_kernel(const AttnArgs p) {
   const long total = (long)p.B * p.heads * p.N * 8;  // 8 lanes per (b,h,n) row
   for (long idx = blockIdx.x * 256L + threadIdx.x; idx < total; idx += (long)gridDim.x * 256L) {
@@ -186,7 +200,12 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const AttnArgs p) {
     const int n = (int)(row % p.N);
     const int h = (int)((row / p.N) % p.heads);
     const long b = row / ((long)p.N * p.heads);
-    const long off = b * p.sbo + (long)n * p.sno + h * 64 + part * 8;
+    long off = b * p.sbo + (long)n * p.sno + h * 64 + part * 8;
+    if constexpr (VARLEN) {  // (the 8 lanes of a row leave together: the shuffles below stay inside the group)
+      const int r0 = p.cu[b];
+      if (n >= p.cu[b + 1] - r0) continue;
+      off = (long)(r0 + n) * p.sno + h * 64 + part * 8;
+    }
     bf16x8 a = *(const bf16x8*)(p.o + off), g = *(const bf16x8*)(p.d_o + off);
     float s = 0.f;
 #pragma unroll
@@ -199,26 +218,35 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const AttnArgs p) {
 }
 
 // ------------------------------------------------------------------------------------------------ backward: dQ
-template <bool CAUSAL>
+template <bool CAUSAL, bool VARLEN = false>
 __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const AttnArgs p) {
   __shared__ __attribute__((aligned(16))) bf16 Ks[KT * RS];
   __shared__ __attribute__((aligned(16))) bf16 Vs[KT * RS];
   __shared__ __attribute__((aligned(16))) bf16 Kr[KT * RT];   // second row-major K image, read transposed (tr16)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, hi = lane >> 5;
   const int b = blockIdx.z, h = blockIdx.y;
+  int N = p.N;
+  long boff = (long)b * p.sb, booff = (long)b * p.sbo;
+  if constexpr (VARLEN) {
+    const int r0 = p.cu[b];
+    N = min(p.cu[b + 1] - r0, p.N);
+    boff = (long)r0 * p.sn;
+    booff = (long)r0 * p.sno;
+    if ((int)blockIdx.x * 128 >= N) return;  // (the whole workgroup, ahead of every barrier)
+  }
   const int qw0 = blockIdx.x * 128;
   const int q0 = qw0 + wave * 32;
   const int qi = q0 + (lane & 31);
-  const int qc = min(qi, p.N - 1);
-  const bool wave_active = q0 < p.N;
-  const bf16* kb_ = p.k + (long)b * p.sb + h * 64;
-  const bf16* vb = p.v + (long)b * p.sb + h * 64;
+  const int qc = min(qi, N - 1);
+  const bool wave_active = q0 < N;
+  const bf16* kb_ = p.k + boff + h * 64;
+  const bf16* vb = p.v + boff + h * 64;
   const float sc2 = p.scale * LOG2E;
 
   bf16x8 qf[4], dof[4];
   {
-    const bf16* qr = p.q + (long)b * p.sb + h * 64 + (long)qc * p.sn + hi * 8;
-    const bf16* gr = p.d_o + (long)b * p.sbo + h * 64 + (long)qc * p.sno + hi * 8;
+    const bf16* qr = p.q + boff + h * 64 + (long)qc * p.sn + hi * 8;
+    const bf16* gr = p.d_o + booff + h * 64 + (long)qc * p.sno + hi * 8;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       qf[ks] = *(const bf16x8*)(qr + ks * 16);
@@ -232,12 +260,12 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const AttnArgs p) {
   zero16(dq[0]);
   zero16(dq[1]);
 
-  const int kend = CAUSAL ? min(p.N, qw0 + 128) : p.N;
+  const int kend = CAUSAL ? min(N, qw0 + 128) : N;
   const int ntiles = (kend + KT - 1) / KT;
   for (int t = 0; t < ntiles; ++t) {
     __syncthreads();
-    stage_tile2<RS, RT>(kb_, p.sn, t * KT, p.N, Ks, Kr);
-    stage_tile2<RS, 0>(vb, p.sn, t * KT, p.N, Vs, nullptr);
+    stage_tile2<RS, RT>(kb_, p.sn, t * KT, N, Ks, Kr);
+    stage_tile2<RS, 0>(vb, p.sn, t * KT, N, Vs, nullptr);
     __syncthreads();
     if (!wave_active) continue;
     const int nkb = min(2, (kend - t * KT + 31) / 32);
@@ -256,7 +284,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const AttnArgs p) {
       for (int r = 0; r < 16; ++r) {
         const int key = key0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
         float pr = fast_exp2(s[r] * sc2 - lse2);
-        if (key >= p.N || (CAUSAL && key > qi)) pr = 0.f;
+        if (key >= N || (CAUSAL && key > qi)) pr = 0.f;
         s[r] = pr * (dp[r] - dlt) * p.scale;
       }
       const bf16x8 d0 = pack8(s, 0), d1 = pack8(s, 8);
@@ -267,8 +295,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const AttnArgs p) {
       }
     }
   }
-  if (!wave_active || qi >= p.N) return;
-  bf16* drow = p.dq + (long)b * p.sb + (long)qi * p.sn + h * 64;
+  if (!wave_active || qi >= N) return;
+  bf16* drow = p.dq + boff + (long)qi * p.sn + h * 64;
 #pragma unroll
   for (int db = 0; db < 2; ++db)
 #pragma unroll
@@ -281,7 +309,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const AttnArgs p) {
 }
 
 // ------------------------------------------------------------------------------------------------ backward: dK, dV
-template <bool CAUSAL>
+template <bool CAUSAL, bool VARLEN = false>
 __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnArgs p) {
   __shared__ __attribute__((aligned(16))) bf16 Qs[KT * RS];
   __shared__ __attribute__((aligned(16))) bf16 Gs[KT * RS];   // dO row-major
@@ -291,19 +319,28 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnArgs p) {
   __shared__ __attribute__((aligned(16))) float dlt_s[KT];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, hi = lane >> 5;
   const int b = blockIdx.z, h = blockIdx.y;
+  int N = p.N;
+  long boff = (long)b * p.sb, booff = (long)b * p.sbo;
+  if constexpr (VARLEN) {
+    const int r0 = p.cu[b];
+    N = min(p.cu[b + 1] - r0, p.N);
+    boff = (long)r0 * p.sn;
+    booff = (long)r0 * p.sno;
+    if ((int)blockIdx.x * 128 >= N) return;  // (the whole workgroup, ahead of every barrier)
+  }
   const int kw0 = blockIdx.x * 128;
   const int k0 = kw0 + wave * 32;
   const int ki = k0 + (lane & 31);
-  const int kc = min(ki, p.N - 1);
-  const bool wave_active = k0 < p.N;
-  const bf16* qb = p.q + (long)b * p.sb + h * 64;
-  const bf16* gb = p.d_o + (long)b * p.sbo + h * 64;
+  const int kc = min(ki, N - 1);
+  const bool wave_active = k0 < N;
+  const bf16* qb = p.q + boff + h * 64;
+  const bf16* gb = p.d_o + booff + h * 64;
   const float sc2 = p.scale * LOG2E;
 
   bf16x8 kf[4], vf[4];
   {
-    const bf16* kr = p.k + (long)b * p.sb + h * 64 + (long)kc * p.sn + hi * 8;
-    const bf16* vr = p.v + (long)b * p.sb + h * 64 + (long)kc * p.sn + hi * 8;
+    const bf16* kr = p.k + boff + h * 64 + (long)kc * p.sn + hi * 8;
+    const bf16* vr = p.v + boff + h * 64 + (long)kc * p.sn + hi * 8;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       kf[ks] = *(const bf16x8*)(kr + ks * 16);
@@ -316,21 +353,21 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnArgs p) {
   zero16(dv[0]);
   zero16(dv[1]);
 
-  const int ntiles = (p.N + KT - 1) / KT;
+  const int ntiles = (N + KT - 1) / KT;
   const int t0 = CAUSAL ? (kw0 / KT) : 0;
   const long srow0 = ((long)b * p.heads + h) * p.N;
   for (int t = t0; t < ntiles; ++t) {
     __syncthreads();
-    stage_tile2<RS, RT>(qb, p.sn, t * KT, p.N, Qs, Qr);
-    stage_tile2<RS, RT>(gb, p.sno, t * KT, p.N, Gs, Gr);
+    stage_tile2<RS, RT>(qb, p.sn, t * KT, N, Qs, Qr);
+    stage_tile2<RS, RT>(gb, p.sno, t * KT, N, Gs, Gr);
     if (threadIdx.x < KT) {
-      const int qn = min(t * KT + (int)threadIdx.x, p.N - 1);
+      const int qn = min(t * KT + (int)threadIdx.x, N - 1);
       lse_s[threadIdx.x] = p.lse[srow0 + qn] * LOG2E;
       dlt_s[threadIdx.x] = p.delta[srow0 + qn];
     }
     __syncthreads();
     if (!wave_active) continue;
-    const int nqb = min(2, (p.N - t * KT + 31) / 32);
+    const int nqb = min(2, (N - t * KT + 31) / 32);
     for (int qblk = 0; qblk < nqb; ++qblk) {
       const int qs0 = t * KT + qblk * 32;
       if (CAUSAL && qs0 + 31 < k0) continue;
@@ -352,7 +389,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnArgs p) {
           const int r = 4 * g + e;
           const int qn = qs0 + 8 * g + 4 * hi + e;
           float pv = fast_exp2(s[r] * sc2 - l4[e]);
-          if (qn >= p.N || ki >= p.N || (CAUSAL && ki > qn)) pv = 0.f;
+          if (qn >= N || ki >= N || (CAUSAL && ki > qn)) pv = 0.f;
           pr[r] = pv;
           s[r] = pv * (dp[r] - d4[e]) * p.scale;
         }
@@ -367,9 +404,9 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnArgs p) {
       }
     }
   }
-  if (!wave_active || ki >= p.N) return;
-  bf16* krow = p.dk + (long)b * p.sb + (long)ki * p.sn + h * 64;
-  bf16* vrow = p.dv + (long)b * p.sb + (long)ki * p.sn + h * 64;
+  if (!wave_active || ki >= N) return;
+  bf16* krow = p.dk + boff + (long)ki * p.sn + h * 64;
+  bf16* vrow = p.dv + boff + (long)ki * p.sn + h * 64;
 #pragma unroll
   for (int db = 0; db < 2; ++db)
 #pragma unroll
@@ -442,7 +479,7 @@ extern "C" int vtp_attn_bwd(const void* q, const void* k, const void* v, const v
   const long rows8 = (long)B * heads * N * 8;
   int dblocks = (int)((rows8 + 255) / 256);
   if (dblocks > 4096) dblocks = 4096;
-  hipLaunchKernelGGL(attn_delta_kernel, dim3(dblocks), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(attn_delta_kernel<false>, dim3(dblocks), dim3(256), 0, s, a);
   dim3 grid(cdiv(N, 128), heads, B);
   if (causal) {
     hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, grid, dim3(256), 0, s, a);
@@ -458,4 +495,38 @@ extern "C" int vtp_attn_bwd(const void* q, const void* k, const void* v, const v
     return vtp_rope_qk(dq, rope_sin, rope_cos, B, N, heads, rope_prefix, 1, stream);
   }
   return VTP_OK;
+}
+
+// The causal tiled kernels over PACKED captions: batch b is the rows [cu[b], cu[b + 1]) (cu int32 [B + 1] on the device) of the packed
+// [rows, 3 * heads * 64] qkv and [rows, heads * 64] o buffers, at most Nmax rows each.  The grid is the padded launch's (ceil(Nmax / 128),
+// heads, B) and lse / delta keep the padded [B, heads, Nmax] layout; rows outside the batches are neither read nor written.
+extern "C" int vtp_attn_fwd_varlen(const void* q, const void* k, const void* v, void* o, float* lse, const int* cu, int B, int Nmax,
+                                   int heads, long sn_qkv, long sn_o, float scale, void* stream) {
+  VTP_REQUIRE(q && k && v && o && cu, "vtp_attn_fwd_varlen: null pointer");
+  if (int e = check_attn("vtp_attn_fwd_varlen", B, Nmax, heads, 0, sn_qkv, 0, sn_o)) return e;
+  AttnArgs a = {};
+  a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.out = (bf16*)o; a.lse = lse;
+  a.B = B; a.N = Nmax; a.heads = heads; a.sn = sn_qkv; a.sno = sn_o; a.scale = scale; a.cu = cu;
+  hipLaunchKernelGGL((attn_fwd_kernel<true, true>), dim3(cdiv(Nmax, 128), heads, B), dim3(256), 0, (hipStream_t)stream, a);
+  return check_launch("attn_fwd_varlen");
+}
+
+extern "C" int vtp_attn_bwd_varlen(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse,
+                                   float* delta, void* dq, void* dk, void* dv, const int* cu, int B, int Nmax, int heads, long sn_qkv,
+                                   long sn_o, float scale, void* stream) {
+  VTP_REQUIRE(q && k && v && o && d_o && lse && delta && dq && dk && dv && cu, "vtp_attn_bwd_varlen: null pointer");
+  if (int e = check_attn("vtp_attn_bwd_varlen", B, Nmax, heads, 0, sn_qkv, 0, sn_o)) return e;
+  hipStream_t s = (hipStream_t)stream;
+  AttnArgs a = {};
+  a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.o = (const bf16*)o; a.d_o = (const bf16*)d_o;
+  a.lse = (float*)lse; a.delta = delta; a.dq = (bf16*)dq; a.dk = (bf16*)dk; a.dv = (bf16*)dv;
+  a.B = B; a.N = Nmax; a.heads = heads; a.sn = sn_qkv; a.sno = sn_o; a.scale = scale; a.cu = cu;
+  const long rows8 = (long)B * heads * Nmax * 8;
+  int dblocks = (int)((rows8 + 255) / 256);
+  if (dblocks > 4096) dblocks = 4096;
+  hipLaunchKernelGGL(attn_delta_kernel<true>, dim3(dblocks), dim3(256), 0, s, a);
+  dim3 grid(cdiv(Nmax, 128), heads, B);
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<true, true>), grid, dim3(256), 0, s, a);
+  hipLaunchKernelGGL((attn_bwd_dkv_kernel<true, true>), grid, dim3(256), 0, s, a);
+  return check_launch("attn_bwd_varlen");
 }

@@ -71,6 +71,98 @@ __global__ __launch_bounds__(256) void scatter_rows_kernel(const float* __restri
   }
 }
 
+// ---- packed captions (causal text tower, arg-max pooling): only the rows up to each caption's EOT are live, and they are stored back to
+// back -- caption b is the rows [cu[b], cu[b + 1]) of every token buffer, row cu[b] + t = its token t <= eot[b].  The plan is built on the
+// device from the ids (the lengths never reach the host); rows[0] = cu[B] is the row limit the row-wise and GEMM kernels read.
+// eot[b] = argmax_t ids[b, t] (first maximum) ; cu = exclusive prefix sum of eot + 1 ; rows[0] = cu[B].   One workgroup: a wave per
+// caption (its lanes read the ids side by side -- a thread per caption would wait for T dependent loads), then one thread adds them up.
+__global__ __launch_bounds__(256) void text_row_plan_kernel(const long* __restrict__ ids, int* __restrict__ eot, int* __restrict__ cu,
+                                                            int* __restrict__ rows, int B, int T) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int b = wave; b < B; b += 4) {
+    long best = 0;
+    int bi = T;  // T: this lane holds no position yet
+    for (int t = lane; t < T; t += 64) {
+      const long v = ids[(long)b * T + t];
+      if (bi == T || v > best) { best = v; bi = t; }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {  // the larger id wins, the earlier position among equal ids
+      const long ov = __shfl_xor(best, off, 64);
+      const int oi = __shfl_xor(bi, off, 64);
+      if (oi < T && (bi == T || ov > best || (ov == best && oi < bi))) { best = ov; bi = oi; }
+    }
+    if (lane == 0) eot[b] = bi;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int acc = 0;
+    for (int b = 0; b < B; ++b) {
+      cu[b] = acc;
+      acc += eot[b] + 1;
+    }
+    cu[B] = acc;
+    rows[0] = acc;
+  }
+}
+
+// x[cu[b] + t, :] = table[ids[b,t], :] + pos[t, :]  for t <= eot[b]
+__global__ __launch_bounds__(256) void embed_tokens_packed_kernel(const long* __restrict__ ids, const float* __restrict__ table,
+                                                                  const float* __restrict__ pos, float* __restrict__ x,
+                                                                  const int* __restrict__ cu, int B, int T, int D) {
+  const int b = blockIdx.x;
+  const int d4 = D / 4;
+  const int r0 = cu[b], len = min(cu[b + 1] - r0, T);
+  for (int i = threadIdx.x; i < len * d4; i += 256) {
+    const int t = i / d4, c = i % d4;
+    const long id = ids[(long)b * T + t];
+    f32x4 e = *(const f32x4*)(table + id * D + 4 * c);
+    f32x4 p = *(const f32x4*)(pos + (long)t * D + 4 * c);
+    *(f32x4*)(x + ((long)r0 + t) * D + 4 * c) = e + p;
+  }
+}
+
+// embed_tokens_bwd over the packed rows: d_table[ids[b,t], :] += dx[cu[b] + t, :] and d_pos[t, :] += the same, for t <= eot[b]
+__global__ __launch_bounds__(256) void embed_tokens_bwd_packed_kernel(const long* __restrict__ ids, const float* __restrict__ dx,
+                                                                      float* __restrict__ d_table, float* __restrict__ d_pos,
+                                                                      const int* __restrict__ cu, int B, int T, int D) {
+  const int t = blockIdx.x;
+  for (int d = threadIdx.x; d < D; d += 256) {
+    float s = 0.f;
+    for (int b = 0; b < B; ++b) {
+      const int r0 = cu[b];
+      if (t >= cu[b + 1] - r0) continue;
+      const float g = dx[((long)r0 + t) * D + d];
+      s += g;
+      unsafeAtomicAdd(d_table + ids[(long)b * T + t] * D + d, g);
+    }
+    d_pos[(long)t * D + d] += s;
+  }
+}
+
+// out[b, :] = x[cu[b + 1] - 1, :]  (the EOT row of caption b)
+__global__ __launch_bounds__(256) void gather_rows_packed_kernel(const float* __restrict__ x, const int* __restrict__ cu,
+                                                                 float* __restrict__ out, int B, int D) {
+  const int b = blockIdx.x;
+  const float* src = x + ((long)cu[b + 1] - 1) * D;
+  for (int d = threadIdx.x; d < D; d += 256) out[(long)b * D + d] = src[d];
+}
+
+// the live rows of dx (f32) and dxb (bf16) = 0 except row cu[b + 1] - 1 = dy[b, :]; rows >= cu[B] are left alone.  Grid (T, B).
+__global__ __launch_bounds__(256) void scatter_rows_packed_kernel(const float* __restrict__ dy, const int* __restrict__ cu,
+                                                                  float* __restrict__ dx, bf16* __restrict__ dxb, int B, int T, int D) {
+  const int b = blockIdx.y, t = blockIdx.x;
+  const int r0 = cu[b], len = min(cu[b + 1] - r0, T);
+  if (t >= len) return;
+  const bool hit = t == len - 1;
+  const long row = (long)r0 + t;
+  for (int d = threadIdx.x; d < D; d += 256) {
+    const float v = hit ? dy[(long)b * D + d] : 0.f;
+    dx[row * D + d] = v;
+    if (dxb) dxb[row * D + d] = f2bf(v);
+  }
+}
+
 // y = x / max(||x||, eps) ; inv[b] = 1 / max(||x||, eps)          (F.normalize, eps 1e-12)
 __global__ __launch_bounds__(256) void l2norm_fwd_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                          float* __restrict__ inv, int B, int D, float eps) {
@@ -214,6 +306,38 @@ extern "C" int vtp_scatter_rows(const float* dy, const int* idx, float* dx, void
   VTP_REQUIRE(dy && idx && dx && B > 0 && T > 0 && D > 0, "vtp_scatter_rows: bad argument");
   hipLaunchKernelGGL(scatter_rows_kernel, dim3(B * T), dim3(256), 0, (hipStream_t)stream, dy, idx, dx, (bf16*)dx_bf16, B, T, D);
   return check_launch("scatter_rows");
+}
+
+extern "C" int vtp_text_row_plan(const long* ids, int* eot, int* cu, int* rows, int B, int T, void* stream) {
+  VTP_REQUIRE(ids && eot && cu && rows && B > 0 && T > 0, "vtp_text_row_plan: bad argument");
+  hipLaunchKernelGGL(text_row_plan_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, ids, eot, cu, rows, B, T);
+  return check_launch("text_row_plan");
+}
+
+extern "C" int vtp_embed_tokens_packed(const long* ids, const float* table, const float* pos, float* x, const int* cu, int B, int T,
+                                       int D, void* stream) {
+  VTP_REQUIRE(ids && table && pos && x && cu && B > 0 && T > 0 && D > 0 && D % 4 == 0, "vtp_embed_tokens_packed: bad argument (D %% 4 == 0)");
+  hipLaunchKernelGGL(embed_tokens_packed_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, ids, table, pos, x, cu, B, T, D);
+  return check_launch("embed_tokens_packed");
+}
+
+extern "C" int vtp_embed_tokens_bwd_packed(const long* ids, const float* dx, float* d_table, float* d_pos, const int* cu, int B, int T,
+                                           int D, void* stream) {
+  VTP_REQUIRE(ids && dx && d_table && d_pos && cu && B > 0 && T > 0 && D > 0, "vtp_embed_tokens_bwd_packed: bad argument");
+  hipLaunchKernelGGL(embed_tokens_bwd_packed_kernel, dim3(T), dim3(256), 0, (hipStream_t)stream, ids, dx, d_table, d_pos, cu, B, T, D);
+  return check_launch("embed_tokens_bwd_packed");
+}
+
+extern "C" int vtp_gather_rows_packed(const float* x, const int* cu, float* out, int B, int D, void* stream) {
+  VTP_REQUIRE(x && cu && out && B > 0 && D > 0, "vtp_gather_rows_packed: bad argument");
+  hipLaunchKernelGGL(gather_rows_packed_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, x, cu, out, B, D);
+  return check_launch("gather_rows_packed");
+}
+
+extern "C" int vtp_scatter_rows_packed(const float* dy, const int* cu, float* dx, void* dx_bf16, int B, int T, int D, void* stream) {
+  VTP_REQUIRE(dy && cu && dx && B > 0 && B <= 65535 && T > 0 && D > 0, "vtp_scatter_rows_packed: bad argument");
+  hipLaunchKernelGGL(scatter_rows_packed_kernel, dim3(T, B), dim3(256), 0, (hipStream_t)stream, dy, cu, dx, (bf16*)dx_bf16, B, T, D);
+  return check_launch("scatter_rows_packed");
 }
 
 extern "C" int vtp_l2norm_fwd(const float* x, float* y, float* inv_norm, int B, int D, float eps, void* stream) {

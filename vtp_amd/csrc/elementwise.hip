@@ -433,7 +433,9 @@ __global__ __launch_bounds__(256) void swiglu_bwd_rows_kernel(const bf16* __rest
 
 template <bool QUICK>
 __global__ __launch_bounds__(256) void gelu_bwd_kernel(const bf16* __restrict__ dy, const bf16* __restrict__ pre,
-                                                       bf16* __restrict__ dx, long n) {
+                                                       bf16* __restrict__ dx, long n, const int* __restrict__ m_rows = nullptr,
+                                                       int row_len = 0) {
+  if (m_rows) n = min(n, (long)*m_rows * row_len);  // device row limit: the first *m_rows rows of row_len elements
   const long n8 = n / 8;
   for (long i = blockIdx.x * 256L + threadIdx.x; i < n8; i += (long)gridDim.x * 256L) {
     bf16x8 g = *(const bf16x8*)(dy + 8 * i), p = *(const bf16x8*)(pre + 8 * i), o;
@@ -837,6 +839,19 @@ extern "C" int vtp_quick_gelu_bwd(const void* dy, const void* pre, void* dx, lon
   VTP_REQUIRE(dy && pre && dx && n > 0 && n % 8 == 0, "vtp_quick_gelu_bwd: bad argument (n %% 8 == 0)");
   hipLaunchKernelGGL(gelu_bwd_kernel<true>, dim3(grid_for(n / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16*)dy, (const bf16*)pre, (bf16*)dx, n);
   return check_launch("quick_gelu_bwd");
+}
+
+// GELU / QuickGELU backward over the rows [0, min(M, *m_rows)) of [M, H] operands (m_rows: device int; the grid is that of M rows)
+extern "C" int vtp_gelu_bwd_limit(const void* dy, const void* pre, void* dx, int M, int H, int quick, const int* m_rows, void* stream) {
+  VTP_REQUIRE(dy && pre && dx && m_rows && M > 0 && H > 0 && H % 8 == 0, "vtp_gelu_bwd_limit: bad argument (H %% 8 == 0)");
+  const long n = (long)M * H;
+  if (quick)
+    hipLaunchKernelGGL(gelu_bwd_kernel<true>, dim3(grid_for(n / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16*)dy, (const bf16*)pre,
+                       (bf16*)dx, n, m_rows, H);
+  else
+    hipLaunchKernelGGL(gelu_bwd_kernel<false>, dim3(grid_for(n / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16*)dy, (const bf16*)pre,
+                       (bf16*)dx, n, m_rows, H);
+  return check_launch("gelu_bwd_limit");
 }
 
 extern "C" int vtp_pixel_shuffle16(const void* t, float* img, int B, int h, int w, void* stream) {

@@ -30,8 +30,14 @@ namespace vtp {
 // the MFMA groups (their issue cost hides behind the matrix pipe) and the fragments of k-step ks+1 are read while the
 // MFMAs of k-step ks execute.
 template <int BM, int BN, int WAVES_M, int WAVES_N, int STAGES, int EPI, bool TRANS, bool PIPE>
-__global__ __launch_bounds__(64 * WAVES_M* WAVES_N) void gemm_nt_kernel(const GemmArgs p) {
+__global__ __launch_bounds__(64 * WAVES_M* WAVES_N) void gemm_nt_kernel(const GemmArgs p_in) {
   constexpr int BK = 64;
+  // device row limit (GemmArgs.m_rows, NT only): the tile list, the row clamps of the loads and the store predicates below all follow
+  // the effective M, so workgroups whose tiles lie beyond it leave before they stage anything; the grid is that of the static M
+  GemmArgs p = p_in;
+  if constexpr (!TRANS) {
+    if (p.m_rows) p.M = min(p.M, __builtin_amdgcn_readfirstlane(*p.m_rows));
+  }
   constexpr int NW = WAVES_M * WAVES_N;
   constexpr int WTM = BM / WAVES_M, WTN = BN / WAVES_N;  // wave tile
   constexpr int TM = WTM / 32, TN = WTN / 32;
@@ -584,9 +590,9 @@ extern "C" int vtp_gemm_nt_config(int M, int N, int K, int epilogue) {
   return cfg | (cs > 1 ? cs << 8 : 0);
 }
 
-extern "C" int vtp_gemm_nt(const void* A, int lda, const void* B, int ldb, void* C, int ldc, void* C2, int ldc2,
-                           const float* bias, const float* gamma, const float* resid, int M, int N, int K, int epilogue,
-                           int a_grp, int a_pre, int c_grp, int c_pre, int splits, float alpha, void* stream) {
+static int gemm_nt_impl(const void* A, int lda, const void* B, int ldb, void* C, int ldc, void* C2, int ldc2,
+                        const float* bias, const float* gamma, const float* resid, int M, int N, int K, int epilogue,
+                        int a_grp, int a_pre, int c_grp, int c_pre, int splits, float alpha, const int* m_rows, void* stream) {
   VTP_REQUIRE(A && B && C, "vtp_gemm_nt: null operand");
   VTP_REQUIRE(M > 0 && N > 0 && K > 0, "vtp_gemm_nt: bad shape M=%d N=%d K=%d", M, N, K);
   const int act_quick = epilogue == VTP_EPI_QUICK_GELU;  // the GELU epilogue with the other activation: same kernels, same dispatch
@@ -621,6 +627,22 @@ extern "C" int vtp_gemm_nt(const void* A, int lda, const void* B, int ldb, void*
     cs = (K + a.k_split - 1) / a.k_split;
     cfg = 8;
   }
+  if (m_rows) {
+    // a device row limit is honoured by the ring kernel alone: the persistent 256-wide kernels and every split-K / ticketed launch
+    // refuse it, and the shapes the table above gives them take the ring configuration it holds for them
+    VTP_REQUIRE(splits == 1 && epilogue <= VTP_EPI_GELU && a_grp == 0 && c_grp == 0,
+                "vtp_gemm_nt_limit: a row limit needs one K slice, a plain / fp32 / SwiGLU / GELU epilogue and no row remaps");
+    VTP_REQUIRE(g_force_cfg < 8, "vtp_gemm_nt_limit: the forced configuration %d takes no row limit (ring configurations only)", g_force_cfg);
+    if (cs > 1) {
+      cs = 1;
+      a.k_split = ks;
+    }
+    if (cfg >= 8) {
+      cfg = pick_cfg(M, N, K, epilogue, 1);
+      if (cfg >= 8) cfg = K >= 4096 ? 21 : 5;
+    }
+    a.m_rows = m_rows;
+  }
   switch (epilogue) {
     case VTP_EPI_BF16: return launch_gemm<EPI_BF16, false>(a, cs, cfg, s);
     case VTP_EPI_F32: return launch_gemm<EPI_F32, false>(a, cs, cfg, s);
@@ -633,6 +655,23 @@ extern "C" int vtp_gemm_nt(const void* A, int lda, const void* B, int ldb, void*
     default: VTP_REQUIRE(false, "vtp_gemm_nt: unknown epilogue %d", epilogue);
   }
   return VTP_OK;
+}
+
+extern "C" int vtp_gemm_nt(const void* A, int lda, const void* B, int ldb, void* C, int ldc, void* C2, int ldc2,
+                           const float* bias, const float* gamma, const float* resid, int M, int N, int K, int epilogue,
+                           int a_grp, int a_pre, int c_grp, int c_pre, int splits, float alpha, void* stream) {
+  return gemm_nt_impl(A, lda, B, ldb, C, ldc, C2, ldc2, bias, gamma, resid, M, N, K, epilogue, a_grp, a_pre, c_grp, c_pre, splits,
+                      alpha, nullptr, stream);
+}
+
+// vtp_gemm_nt over the rows [0, min(M, *m_rows)) only: m_rows is a DEVICE int read by the kernel, so the launch geometry (and a
+// captured graph) stays that of the static M while tiles, loads and stores follow the count.  Rows >= *m_rows of A are never read
+// and rows >= *m_rows of C / C2 never written; the rows below it are bit-identical to the unlimited launch on the same configuration.
+extern "C" int vtp_gemm_nt_limit(const void* A, int lda, const void* B, int ldb, void* C, int ldc, void* C2, int ldc2,
+                                const float* bias, const float* gamma, const float* resid, int M, int N, int K, int epilogue,
+                                float alpha, const int* m_rows, void* stream) {
+  VTP_REQUIRE(m_rows, "vtp_gemm_nt_limit: null row count");
+  return gemm_nt_impl(A, lda, B, ldb, C, ldc, C2, ldc2, bias, gamma, resid, M, N, K, epilogue, 0, 0, 0, 0, 1, alpha, m_rows, stream);
 }
 
 // w3 dgrad with the SwiGLU backward in its epilogue (ffn.py:78-81 backward): dh = dy W3 is formed per tile and leaves as

@@ -557,7 +557,8 @@ __global__ __launch_bounds__(512) void gemm8p_kernel(const GemmArgs p) {
 // split-major over the XCDs like the flat split-K launches.  The slices of a tile are combined in the launch by the last arriver
 // (gemm8p_body), which also applies the epilogue (C = C + sum or C = sum, SwiGLU row de-interleave, fused bias-gradient column sums):
 // no slab buffers, no reduce launches, no separate column-sum launches.
-__global__ __launch_bounds__(512) void gemm8p_grouped_tn_kernel(const GroupArgs ga) {
+template <bool LIMIT>
+__device__ __forceinline__ void gemm8p_grouped_tn_body(const GroupArgs& ga) {
   const int c = xcd_chunk_start(blockIdx.x, gridDim.x) + ((int)blockIdx.x >> 3);
   const int zslice = c / ga.ntiles, tile = c - zslice * ga.ntiles;
   int g = 0;
@@ -569,10 +570,18 @@ __global__ __launch_bounds__(512) void gemm8p_grouped_tn_kernel(const GroupArgs 
   p.M = (int)pr.M; p.N = (int)pr.N; p.K = ga.K; p.lda = (int)pr.lda; p.ldb = (int)pr.ldb; p.ldc = (int)pr.ldc;
   p.c_grp = (int)pr.c_grp; p.c_pre = (int)pr.c_pre; p.k_split = ga.k_split; p.alpha = 1.f; p.xcd_swizzle = 0;
   p.timing = ga.timing;
+  if constexpr (LIMIT) {  // device token count (one K slice): the K-tail zero-fill of the staging covers the last partial k-tile
+    p.K = min(p.K, __builtin_amdgcn_readfirstlane(*ga.k_rows));
+    p.k_split = (p.K + 63) & ~63;
+  }
   const int nt = ((p.M + 255) >> 8) * ((p.N + 255) >> 8);
   gemm8p_body<EPI_F32, true, 0>(p, tile - (int)pr.tile0, zslice, nt, true,
                                 GroupTile{ga.splits > 1 ? ga.part : nullptr, ga.ticket, tile, ga.splits});
 }
+
+__global__ __launch_bounds__(512) void gemm8p_grouped_tn_kernel(const GroupArgs ga) { gemm8p_grouped_tn_body<false>(ga); }
+// ... with the token count read from GroupArgs.k_rows (vtp_gemm_tn_grouped_limit; a kernel of its own: the launch above keeps its code)
+__global__ __launch_bounds__(512) void gemm8p_grouped_tn_limit_kernel(const GroupArgs ga) { gemm8p_grouped_tn_body<true>(ga); }
 
 // diagnostics (vtp_gemm_debug): stamp buffer and a cap on the persistent grid (0 = every CU)
 static unsigned long long* g_p8_timing = nullptr;
@@ -743,6 +752,26 @@ extern "C" int vtp_gemm_tn_grouped(const void* probs, int nprob, int ntiles, int
     attr_set = true;
   }
   hipLaunchKernelGGL(gemm8p_grouped_tn_kernel, dim3(ntiles * ga.splits), dim3(512), P8_LDS, (hipStream_t)stream, ga);
+  return check_launch("gemm8p_grouped_tn");
+}
+// vtp_gemm_tn_grouped over the token rows [0, min(K, *k_rows)) (k_rows: device int): one K slice per tile, so no workgroup ever waits on
+// the ticket of a slice that turned out empty, and no partial-sum scratch.  Rows >= *k_rows of the operands are never read.
+extern "C" int vtp_gemm_tn_grouped_limit(const void* probs, int nprob, int ntiles, int K, const int* k_rows, void* stream) {
+  using namespace vtp;
+  VTP_REQUIRE(probs && k_rows && nprob >= 1 && nprob <= 8, "vtp_gemm_tn_grouped_limit: 1..8 problems and a row count");
+  VTP_REQUIRE(ntiles >= 1 && K >= 1, "vtp_gemm_tn_grouped_limit: bad shape (ntiles %d, K %d)", ntiles, K);
+  GroupArgs ga{};
+  ga.probs = (const GroupProblem*)probs;
+  ga.nprob = nprob; ga.ntiles = ntiles; ga.K = K; ga.splits = 1;
+  ga.k_split = (K + 63) / 64 * 64;
+  ga.timing = g_p8_timing;
+  ga.k_rows = k_rows;
+  static bool attr_set = false;
+  if (!attr_set) {
+    hipFuncSetAttribute((const void*)gemm8p_grouped_tn_limit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, P8_LDS);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(gemm8p_grouped_tn_limit_kernel, dim3(ntiles), dim3(512), P8_LDS, (hipStream_t)stream, ga);
   return check_launch("gemm8p_grouped_tn");
 }
 // The same launch on the one-wave-per-SIMD kernel (gemm4w_tn.hip), from an explicit work-item list: items = device array of nitems

@@ -61,6 +61,9 @@ struct GemmArgs {
   // diagnostics (vtp_gemm_debug): per workgroup and tile, s_memrealtime stamps {tile start, k loop done, epilogue issued}; null = off
   unsigned long long* timing;
   int dbg_delay;  // diagnostics: > 0: every second workgroup (per XCD) starts this many 10-ns ticks late (lock-step experiments)
+  // device row limit (NT ring kernel only, vtp_gemm_nt_limit): the launch computes rows [0, min(M, *m_rows)) -- tiles beyond them return,
+  // loads are clamped to them, stores predicated on them; M stays the static launch geometry.  null: off.  No other kernel reads it.
+  const int* m_rows;
 };
 
 // XCD-aware order of an n-entry list (the tiles of a persistent launch, the workgroups of a flat one): workgroups are dealt to the 8

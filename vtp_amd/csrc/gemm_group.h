@@ -31,6 +31,9 @@ struct GroupArgs {
   int nprob, ntiles, splits, K, k_split;  // splits: slices per tile (8-phase kernel) | partial-sum slots per tile (item lists)
   unsigned long long* timing;
   const GroupItem* items;  // one-wave-per-SIMD kernel: one record per workgroup, never null | 8-phase kernel: unused (null)
+  // 8-phase kernel, one K slice only (vtp_gemm_tn_grouped_limit): device count of the token rows that hold data -- every problem sums
+  // over rows [0, min(K, *k_rows)) and no row beyond them is read.  null: off.  The item-list kernel does not read it.
+  const int* k_rows;
 };
 
 }  // namespace vtp

@@ -14,10 +14,13 @@ template <int KIND, int NC>  // KIND 0 rms, 1 layernorm; NC float4 chunks per la
 __global__ __launch_bounds__(256) void norm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                        const float* __restrict__ b, bf16* __restrict__ y,
                                                        float* __restrict__ stats, int M, int D, float eps,
-                                                       uint8_t* __restrict__ y8 = nullptr, const float* __restrict__ q_scale = nullptr) {
+                                                       uint8_t* __restrict__ y8 = nullptr, const float* __restrict__ q_scale = nullptr,
+                                                       const int* __restrict__ m_rows = nullptr) {
   // y8 / q_scale: the fp8 forward path -- the bf16-rounded output leaves as e4m3(y * q_scale[0]) (1 byte per element) instead
+  // m_rows: device row limit -- rows >= *m_rows are neither read nor written (the grid is that of the static M)
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (m_rows) M = min(M, *m_rows);
   if (row >= M) return;
   const float* xr = x + (size_t)row * D;
   f32x4 v[NC];
@@ -98,7 +101,9 @@ __global__ __launch_bounds__(256, 2) void norm_bwd_kernel(const bf16* __restrict
                                                        bf16* __restrict__ dxb, float* __restrict__ dw, float* __restrict__ db,
                                                        float* __restrict__ dxsum, int M, int D,
                                                        const float* __restrict__ pvec = nullptr, int prow0 = 0, int pB = 0,
-                                                       int pN = 1, const int* __restrict__ dres_rows = nullptr, int dres_M = 0) {
+                                                       int pN = 1, const int* __restrict__ dres_rows = nullptr, int dres_M = 0,
+                                                       const int* __restrict__ m_rows = nullptr) {
+  if (m_rows) M = min(M, *m_rows);  // device row limit: rows >= *m_rows are not read, not written and add nothing to dw / db / dxsum
   constexpr int R = NC <= 3 ? 2 : 1;  // rows in flight per wave: the x / dy loads of all R rows are issued before the first reduction
   const int lane = threadIdx.x & 63;
   const int wv_id = threadIdx.x >> 6;
@@ -283,6 +288,19 @@ extern "C" int vtp_norm_fwd(const float* x, const float* w, const float* b, void
   return check_launch("norm_fwd");
 }
 
+extern "C" int vtp_norm_fwd_limit(const float* x, const float* w, const float* b, void* y, float* stats, int M, int D, float eps,
+                                 int kind, const int* m_rows, void* stream) {
+  VTP_REQUIRE(x && w && y && m_rows, "vtp_norm_fwd_limit: null pointer");
+  VTP_REQUIRE(M > 0 && D > 0 && D % 4 == 0 && D <= NORM_MAXC * 256, "vtp_norm_fwd_limit: need 0 < D <= 2048, D %% 4 == 0 (D=%d)", D);
+  VTP_REQUIRE(kind == 0 || (kind == 1 && b), "vtp_norm_fwd_limit: kind must be 0 (rms) or 1 (layernorm, needs bias)");
+  dim3 grid(cdiv(M, 4)), block(256);
+  if (kind == 0)
+    NORM_DISPATCH(norm_fwd_kernel, 0, x, w, b, (bf16*)y, stats, M, D, eps, (uint8_t*)nullptr, (const float*)nullptr, m_rows);
+  else
+    NORM_DISPATCH(norm_fwd_kernel, 1, x, w, b, (bf16*)y, stats, M, D, eps, (uint8_t*)nullptr, (const float*)nullptr, m_rows);
+  return check_launch("norm_fwd_limit");
+}
+
 extern "C" int vtp_norm_fwd_e4m3(const float* x, const float* w, const float* b, void* y8, const float* q_scale, float* stats, int M,
                                  int D, float eps, int kind, void* stream) {
   VTP_REQUIRE(x && w && y8 && q_scale, "vtp_norm_fwd_e4m3: null pointer");
@@ -324,6 +342,26 @@ extern "C" int vtp_norm_bwd(const void* dy, const float* x, const float* w, cons
   else
     NORM_DISPATCH(norm_bwd_kernel, 1, (const bf16*)dy, x, w, stats, dres, dx, (bf16*)dx_bf16, dw, db, dx_colsum, M, D);
   return check_launch("norm_bwd");
+}
+
+// vtp_norm_bwd over the rows [0, min(M, *m_rows)) (m_rows: device int; the grid is that of the static M)
+extern "C" int vtp_norm_bwd_limit(const void* dy, const float* x, const float* w, const float* stats, const float* dres, float* dx,
+                                  void* dx_bf16, float* dw, float* db, float* dx_colsum, int M, int D, int kind, const int* m_rows,
+                                  void* stream) {
+  VTP_REQUIRE(dy && x && w && stats && dx && m_rows, "vtp_norm_bwd_limit: null pointer");
+  VTP_REQUIRE(!dx_colsum || dx_bf16, "vtp_norm_bwd_limit: dx_colsum sums the bf16 output and needs dx_bf16");
+  VTP_REQUIRE(M > 0 && D > 0 && D % 4 == 0 && D <= NORM_MAXC * 256, "vtp_norm_bwd_limit: need 0 < D <= 2048, D %% 4 == 0 (D=%d)", D);
+  VTP_REQUIRE(kind == 0 || kind == 1, "vtp_norm_bwd_limit: kind must be 0 or 1");
+  dim3 grid(norm_bwd_blocks(M, D)), block(256);
+  const bf16* dyb = (const bf16*)dy;
+  bf16* dxb = (bf16*)dx_bf16;
+  if (kind == 0)
+    NORM_DISPATCH(norm_bwd_kernel, 0, dyb, x, w, stats, dres, dx, dxb, dw, db, dx_colsum, M, D, (const float*)nullptr, 0, 0, 1,
+                  (const int*)nullptr, 0, m_rows);
+  else
+    NORM_DISPATCH(norm_bwd_kernel, 1, dyb, x, w, stats, dres, dx, dxb, dw, db, dx_colsum, M, D, (const float*)nullptr, 0, 0, 1,
+                  (const int*)nullptr, 0, m_rows);
+  return check_launch("norm_bwd_limit");
 }
 
 template <int KIND>

@@ -316,14 +316,17 @@ OVERLAP = Overlap()
 
 def linear_bwd(ws: Workspace, tag: str, L, dy_b, x_b, M: int, d_in, *, need_dx: bool = True, dy_remap=(0, 0),
                x_remap=(0, 0), dx_remap=(0, 0), gw=None, gb=None, N=None, K=None, wT=None, swiglu_h: int = 0,
-               bias_grad_done: bool = False, ls=None, dgrad_swiglu=None, defer=None):
+               bias_grad_done: bool = False, ls=None, dgrad_swiglu=None, defer=None, m_rows=None):
     """Backward of y[M,N] = x[M,K] W^T + b given dy (bf16 [M,N]):  dW += dy^T x,  db += colsum(dy),  dx = dy W.
     dx is an NT GEMM against the cached transposed weight W^T.  dW is a TN GEMM (ops.gemm_tn) straight from the activation layouts --
     no transposed copies; the transpose happens in the kernel's LDS reads -- split-K over the token dimension: slices write private
     fp32 slabs (plain stores) that one reduce kernel folds into the flat gradient; db is a column-sum launch beside it.  With `defer`
     (the transformer blocks) the problem is only recorded and the caller runs the block's weight gradients as ONE grouped launch
     (ops.WgradGroup: the 8-phase kernel, or the one-wave-per-SIMD kernel on a work-item list; K slices combined inside the launch,
-    column sums fused)."""
+    column sums fused).  m_rows (int32 [1] on the device; packed text captions): only the first m_rows[0] of the M token rows hold data --
+    the dgrad runs under that row limit and the recorded weight-gradient problem sums over those rows alone (grouped launches only)."""
+    if m_rows is not None and (defer is None or ls is not None or dgrad_swiglu is not None):
+        raise ValueError("linear_bwd: a device row limit needs the grouped weight-gradient path (defer) and a plain dgrad")
     if L is not None:
         N = L.N if N is None else N
         K = L.K if K is None else K
@@ -393,7 +396,7 @@ def linear_bwd(ws: Workspace, tag: str, L, dy_b, x_b, M: int, d_in, *, need_dx: 
         ops.gemm_dgrad_swiglu(dy_b, wT, dgrad_swiglu, d_in, M, K, N)
     elif need_dx:
         ops.gemm_nt(dy_b, wT, d_in, M=M, N=K, K=N, lda=dy_b.stride(0), ldb=N, ldc=d_in.stride(0), epi=EPI_BF16,
-                    a_remap=dy_remap, c_remap=dx_remap)
+                    a_remap=dy_remap, c_remap=dx_remap, m_rows=m_rows)
 
 
 class WgradGroups:
@@ -511,6 +514,11 @@ class Stack:
         # must accumulate like nn.Parameter.grad does, never does).  Saves the 256-KiB read of every output tile in the epilogue of the
         # step's dominant kernel: 38 -> 24 us per last-arriving workgroup (tools/wgrad_timeline.py)
         self.wgrad_overwrite = False
+        # packed captions (TextEngine, causal + arg-max pooling): (cu int32 [B + 1], rows int32 [1]) on the device -- sequence b of the one
+        # segment is the rows [cu[b], cu[b + 1]) of every token buffer and only the first rows[0] rows hold data.  Launch geometry stays
+        # that of the static M = B * T; the kernels read the counts (ops: m_rows / k_rows / the varlen attention).  Set by the owner
+        # before forward() and left in place for the matching backward(); None: padded rows.
+        self.varlen = None
 
     def _rope_plan(self, ws: Workspace, segs, prefix_tokens: int, M: int):
         """(rope_pos int32 [M], sin, cos) for the fused qkv + RoPE epilogue: rope_pos[m] = row of the concatenated per-segment
@@ -685,6 +693,11 @@ class Stack:
     def _attention(self, qkv, o, lse, rows, i: int, prefix_tokens: int, rope_qk: bool):
         """per-segment RoPE (unless the qkv projection applied it: rope_qk False) + attention over qkv [M, 3D] -> o [M, D]"""
         D, heads = self.D, self.heads
+        if self.varlen is not None:
+            (r0, Bs, Ns, rp), = rows
+            assert rp is None and self.causal
+            ops.attn_fwd_varlen(qkv, qkv[:, D:], qkv[:, 2 * D:], o, lse, self.varlen[0], Bs, Ns, heads, 3 * D, D, ATTN_SCALE)
+            return
         for r0, Bs, Ns, rp in rows:
             q_s, o_s = qkv[r0:r0 + Bs * Ns], o[r0:r0 + Bs * Ns]
             if rp is not None and rope_qk:
@@ -697,10 +710,11 @@ class Stack:
         """out = (resid +) proj(attn(rope(qkv(norm1(x)))));  returns (xn1, st1, qkv, o, lse).  proj=False: stops behind the attention
         (the caller projects a subset of the rows of o)"""
         D, heads, b = self.D, self.heads, self.blocks[i]
+        mr = None if self.varlen is None else self.varlen[1]
         xn1, st1 = ws.get(t + "xn1", (M, D), BF), ws.get(t + "st1", (M, 2), F32)
         qkv, o = ws.get(t + "qkv", (M, 3 * D), BF), ws.get(t + "o", (M, D), BF)
         lse = ws.get(t + "lse", (M * heads,), F32)  # per segment [B_i, heads, N_i]
-        ops.norm_fwd(x, b.n1w, b.n1b, xn1, st1, M, D, self.eps, self.kind)
+        ops.norm_fwd(x, b.n1w, b.n1b, xn1, st1, M, D, self.eps, self.kind, m_rows=mr)
         if rope_plan is not None:  # apply_rope rides in the epilogue of the qkv projection (all segments, one launch)
             ps, pc = self._plan_tabs(rope_plan, i)
             ops.gemm_qkv_rope(xn1, b.qkv.w, b.qkv.bias, qkv, M, 3 * D, D, rope_plan[0], ps, pc, 2 * D)
@@ -710,25 +724,26 @@ class Stack:
             ops.gemm_nt(xn1, b.qkv.w, qkv_pre, M=M, N=3 * D, K=D, bias=b.qkv.bias, epi=EPI_BF16)
             ops.qk_norm_fwd(qkv_pre, b.qn_w, b.kn_w, qkv, qinv, M, D)
         else:
-            ops.gemm_nt(xn1, b.qkv.w, qkv, M=M, N=3 * D, K=D, bias=b.qkv.bias, epi=EPI_BF16)
+            ops.gemm_nt(xn1, b.qkv.w, qkv, M=M, N=3 * D, K=D, bias=b.qkv.bias, epi=EPI_BF16, m_rows=mr)
         self._attention(qkv, o, lse, rows, i, prefix_tokens, rope_plan is None)
         if proj:
-            ops.gemm_nt(o, b.proj.w, out, M=M, N=D, K=D, bias=b.proj.bias, gamma=b.ls1, resid=resid, epi=EPI_F32)
+            ops.gemm_nt(o, b.proj.w, out, M=M, N=D, K=D, bias=b.proj.bias, gamma=b.ls1, resid=resid, epi=EPI_F32, m_rows=mr)
         return xn1, st1, qkv, o, lse
 
     def _ffn_fwd(self, ws: Workspace, t: str, i: int, x, out, resid, M: int, train: bool):
         """out = (resid +) w3(act(w12 / fc(norm2(x))));  returns (xn2, st2, pre, hid) -- pre (the FFN pre-activations) only in training"""
         D, H, b = self.D, self.H, self.blocks[i]
+        mr = None if self.varlen is None else self.varlen[1]
         xn2, st2 = ws.get(t + "xn2", (M, D), BF), ws.get(t + "st2", (M, 2), F32)
         pre = ws.get(t + "x12", (M, 2 * H if self.swiglu else H), BF) if train else None
         hid = ws.get(t + "hid", (M, H), BF)
-        ops.norm_fwd(x, b.n2w, b.n2b, xn2, st2, M, D, self.eps, self.kind)
+        ops.norm_fwd(x, b.n2w, b.n2b, xn2, st2, M, D, self.eps, self.kind, m_rows=mr)
         if self.swiglu:
-            ops.gemm_nt(xn2, b.w12.w12, hid, M=M, N=2 * H, K=D, c2=pre, ldc2=2 * H, bias=b.w12.b12, epi=EPI_SWIGLU)
+            ops.gemm_nt(xn2, b.w12.w12, hid, M=M, N=2 * H, K=D, c2=pre, ldc2=2 * H, bias=b.w12.b12, epi=EPI_SWIGLU, m_rows=mr)
         else:  # Mlp FFN (ffn_layer = "mlp", ffn.py:21-48; the text tower's c_fc / c_proj): fc1 -> GELU -> fc2
             ops.gemm_nt(xn2, b.fc.w, hid, M=M, N=H, K=D, c2=pre, ldc2=H, bias=b.fc.bias,
-                        epi=ops.EPI_QUICK_GELU if self.quick_gelu else EPI_GELU)
-        ops.gemm_nt(hid, b.w3.w, out, M=M, N=D, K=H, bias=b.w3.bias, gamma=b.ls2, resid=resid, epi=EPI_F32)
+                        epi=ops.EPI_QUICK_GELU if self.quick_gelu else EPI_GELU, m_rows=mr)
+        ops.gemm_nt(hid, b.w3.w, out, M=M, N=D, K=H, bias=b.w3.bias, gamma=b.ls2, resid=resid, epi=EPI_F32, m_rows=mr)
         return xn2, st2, pre, hid
 
     def _ffn_bwd(self, ws: Workspace, i: int, s: BlockSaved, dy, dy_b, dx, dx_b, M: int, bt: str, dpre, *, fused: bool,
@@ -736,9 +751,10 @@ class Stack:
         """dy / dy_b: gradient of the FFN branch output (f32 / bf16 copy); dx (+ dx_b) = dy + the gradient through the branch into its
         input.  fused: the SwiGLU backward rides in the w3 dgrad's epilogue.  probs: collects the grouped weight-gradient problems."""
         D, H, b = self.D, self.H, self.blocks[i]
+        mr = None if self.varlen is None else self.varlen[1]
         dh, dxn = ws.get(bt + "dh", (M, H), BF), ws.get(bt + "dxn", (M, D), BF)
         linear_bwd(ws, "w3", b.w3, dy_b, s.hid, M, dpre if fused else dh, bias_grad_done=bias_done,
-                   ls=(b.ls2, b.gls2) if b.ls2 is not None else None, dgrad_swiglu=s.pre if fused else None, defer=probs)
+                   ls=(b.ls2, b.gls2) if b.ls2 is not None else None, dgrad_swiglu=s.pre if fused else None, defer=probs, m_rows=mr)
         OVERLAP.run_deferred()  # side work forked at the block boundary: behind the block's first main-stream kernel
         if self.swiglu:
             if not fused:
@@ -746,9 +762,9 @@ class Stack:
             linear_bwd(ws, "w12", None, dpre, s.xn2, M, dxn, N=2 * H, K=D, gw=b.w12.gw1, gb=b.w12.gb1, wT=b.w12.w12T, swiglu_h=H,
                        defer=probs)
         else:
-            ops.gelu_bwd(dh, s.pre, dpre, M * H, quick=self.quick_gelu)
-            linear_bwd(ws, "fc", b.fc, dpre, s.xn2, M, dxn, defer=probs)
-        ops.norm_bwd(dxn, s.ffn_in, b.n2w, s.st2, dy, dx, dx_b, b.gn2w, b.gn2b, M, D, self.kind, dx_colsum=dx_colsum)
+            ops.gelu_bwd(dh, s.pre, dpre, M * H, quick=self.quick_gelu, m_rows=mr, H=H)
+            linear_bwd(ws, "fc", b.fc, dpre, s.xn2, M, dxn, defer=probs, m_rows=mr)
+        ops.norm_bwd(dxn, s.ffn_in, b.n2w, s.st2, dy, dx, dx_b, b.gn2w, b.gn2b, M, D, self.kind, dx_colsum=dx_colsum, m_rows=mr)
 
     def _attn_bwd(self, ws: Workspace, t: str, i: int, s: BlockSaved, dy, dy_b, dx, dx_b, M: int, bt: str, dqkv, rows,
                   prefix_tokens: int, *, bias_done: bool = False, probs=None, join: bool = False, dx_colsum=None):
@@ -757,6 +773,7 @@ class Stack:
         gradients: the projection's dgrad and weight gradient run on them, d_o is expanded to all M rows for the attention backward
         (every row is a key / value), and norm1's backward picks its residual gradient through the row map."""
         D, heads, b = self.D, self.heads, self.blocks[i]
+        mr = None if self.varlen is None else self.varlen[1]
         d_o, dxn = ws.get(bt + "do", (M, D), BF), ws.get(bt + "dxn", (M, D), BF)
         delta = ws.get(bt + "delta", (M * heads,), F32)
         if s.row_map is not None:
@@ -769,7 +786,12 @@ class Stack:
             ops.expand_rows_bf16(d_o_c, s.row_map, d_o, M, Mc, D)
         else:
             linear_bwd(ws, "proj", b.proj, dy_b, s.o, M, d_o, bias_grad_done=bias_done,
-                       ls=(b.ls1, b.gls1) if b.ls1 is not None else None, defer=probs)
+                       ls=(b.ls1, b.gls1) if b.ls1 is not None else None, defer=probs, m_rows=mr)
+        if self.varlen is not None:
+            (r0, Bs, Ns, rp), = rows
+            ops.attn_bwd_varlen(s.qkv, s.qkv[:, D:], s.qkv[:, 2 * D:], s.o, d_o, s.lse, delta, dqkv, dqkv[:, D:], dqkv[:, 2 * D:],
+                                self.varlen[0], Bs, Ns, heads, 3 * D, D, ATTN_SCALE)
+            rows = ()
         for r0, Bs, Ns, rp in rows:
             r1 = r0 + Bs * Ns
             q_s, dq_s = s.qkv[r0:r1], dqkv[r0:r1]
@@ -780,13 +802,22 @@ class Stack:
         if b.qn_w is not None:  # gradient w.r.t. the normalised q, k -> w.r.t. the projection output (in place), + dw
             ops.qk_norm_bwd(dqkv, ws.get(t + "qkv_pre", (M, 3 * D), BF), ws.get(t + "qinv", (M, 2 * heads), F32), b.qn_w, b.kn_w,
                             b.g_qn, b.g_kn, M, D)
-        linear_bwd(ws, "qkv", b.qkv, dqkv, s.xn1, M, dxn, defer=probs)
+        linear_bwd(ws, "qkv", b.qkv, dqkv, s.xn1, M, dxn, defer=probs, m_rows=mr)
         if join:
             OVERLAP.join()
         if s.row_map is not None:
             ops.norm_bwd_rows(dxn, s.attn_in, b.n1w, s.st1, dy, s.row_map, dx, dx_b, b.gn1w, b.gn1b, M, D, self.kind, dx_colsum=dx_colsum)
         else:
-            ops.norm_bwd(dxn, s.attn_in, b.n1w, s.st1, dy, dx, dx_b, b.gn1w, b.gn1b, M, D, self.kind, dx_colsum=dx_colsum)
+            ops.norm_bwd(dxn, s.attn_in, b.n1w, s.st1, dy, dx, dx_b, b.gn1w, b.gn1b, M, D, self.kind, dx_colsum=dx_colsum, m_rows=mr)
+
+    def varlen_ok(self, M: int) -> bool:
+        """may a pass over M static token rows run on packed captions (self.varlen)?  Causal blocks without RoPE, QK norm, LayerScale,
+        stochastic depth or the fp8 forward, and a token count at which the backward takes the grouped weight gradients (the only
+        weight-gradient path that reads the row count)"""
+        D, H = self.D, self.H
+        return (self.causal and not self.qk_norm and self.drop_plan is None and getattr(self, "fp8", None) is None
+                and all(b.ls1 is None and b.ls2 is None for b in self.blocks) and M >= 256 and D % 8 == 0 and H % 8 == 0
+                and ops.wgrad_group_fits(M, max(3 * D, 2 * H if self.swiglu else H)))
 
     # x: f32 [M, D] input residual.  Returns the output residual (f32 [M, D]).
     def tail_rows_ok(self, train: bool) -> bool:
@@ -809,6 +840,8 @@ class Stack:
         M = sum(b * n for b, n, _ in segs)
         if tail is not None and not self.tail_rows_ok(train):
             raise RuntimeError("Stack.forward: a tail row plan was passed to a pass that cannot take one (tail_rows_ok)")
+        if self.varlen is not None and not (self.varlen_ok(M) and tail is None and len(segs) == 1 and segs[0][2] is None):
+            raise RuntimeError("Stack.forward: packed captions were set on a pass that cannot take them (varlen_ok, one segment, no RoPE)")
         fp8 = getattr(self, "fp8", None)
         if fp8 is not None and fp8["ready"] and not train:
             return self._forward_fp8(ws, x, segs, prefix_tokens, M)
@@ -960,6 +993,9 @@ class Stack:
         # stochastic depth and small token counts take the per-layer launches (ring-kernel fallback inside).
         grouped = not drop and M >= 256 and all(b.ls1 is None and b.ls2 is None for b in self.blocks) \
             and ops.wgrad_group_fits(M, max(3 * D, 2 * H if self.swiglu else H)) and D % 8 == 0 and H % 8 == 0
+        vl = self.varlen
+        if vl is not None and not (grouped and tail_Mc is None and len(segs) == 1 and not extra_last):
+            raise RuntimeError("Stack.backward: packed captions need the grouped weight gradients of one plain segment (varlen_ok)")
         par = (lambda i: f".{i & 1}") if grouped else (lambda i: "")
         groups = ws.__dict__.setdefault("_wgrad_groups", {})
         scratch = self.__dict__.setdefault("_wgrad_scratch", {})
@@ -1021,7 +1057,7 @@ class Stack:
                 yield ("block", i)
                 continue
             extra = [dict(pr, dy=dy_b) for pr in extra_last] if (i == 0 and hold_last and extra_last) else []
-            gkey = (i, bool(self.wgrad_overwrite), len(extra), Mf)
+            gkey = (i, bool(self.wgrad_overwrite), len(extra), Mf, vl is not None)
             grp = groups.get(gkey)
             if grp is None:
                 # problems over different token counts (tail rows: proj / w12 / w3 over Mc rows beside qkv over all M) share the
@@ -1031,7 +1067,7 @@ class Stack:
                     counts = [None]
                 parts = []
                 for kt in counts:
-                    g = ops.WgradGroup(M if kt is None else kt)
+                    g = ops.WgradGroup(M if kt is None else kt, k_rows=None if vl is None else vl[1])
                     for pr in probs + extra:
                         if kt is None or pr.get("Ktok", M) == kt:
                             g.add(pr["dy"], pr["x"], pr["gw"], pr["gb"], pr["N"], pr["K"], pr["swiglu_h"],

@@ -28,8 +28,9 @@ def pad8(n: int) -> int:
 
 
 def gemm_nt(a, b, c, *, M=None, N=None, K=None, lda=None, ldb=None, ldc=None, c2=None, ldc2=0, bias=None, gamma=None,
-            resid=None, epi=EPI_BF16, a_remap=(0, 0), c_remap=(0, 0), splits=1, alpha=1.0):
-    """c[M,N] = epi(alpha * a[M,K] @ b[N,K]^T).  a, b bf16 (K-contiguous rows)."""
+            resid=None, epi=EPI_BF16, a_remap=(0, 0), c_remap=(0, 0), splits=1, alpha=1.0, m_rows=None):
+    """c[M,N] = epi(alpha * a[M,K] @ b[N,K]^T).  a, b bf16 (K-contiguous rows).  m_rows (int32 [1] on the device): only the rows
+    [0, min(M, m_rows[0])) are computed -- the rest of a is not read, the rest of c not written (ring kernel, static launch geometry)."""
     M = a.shape[0] if M is None else M
     K = a.shape[1] if K is None else K
     N = b.shape[0] if N is None else N
@@ -38,6 +39,12 @@ def gemm_nt(a, b, c, *, M=None, N=None, K=None, lda=None, ldb=None, ldc=None, c2
     ldc = c.stride(0) if ldc is None else ldc
     if c2 is not None and not ldc2:
         ldc2 = c2.stride(0)
+    if m_rows is not None:
+        if a_remap != (0, 0) or c_remap != (0, 0) or splits != 1:
+            raise ValueError("gemm_nt: a row limit takes no row remaps and one K slice")
+        _lib.check(_lib_().vtp_gemm_nt_limit(_p(a), lda, _p(b), ldb, _p(c), ldc, _p(c2), ldc2, _p(bias), _p(gamma), _p(resid), M, N, K,
+                                             epi, alpha, _p(m_rows), _s()), "vtp_gemm_nt_limit")
+        return
     rc = _lib_().vtp_gemm_nt(_p(a), lda, _p(b), ldb, _p(c), ldc, _p(c2), ldc2, _p(bias), _p(gamma), _p(resid), M, N, K,
                              epi, a_remap[0], a_remap[1], c_remap[0], c_remap[1], splits, alpha, _s())
     _lib.check(rc, "vtp_gemm_nt")
@@ -49,11 +56,19 @@ def gemm_qkv_rope(a, w, bias, c, M, N, K, rope_pos, rope_sin, rope_cos, rope_col
                                          _p(rope_pos), _p(rope_sin), _p(rope_cos), rope_cols, _s()), "vtp_gemm_qkv_rope")
 
 
-def norm_fwd(x, w, b, y, stats, M, D, eps, kind):
+def norm_fwd(x, w, b, y, stats, M, D, eps, kind, m_rows=None):
+    """m_rows (here and below): int32 [1] on the device -- the kernel works on the rows [0, min(M, m_rows[0])) only"""
+    if m_rows is not None:
+        _lib.check(_lib_().vtp_norm_fwd_limit(_p(x), _p(w), _p(b), _p(y), _p(stats), M, D, eps, kind, _p(m_rows), _s()), "vtp_norm_fwd_limit")
+        return
     _lib.check(_lib_().vtp_norm_fwd(_p(x), _p(w), _p(b), _p(y), _p(stats), M, D, eps, kind, _s()), "vtp_norm_fwd")
 
 
-def norm_bwd(dy, x, w, stats, dres, dx, dxb, dw, db, M, D, kind, dx_colsum=None):
+def norm_bwd(dy, x, w, stats, dres, dx, dxb, dw, db, M, D, kind, dx_colsum=None, m_rows=None):
+    if m_rows is not None:
+        _lib.check(_lib_().vtp_norm_bwd_limit(_p(dy), _p(x), _p(w), _p(stats), _p(dres), _p(dx), _p(dxb), _p(dw), _p(db), _p(dx_colsum),
+                                              M, D, kind, _p(m_rows), _s()), "vtp_norm_bwd_limit")
+        return
     _lib.check(_lib_().vtp_norm_bwd(_p(dy), _p(x), _p(w), _p(stats), _p(dres), _p(dx), _p(dxb), _p(dw), _p(db), _p(dx_colsum),
                                     M, D, kind, _s()), "vtp_norm_bwd")
 
@@ -94,6 +109,18 @@ def attn_bwd(q, k, v, o, d_o, lse, delta, dq, dk, dv, B, N, heads, sb, sn, sbo, 
     rs, rc = (rope[0], rope[1]) if rope is not None else (None, None)
     _lib.check(_lib_().vtp_attn_bwd(_p(q), _p(k), _p(v), _p(o), _p(d_o), _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), _p(rs),
                                     _p(rc), rope_prefix, B, N, heads, sb, sn, sbo, sno, scale, int(causal), _s()), "vtp_attn_bwd")
+
+
+def attn_fwd_varlen(q, k, v, o, lse, cu, B, Nmax, heads, sn, sno, scale):
+    """causal attention over packed captions: batch b = rows [cu[b], cu[b + 1]) of the packed buffers (cu int32 [B + 1] on the device);
+    lse keeps the padded [B, heads, Nmax] layout"""
+    _lib.check(_lib_().vtp_attn_fwd_varlen(_p(q), _p(k), _p(v), _p(o), _p(lse), _p(cu), B, Nmax, heads, sn, sno, scale, _s()),
+               "vtp_attn_fwd_varlen")
+
+
+def attn_bwd_varlen(q, k, v, o, d_o, lse, delta, dq, dk, dv, cu, B, Nmax, heads, sn, sno, scale):
+    _lib.check(_lib_().vtp_attn_bwd_varlen(_p(q), _p(k), _p(v), _p(o), _p(d_o), _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), _p(cu), B, Nmax,
+                                           heads, sn, sno, scale, _s()), "vtp_attn_bwd_varlen")
 
 
 def im2col16(img, patches, B, H, W):
@@ -155,8 +182,11 @@ def swiglu_bwd(dh, x12, dx12, M, H, db12=None):
     _lib.check(_lib_().vtp_swiglu_bwd(_p(dh), _p(x12), _p(dx12), _p(db12), M, H, _s()), "vtp_swiglu_bwd")
 
 
-def gelu_bwd(dy, pre, dx, n, quick: bool = False):
-    if quick:
+def gelu_bwd(dy, pre, dx, n, quick: bool = False, m_rows=None, H: int = 0):
+    """m_rows: the operands are [n / H, H] and only their first min(n / H, m_rows[0]) rows are processed"""
+    if m_rows is not None:
+        _lib.check(_lib_().vtp_gelu_bwd_limit(_p(dy), _p(pre), _p(dx), n // H, H, int(quick), _p(m_rows), _s()), "vtp_gelu_bwd_limit")
+    elif quick:
         _lib.check(_lib_().vtp_quick_gelu_bwd(_p(dy), _p(pre), _p(dx), n, _s()), "vtp_quick_gelu_bwd")
     else:
         _lib.check(_lib_().vtp_gelu_bwd(_p(dy), _p(pre), _p(dx), n, _s()), "vtp_gelu_bwd")
@@ -326,7 +356,10 @@ class WgradGroup:
     over the same token rows.  add() the problems, finalize() once (the operand buffers are static: the device descriptor table
     is built a single time), launch() every step."""
 
-    def __init__(self, Ktok: int):
+    def __init__(self, Ktok: int, k_rows=None):
+        """k_rows (int32 [1] on the device): the problems sum over the token rows [0, min(Ktok, k_rows[0])) only and read no row beyond
+        them (vtp_gemm_tn_grouped_limit: the 8-phase kernel, one K slice per tile)"""
+        self.k_rows = k_rows
         self.Ktok, self.rows, self.ntiles, self.keep = int(Ktok), [], 0, []
         self.table = self.part = self.ticket = None
         self._uniform = {}  # splits -> (items, nitems, slots): uniform lists of a forced launch(kernel=1)
@@ -366,6 +399,11 @@ class WgradGroup:
                              "use the per-layer weight-gradient path (linear_bwd without `defer`)")
         _, self.splits = wgrad_group_splits(self.ntiles, self.Ktok)
         self.table = torch.tensor(self.rows, dtype=torch.int64, device=device)
+        if self.k_rows is not None:  # a device token count: one slice (a slice may turn out empty, and nobody may wait on its ticket)
+            if self.mixed:
+                raise ValueError("WgradGroup: a device token count takes one static token count for every problem")
+            self.splits, self.kernel, self.items, self.nitems, self.slots = 1, 0, None, None, 1
+            return self
         self.kernel = 1 if self.mixed else wgrad_group_kernel(self.ntiles, self.splits, self.Ktok)
         self.items, self.nitems, self.slots = None, None, self.splits
         if self.kernel == 1:  # uneven cut: the tiles with bias-gradient work get one slice more (wgrad_group_items)
@@ -388,6 +426,12 @@ class WgradGroup:
         current self.splits written as a list -- None = the measured choice made by finalize() (ops.wgrad_group_kernel)"""
         if kernel is None:
             kernel = self.kernel
+        if self.k_rows is not None:
+            if kernel != 0:
+                raise ValueError("WgradGroup.launch: a device token count runs on the 8-phase kernel only")
+            _lib.check(_lib_().vtp_gemm_tn_grouped_limit(_p(self.table), len(self.rows), self.ntiles, self.Ktok, _p(self.k_rows), _s()),
+                       "vtp_gemm_tn_grouped_limit")
+            return
         if kernel == 0 and self.mixed:
             raise ValueError("WgradGroup.launch: the 8-phase kernel takes one token count for every problem")
         if kernel == 0:
@@ -479,6 +523,29 @@ def gather_rows(x, idx, out, B, T, D):
 
 def scatter_rows(dy, idx, dx, dxb, B, T, D):
     _lib.check(_lib_().vtp_scatter_rows(_p(dy), _p(idx), _p(dx), _p(dxb), B, T, D, _s()), "vtp_scatter_rows")
+
+
+def text_row_plan(ids, eot, cu, rows, B, T):
+    """the packed-caption plan, on the device: eot int32 [B] (first arg-max of every caption), cu int32 [B + 1] (exclusive prefix sum of
+    eot + 1), rows int32 [1] (= cu[B], the live row count)"""
+    _lib.check(_lib_().vtp_text_row_plan(_p(ids), _p(eot), _p(cu), _p(rows), B, T, _s()), "vtp_text_row_plan")
+
+
+def embed_tokens_packed(ids, table, pos, x, cu, B, T, D):
+    _lib.check(_lib_().vtp_embed_tokens_packed(_p(ids), _p(table), _p(pos), _p(x), _p(cu), B, T, D, _s()), "vtp_embed_tokens_packed")
+
+
+def embed_tokens_bwd_packed(ids, dx, d_table, d_pos, cu, B, T, D):
+    _lib.check(_lib_().vtp_embed_tokens_bwd_packed(_p(ids), _p(dx), _p(d_table), _p(d_pos), _p(cu), B, T, D, _s()),
+               "vtp_embed_tokens_bwd_packed")
+
+
+def gather_rows_packed(x, cu, out, B, D):
+    _lib.check(_lib_().vtp_gather_rows_packed(_p(x), _p(cu), _p(out), B, D, _s()), "vtp_gather_rows_packed")
+
+
+def scatter_rows_packed(dy, cu, dx, dxb, B, T, D):
+    _lib.check(_lib_().vtp_scatter_rows_packed(_p(dy), _p(cu), _p(dx), _p(dxb), B, T, D, _s()), "vtp_scatter_rows_packed")
 
 
 def l2norm_fwd(x, y, inv, B, D, eps=1e-12):
