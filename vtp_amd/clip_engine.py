@@ -8,7 +8,7 @@ from typing import Dict, Optional
 import torch
 
 from . import ops
-from .engine import BF, F32, OVERLAP, ParamStore, Stack, Workspace, _env_flag, linear_bwd
+from .engine import BF, F32, OVERLAP, ParamStore, RowPlan, Stack, Workspace, _env_flag, linear_bwd
 from .ops import EPI_BF16, EPI_F32
 
 I32 = torch.int32
@@ -54,7 +54,7 @@ class TextEngine:
         eot = ws.get("eot", (B,), I32)
         plan = None
         if self.packed and _env_flag("VTP_TEXT_VARLEN") and self.stack.varlen_ok(B * T):
-            plan = (ws.get("cu", (B + 1,), I32), ws.get("rows", (1,), I32))
+            plan = RowPlan(ws.get("cu", (B + 1,), I32), ws.get("rows", (1,), I32))
         self.stack.varlen = plan
         if plan is not None:
             cu, rows = plan
@@ -128,14 +128,14 @@ class TextEngine:
         dx = ws.get("b.dxt", (B * T, D), F32)
         dx_b = ws.get("b.dxt_b", (B * T, D), BF)
         if plan is not None:
-            ops.scatter_rows_packed(d_pooled, plan[0], dx, dx_b, B, T, D)
+            ops.scatter_rows_packed(d_pooled, plan.cu, dx, dx_b, B, T, D)
         else:
             ops.scatter_rows(d_pooled, eot, dx, dx_b, B, T, D)
         OVERLAP.join()
         yield "tail"
         dx0, _ = yield from self.stack.backward(ws, dx, dx_b, [(B, T, None)], 0)
         if plan is not None:
-            ops.embed_tokens_bwd_packed(ids, dx0, st.g("token_embedding.weight"), st.g("positional_embedding"), plan[0], B, T, D)
+            ops.embed_tokens_bwd_packed(ids, dx0, st.g("token_embedding.weight"), st.g("positional_embedding"), plan.cu, B, T, D)
         else:
             ops.embed_tokens_bwd(ids, dx0, st.g("token_embedding.weight"), st.g("positional_embedding"), B, T, D)
         OVERLAP.join()

@@ -17,6 +17,7 @@
 // tiles read transposed use a 192-B row stride (the 4 rows x 64 B of a half-wave land on disjoint bank quarters).
 #include "common.h"
 #include <cstdlib>
+#include <type_traits>
 #include "vtp_hip.h"
 
 namespace vtp {
@@ -442,23 +443,51 @@ static int check_attn(const char* who, int B, int N, int heads, long sb, long sn
   return VTP_OK;
 }
 
+// cu != null: the causal tiled kernels over PACKED captions.  Batch b is the rows [cu[b], cu[b + 1]) (cu int32 [B + 1] on the device) of
+// the packed [rows, 3 * heads * 64] qkv and [rows, heads * 64] o buffers, at most N rows each (sb / sbo unused).  The grid is the padded
+// launch's and lse / delta keep the padded [B, heads, N] layout; rows outside the batches are neither read nor written.
+static AttnArgs attn_args(const void* q, const void* k, const void* v, const void* o, const void* d_o, void* out, const float* lse,
+                          float* delta, void* dq, void* dk, void* dv, const int* cu, int B, int N, int heads, long sb, long sn, long sbo,
+                          long sno, float scale) {
+  AttnArgs a = {};
+  a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.o = (const bf16*)o; a.d_o = (const bf16*)d_o;
+  a.out = (bf16*)out; a.lse = (float*)lse; a.delta = delta; a.dq = (bf16*)dq; a.dk = (bf16*)dk; a.dv = (bf16*)dv;
+  a.B = B; a.N = N; a.heads = heads; a.sb = sb; a.sn = sn; a.sbo = sbo; a.sno = sno; a.scale = scale; a.cu = cu;
+  return a;
+}
+
+static void launch_attn_tiled_fwd(const AttnArgs& a, int causal, hipStream_t s) {
+  const dim3 grid(cdiv(a.N, 128), a.heads, a.B), block(256);
+  if (!a.cu && causal) hipLaunchKernelGGL(attn_fwd_kernel<true>, grid, block, 0, s, a);
+  else if (!a.cu) hipLaunchKernelGGL(attn_fwd_kernel<false>, grid, block, 0, s, a);
+  else hipLaunchKernelGGL((attn_fwd_kernel<true, true>), grid, block, 0, s, a);
+}
+
+static void launch_attn_tiled_bwd(const AttnArgs& a, int causal, hipStream_t s) {
+  const long rows8 = (long)a.B * a.heads * a.N * 8;
+  int dblocks = (int)((rows8 + 255) / 256);
+  if (dblocks > 4096) dblocks = 4096;
+  const dim3 grid(cdiv(a.N, 128), a.heads, a.B), block(256);
+  auto run = [&](auto c, auto vl) {  // delta, then dq, then dk / dv
+    hipLaunchKernelGGL(attn_delta_kernel<decltype(vl)::value>, dim3(dblocks), block, 0, s, a);
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<decltype(c)::value, decltype(vl)::value>), grid, block, 0, s, a);
+    hipLaunchKernelGGL((attn_bwd_dkv_kernel<decltype(c)::value, decltype(vl)::value>), grid, block, 0, s, a);
+  };
+  if (!a.cu && causal) run(std::true_type{}, std::false_type{});
+  else if (!a.cu) run(std::false_type{}, std::false_type{});
+  else run(std::true_type{}, std::true_type{});
+}
+
 extern "C" int vtp_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B, int N, int heads,
                             long sb_qkv, long sn_qkv, long sb_o, long sn_o, float scale, int causal, void* stream) {
   VTP_REQUIRE(q && k && v && o, "vtp_attn_fwd: null pointer");
   if (int e = check_attn("vtp_attn_fwd", B, N, heads, sb_qkv, sn_qkv, sb_o, sn_o)) return e;
-  AttnArgs a = {};
-  a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.out = (bf16*)o; a.lse = lse;
-  a.B = B; a.N = N; a.heads = heads; a.sb = sb_qkv; a.sn = sn_qkv; a.sbo = sb_o; a.sno = sn_o; a.scale = scale;
   if (use_resident(N, causal))
     return attn_resident_fwd(q, k, v, o, lse, B, N, heads, sb_qkv, sn_qkv, sb_o, sn_o, scale, (hipStream_t)stream);
-  dim3 grid(cdiv(N, 128), heads, B);
-  if (causal) hipLaunchKernelGGL(attn_fwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(attn_fwd_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, a);
+  const AttnArgs a = attn_args(q, k, v, 0, 0, o, lse, 0, 0, 0, 0, nullptr, B, N, heads, sb_qkv, sn_qkv, sb_o, sn_o, scale);
+  launch_attn_tiled_fwd(a, causal, (hipStream_t)stream);
   return check_launch("attn_fwd");
 }
-
-extern "C" int vtp_rope_qk(void* qkv, const void* sin, const void* cos, int B, int N, int heads, int prefix, int inverse,
-                           void* stream);
 
 extern "C" int vtp_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse,
                             float* delta, void* dq, void* dk, void* dv, const void* rope_sin, const void* rope_cos,
@@ -468,26 +497,11 @@ extern "C" int vtp_attn_bwd(const void* q, const void* k, const void* v, const v
   VTP_REQUIRE((rope_sin == nullptr) == (rope_cos == nullptr), "vtp_attn_bwd: rope_sin and rope_cos go together");
   VTP_REQUIRE(!rope_sin || (rope_prefix >= 0 && rope_prefix <= N), "vtp_attn_bwd: rope_prefix must be in [0, N]");
   if (int e = check_attn("vtp_attn_bwd", B, N, heads, sb_qkv, sn_qkv, sb_o, sn_o)) return e;
-  hipStream_t s = (hipStream_t)stream;
   if (use_resident(N, causal))  // delta and the inverse RoPE of dq / dk are fused into the resident kernels
     return attn_resident_bwd(q, k, v, o, d_o, lse, delta, dq, dk, dv, rope_sin, rope_cos, rope_prefix, B, N, heads, sb_qkv,
-                             sn_qkv, sb_o, sn_o, scale, s);
-  AttnArgs a = {};
-  a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.o = (const bf16*)o; a.d_o = (const bf16*)d_o;
-  a.lse = (float*)lse; a.delta = delta; a.dq = (bf16*)dq; a.dk = (bf16*)dk; a.dv = (bf16*)dv;
-  a.B = B; a.N = N; a.heads = heads; a.sb = sb_qkv; a.sn = sn_qkv; a.sbo = sb_o; a.sno = sn_o; a.scale = scale;
-  const long rows8 = (long)B * heads * N * 8;
-  int dblocks = (int)((rows8 + 255) / 256);
-  if (dblocks > 4096) dblocks = 4096;
-  hipLaunchKernelGGL(attn_delta_kernel<false>, dim3(dblocks), dim3(256), 0, s, a);
-  dim3 grid(cdiv(N, 128), heads, B);
-  if (causal) {
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, grid, dim3(256), 0, s, a);
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel<true>, grid, dim3(256), 0, s, a);
-  } else {
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<false>, grid, dim3(256), 0, s, a);
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel<false>, grid, dim3(256), 0, s, a);
-  }
+                             sn_qkv, sb_o, sn_o, scale, (hipStream_t)stream);
+  const AttnArgs a = attn_args(q, k, v, o, d_o, 0, lse, delta, dq, dk, dv, nullptr, B, N, heads, sb_qkv, sn_qkv, sb_o, sn_o, scale);
+  launch_attn_tiled_bwd(a, causal, (hipStream_t)stream);
   if (int e = check_launch("attn_bwd")) return e;
   if (rope_sin) {  // tiled path: the standalone inverse-RoPE kernel on the packed [*, 3*heads*64] gradient buffer
     VTP_REQUIRE((const bf16*)dk == (const bf16*)dq + heads * 64 && sn_qkv == 3L * heads * 64 && sb_qkv == (long)N * sn_qkv,
@@ -497,17 +511,12 @@ extern "C" int vtp_attn_bwd(const void* q, const void* k, const void* v, const v
   return VTP_OK;
 }
 
-// The causal tiled kernels over PACKED captions: batch b is the rows [cu[b], cu[b + 1]) (cu int32 [B + 1] on the device) of the packed
-// [rows, 3 * heads * 64] qkv and [rows, heads * 64] o buffers, at most Nmax rows each.  The grid is the padded launch's (ceil(Nmax / 128),
-// heads, B) and lse / delta keep the padded [B, heads, Nmax] layout; rows outside the batches are neither read nor written.
 extern "C" int vtp_attn_fwd_varlen(const void* q, const void* k, const void* v, void* o, float* lse, const int* cu, int B, int Nmax,
                                    int heads, long sn_qkv, long sn_o, float scale, void* stream) {
   VTP_REQUIRE(q && k && v && o && cu, "vtp_attn_fwd_varlen: null pointer");
   if (int e = check_attn("vtp_attn_fwd_varlen", B, Nmax, heads, 0, sn_qkv, 0, sn_o)) return e;
-  AttnArgs a = {};
-  a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.out = (bf16*)o; a.lse = lse;
-  a.B = B; a.N = Nmax; a.heads = heads; a.sn = sn_qkv; a.sno = sn_o; a.scale = scale; a.cu = cu;
-  hipLaunchKernelGGL((attn_fwd_kernel<true, true>), dim3(cdiv(Nmax, 128), heads, B), dim3(256), 0, (hipStream_t)stream, a);
+  const AttnArgs a = attn_args(q, k, v, 0, 0, o, lse, 0, 0, 0, 0, cu, B, Nmax, heads, 0, sn_qkv, 0, sn_o, scale);
+  launch_attn_tiled_fwd(a, 1, (hipStream_t)stream);
   return check_launch("attn_fwd_varlen");
 }
 
@@ -516,17 +525,7 @@ extern "C" int vtp_attn_bwd_varlen(const void* q, const void* k, const void* v, 
                                    long sn_o, float scale, void* stream) {
   VTP_REQUIRE(q && k && v && o && d_o && lse && delta && dq && dk && dv && cu, "vtp_attn_bwd_varlen: null pointer");
   if (int e = check_attn("vtp_attn_bwd_varlen", B, Nmax, heads, 0, sn_qkv, 0, sn_o)) return e;
-  hipStream_t s = (hipStream_t)stream;
-  AttnArgs a = {};
-  a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.o = (const bf16*)o; a.d_o = (const bf16*)d_o;
-  a.lse = (float*)lse; a.delta = delta; a.dq = (bf16*)dq; a.dk = (bf16*)dk; a.dv = (bf16*)dv;
-  a.B = B; a.N = Nmax; a.heads = heads; a.sn = sn_qkv; a.sno = sn_o; a.scale = scale; a.cu = cu;
-  const long rows8 = (long)B * heads * Nmax * 8;
-  int dblocks = (int)((rows8 + 255) / 256);
-  if (dblocks > 4096) dblocks = 4096;
-  hipLaunchKernelGGL(attn_delta_kernel<true>, dim3(dblocks), dim3(256), 0, s, a);
-  dim3 grid(cdiv(Nmax, 128), heads, B);
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<true, true>), grid, dim3(256), 0, s, a);
-  hipLaunchKernelGGL((attn_bwd_dkv_kernel<true, true>), grid, dim3(256), 0, s, a);
+  const AttnArgs a = attn_args(q, k, v, o, d_o, 0, lse, delta, dq, dk, dv, cu, B, Nmax, heads, 0, sn_qkv, 0, sn_o, scale);
+  launch_attn_tiled_bwd(a, 1, (hipStream_t)stream);
   return check_launch("attn_bwd_varlen");
 }

@@ -829,29 +829,28 @@ extern "C" int vtp_swiglu_bwd(const void* dh, const void* x12, void* dx12, float
   return check_launch("swiglu_bwd");
 }
 
+// GELU / QuickGELU backward; m_rows (device int) set: over the rows [0, min(M, *m_rows)) of [M, row_len] operands (the grid is that of M rows)
+static int launch_gelu_bwd(const char* label, const void* dy, const void* pre, void* dx, long n, int quick, const int* m_rows, int row_len,
+                           void* stream) {
+  auto* kern = !quick ? gelu_bwd_kernel<false> : gelu_bwd_kernel<true>;
+  hipLaunchKernelGGL(kern, dim3(grid_for(n / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16*)dy, (const bf16*)pre, (bf16*)dx, n,
+                     m_rows, row_len);
+  return check_launch(label);
+}
+
 extern "C" int vtp_gelu_bwd(const void* dy, const void* pre, void* dx, long n, void* stream) {
   VTP_REQUIRE(dy && pre && dx && n > 0 && n % 8 == 0, "vtp_gelu_bwd: bad argument (n %% 8 == 0)");
-  hipLaunchKernelGGL(gelu_bwd_kernel<false>, dim3(grid_for(n / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16*)dy, (const bf16*)pre, (bf16*)dx, n);
-  return check_launch("gelu_bwd");
+  return launch_gelu_bwd("gelu_bwd", dy, pre, dx, n, 0, nullptr, 0, stream);
 }
 
 extern "C" int vtp_quick_gelu_bwd(const void* dy, const void* pre, void* dx, long n, void* stream) {
   VTP_REQUIRE(dy && pre && dx && n > 0 && n % 8 == 0, "vtp_quick_gelu_bwd: bad argument (n %% 8 == 0)");
-  hipLaunchKernelGGL(gelu_bwd_kernel<true>, dim3(grid_for(n / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16*)dy, (const bf16*)pre, (bf16*)dx, n);
-  return check_launch("quick_gelu_bwd");
+  return launch_gelu_bwd("quick_gelu_bwd", dy, pre, dx, n, 1, nullptr, 0, stream);
 }
 
-// GELU / QuickGELU backward over the rows [0, min(M, *m_rows)) of [M, H] operands (m_rows: device int; the grid is that of M rows)
 extern "C" int vtp_gelu_bwd_limit(const void* dy, const void* pre, void* dx, int M, int H, int quick, const int* m_rows, void* stream) {
   VTP_REQUIRE(dy && pre && dx && m_rows && M > 0 && H > 0 && H % 8 == 0, "vtp_gelu_bwd_limit: bad argument (H %% 8 == 0)");
-  const long n = (long)M * H;
-  if (quick)
-    hipLaunchKernelGGL(gelu_bwd_kernel<true>, dim3(grid_for(n / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16*)dy, (const bf16*)pre,
-                       (bf16*)dx, n, m_rows, H);
-  else
-    hipLaunchKernelGGL(gelu_bwd_kernel<false>, dim3(grid_for(n / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16*)dy, (const bf16*)pre,
-                       (bf16*)dx, n, m_rows, H);
-  return check_launch("gelu_bwd_limit");
+  return launch_gelu_bwd("gelu_bwd_limit", dy, pre, dx, (long)M * H, quick, m_rows, H, stream);
 }
 
 extern "C" int vtp_pixel_shuffle16(const void* t, float* img, int B, int h, int w, void* stream) {

@@ -734,45 +734,40 @@ int launch_gemm8p_tn(const GemmArgs& a, int epi, int splits, hipStream_t s) {
 namespace vtp {
 int launch_gemm4w_grouped_tn_items(const GroupArgs& ga, int nitems, hipStream_t s);  // gemm4w_tn.hip
 }
-extern "C" int vtp_gemm_tn_grouped(const void* probs, int nprob, int ntiles, int K, int splits, void* part, void* ticket,
-                                   void* stream) {
+// k_rows (device int) set: the launch sums over the token rows [0, min(K, *k_rows)) with ONE K slice per tile (k_split = K rounded up to
+// 64), so no workgroup ever waits on the ticket of a slice that turned out empty, and no partial-sum scratch.  Rows >= *k_rows of the
+// operands are never read.  That launch is a kernel of its own (the unlimited one keeps its code).
+static int launch_gemm8p_grouped_tn(const void* probs, int nprob, int ntiles, int K, int splits, void* part, void* ticket,
+                                    const int* k_rows, void* stream) {
   using namespace vtp;
-  VTP_REQUIRE(probs && nprob >= 1 && nprob <= 8, "vtp_gemm_tn_grouped: 1..8 problems");
-  VTP_REQUIRE(ntiles >= 1 && K >= 1 && splits >= 1, "vtp_gemm_tn_grouped: bad shape (ntiles %d, K %d, splits %d)", ntiles, K, splits);
-  VTP_REQUIRE(splits == 1 || (part && ticket), "vtp_gemm_tn_grouped: split-K needs the partial-sum and ticket buffers");
+  if (k_rows) { splits = 1; part = ticket = nullptr; }
   GroupArgs ga{};
   ga.probs = (const GroupProblem*)probs; ga.part = (float*)part; ga.ticket = (int*)ticket;
   ga.nprob = nprob; ga.ntiles = ntiles; ga.K = K;
   ga.k_split = ((K + splits - 1) / splits + 63) / 64 * 64;
   ga.splits = (K + ga.k_split - 1) / ga.k_split;
   ga.timing = g_p8_timing;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)gemm8p_grouped_tn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, P8_LDS);
-    attr_set = true;
+  ga.k_rows = k_rows;
+  auto* kern = k_rows ? gemm8p_grouped_tn_limit_kernel : gemm8p_grouped_tn_kernel;
+  static bool attr_set[2] = {false, false};  // the dynamic-LDS attribute, once per kernel
+  if (!attr_set[k_rows != nullptr]) {
+    hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, P8_LDS);
+    attr_set[k_rows != nullptr] = true;
   }
-  hipLaunchKernelGGL(gemm8p_grouped_tn_kernel, dim3(ntiles * ga.splits), dim3(512), P8_LDS, (hipStream_t)stream, ga);
+  hipLaunchKernelGGL(kern, dim3(ntiles * ga.splits), dim3(512), P8_LDS, (hipStream_t)stream, ga);
   return check_launch("gemm8p_grouped_tn");
 }
-// vtp_gemm_tn_grouped over the token rows [0, min(K, *k_rows)) (k_rows: device int): one K slice per tile, so no workgroup ever waits on
-// the ticket of a slice that turned out empty, and no partial-sum scratch.  Rows >= *k_rows of the operands are never read.
+extern "C" int vtp_gemm_tn_grouped(const void* probs, int nprob, int ntiles, int K, int splits, void* part, void* ticket,
+                                   void* stream) {
+  VTP_REQUIRE(probs && nprob >= 1 && nprob <= 8, "vtp_gemm_tn_grouped: 1..8 problems");
+  VTP_REQUIRE(ntiles >= 1 && K >= 1 && splits >= 1, "vtp_gemm_tn_grouped: bad shape (ntiles %d, K %d, splits %d)", ntiles, K, splits);
+  VTP_REQUIRE(splits == 1 || (part && ticket), "vtp_gemm_tn_grouped: split-K needs the partial-sum and ticket buffers");
+  return launch_gemm8p_grouped_tn(probs, nprob, ntiles, K, splits, part, ticket, nullptr, stream);
+}
 extern "C" int vtp_gemm_tn_grouped_limit(const void* probs, int nprob, int ntiles, int K, const int* k_rows, void* stream) {
-  using namespace vtp;
   VTP_REQUIRE(probs && k_rows && nprob >= 1 && nprob <= 8, "vtp_gemm_tn_grouped_limit: 1..8 problems and a row count");
   VTP_REQUIRE(ntiles >= 1 && K >= 1, "vtp_gemm_tn_grouped_limit: bad shape (ntiles %d, K %d)", ntiles, K);
-  GroupArgs ga{};
-  ga.probs = (const GroupProblem*)probs;
-  ga.nprob = nprob; ga.ntiles = ntiles; ga.K = K; ga.splits = 1;
-  ga.k_split = (K + 63) / 64 * 64;
-  ga.timing = g_p8_timing;
-  ga.k_rows = k_rows;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)gemm8p_grouped_tn_limit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, P8_LDS);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(gemm8p_grouped_tn_limit_kernel, dim3(ntiles), dim3(512), P8_LDS, (hipStream_t)stream, ga);
-  return check_launch("gemm8p_grouped_tn");
+  return launch_gemm8p_grouped_tn(probs, nprob, ntiles, K, 1, nullptr, nullptr, k_rows, stream);
 }
 // The same launch on the one-wave-per-SIMD kernel (gemm4w_tn.hip), from an explicit work-item list: items = device array of nitems
 // records of 8 int32 {tile, kbeg, kcount, nparts, part, 0, 0, 0} -- one workgroup each; the items of a tile partition [0, K) into

@@ -4,6 +4,7 @@
 // Rows are read as float4 per lane (16 B), row-resident in registers (D <= 2048).
 #include "common.h"
 #include <cstdlib>
+#include <type_traits>
 #include "vtp_hip.h"
 
 namespace vtp {
@@ -265,53 +266,61 @@ __global__ __launch_bounds__(POOL_WAVES * 64) void pool_patch_rows_kernel(const 
 }  // namespace vtp
 using namespace vtp;
 
-#define NORM_DISPATCH(KERNEL, KIND, ...)                                                            \
-  do {                                                                                              \
-    const int nc = cdiv(D, 256);                                                                    \
-    if (nc <= 1) hipLaunchKernelGGL((KERNEL<KIND, 1>), grid, block, 0, (hipStream_t)stream, __VA_ARGS__);      \
-    else if (nc == 2) hipLaunchKernelGGL((KERNEL<KIND, 2>), grid, block, 0, (hipStream_t)stream, __VA_ARGS__); \
-    else if (nc == 3) hipLaunchKernelGGL((KERNEL<KIND, 3>), grid, block, 0, (hipStream_t)stream, __VA_ARGS__); \
-    else if (nc == 4) hipLaunchKernelGGL((KERNEL<KIND, 4>), grid, block, 0, (hipStream_t)stream, __VA_ARGS__); \
-    else hipLaunchKernelGGL((KERNEL<KIND, 8>), grid, block, 0, (hipStream_t)stream, __VA_ARGS__);              \
-  } while (0)
+// everything norm_fwd_kernel takes (y8 / q_scale: the e4m3 output instead of y; m_rows: device row limit, null = all M rows)
+struct NormFwdArgs {
+  const float *x, *w, *b;
+  bf16* y;
+  uint8_t* y8;
+  const float* q_scale;
+  float* stats;
+  int M, D;
+  float eps;
+  int kind;
+  const int* m_rows;
+};
 
-extern "C" int vtp_norm_fwd(const float* x, const float* w, const float* b, void* y, float* stats, int M, int D,
-                            float eps, int kind, void* stream) {
-  VTP_REQUIRE(x && w && y, "vtp_norm_fwd: null pointer");
-  VTP_REQUIRE(M > 0 && D > 0 && D % 4 == 0 && D <= NORM_MAXC * 256, "vtp_norm_fwd: need 0 < D <= 2048, D %% 4 == 0 (D=%d)", D);
-  VTP_REQUIRE(kind == 0 || (kind == 1 && b), "vtp_norm_fwd: kind must be 0 (rms) or 1 (layernorm, needs bias)");
-  dim3 grid(cdiv(M, 4)), block(256);
-  if (kind == 0)
-    NORM_DISPATCH(norm_fwd_kernel, 0, x, w, b, (bf16*)y, stats, M, D, eps);
-  else
-    NORM_DISPATCH(norm_fwd_kernel, 1, x, w, b, (bf16*)y, stats, M, D, eps);
-  return check_launch("norm_fwd");
+// everything norm_bwd_kernel takes (pvec .. pN: the pooled-vector variant; dres_rows / dres_M: the row-mapped one)
+struct NormBwdArgs {
+  const bf16* dy;
+  const float *x, *w, *stats, *dres;
+  float* dx;
+  bf16* dxb;
+  float *dw, *db, *dxsum;
+  int M, D, kind;
+  const float* pvec;
+  int prow0, pB, pN;
+  const int* dres_rows;
+  int dres_M;
+  const int* m_rows;
+};
+
+// the one KIND x NC dispatch: f(KIND, NC) as integral constants, NC = float4 chunks per lane of a D-wide row.  WIDE = false stops at
+// NC = 4 (D <= 1024): the pooled-vector and row-mapped backward have no NC = 8 variant -- the wide rows leave no registers for the
+// vector's / the mapped read (it spilled ~2 100 VGPRs)
+template <bool WIDE, class F>
+static void norm_dispatch(int kind, int D, F f) {
+  auto by_nc = [&](auto kc) {
+    const int nc = cdiv(D, 256);
+    if (nc <= 1) f(kc, std::integral_constant<int, 1>{});
+    else if (nc == 2) f(kc, std::integral_constant<int, 2>{});
+    else if (nc == 3) f(kc, std::integral_constant<int, 3>{});
+    else if (!WIDE || nc == 4) f(kc, std::integral_constant<int, 4>{});
+    else if constexpr (WIDE) f(kc, std::integral_constant<int, 8>{});
+  };
+  if (kind == 0) by_nc(std::integral_constant<int, 0>{});
+  else by_nc(std::integral_constant<int, 1>{});
 }
 
-extern "C" int vtp_norm_fwd_limit(const float* x, const float* w, const float* b, void* y, float* stats, int M, int D, float eps,
-                                 int kind, const int* m_rows, void* stream) {
-  VTP_REQUIRE(x && w && y && m_rows, "vtp_norm_fwd_limit: null pointer");
-  VTP_REQUIRE(M > 0 && D > 0 && D % 4 == 0 && D <= NORM_MAXC * 256, "vtp_norm_fwd_limit: need 0 < D <= 2048, D %% 4 == 0 (D=%d)", D);
-  VTP_REQUIRE(kind == 0 || (kind == 1 && b), "vtp_norm_fwd_limit: kind must be 0 (rms) or 1 (layernorm, needs bias)");
-  dim3 grid(cdiv(M, 4)), block(256);
-  if (kind == 0)
-    NORM_DISPATCH(norm_fwd_kernel, 0, x, w, b, (bf16*)y, stats, M, D, eps, (uint8_t*)nullptr, (const float*)nullptr, m_rows);
-  else
-    NORM_DISPATCH(norm_fwd_kernel, 1, x, w, b, (bf16*)y, stats, M, D, eps, (uint8_t*)nullptr, (const float*)nullptr, m_rows);
-  return check_launch("norm_fwd_limit");
-}
-
-extern "C" int vtp_norm_fwd_e4m3(const float* x, const float* w, const float* b, void* y8, const float* q_scale, float* stats, int M,
-                                 int D, float eps, int kind, void* stream) {
-  VTP_REQUIRE(x && w && y8 && q_scale, "vtp_norm_fwd_e4m3: null pointer");
-  VTP_REQUIRE(M > 0 && D > 0 && D % 4 == 0 && D <= NORM_MAXC * 256, "vtp_norm_fwd_e4m3: need 0 < D <= 2048, D %% 4 == 0 (D=%d)", D);
-  VTP_REQUIRE(kind == 0 || (kind == 1 && b), "vtp_norm_fwd_e4m3: kind must be 0 (rms) or 1 (layernorm, needs bias)");
-  dim3 grid(cdiv(M, 4)), block(256);
-  if (kind == 0)
-    NORM_DISPATCH(norm_fwd_kernel, 0, x, w, b, (bf16*)nullptr, stats, M, D, eps, (uint8_t*)y8, q_scale);
-  else
-    NORM_DISPATCH(norm_fwd_kernel, 1, x, w, b, (bf16*)nullptr, stats, M, D, eps, (uint8_t*)y8, q_scale);
-  return check_launch("norm_fwd_e4m3");
+// A row limit (m_rows, device int) keeps the grid of the static M: rows >= *m_rows are neither read nor written.
+static int launch_norm_fwd(const char* who, const char* label, const NormFwdArgs& a, void* stream) {
+  VTP_REQUIRE(a.M > 0 && a.D > 0 && a.D % 4 == 0 && a.D <= NORM_MAXC * 256, "%s: need 0 < D <= %d, D %% 4 == 0 (D=%d)", who,
+              NORM_MAXC * 256, a.D);
+  VTP_REQUIRE(a.kind == 0 || (a.kind == 1 && a.b), "%s: kind must be 0 (rms) or 1 (layernorm, needs bias)", who);
+  norm_dispatch<true>(a.kind, a.D, [&](auto kc, auto nc) {
+    hipLaunchKernelGGL((norm_fwd_kernel<decltype(kc)::value, decltype(nc)::value>), dim3(cdiv(a.M, 4)), dim3(256), 0, (hipStream_t)stream,
+                       a.x, a.w, a.b, a.y, a.stats, a.M, a.D, a.eps, a.y8, a.q_scale, a.m_rows);
+  });
+  return check_launch(label);
 }
 
 static int norm_bwd_blocks(int M, int D) {
@@ -329,19 +338,56 @@ static int norm_bwd_blocks(int M, int D) {
   return blocks > cap ? cap : blocks;
 }
 
+// A row limit (m_rows, device int) keeps the grid of the static M: rows >= *m_rows are not read, not written and add nothing to
+// dw / db / dx_colsum.
+template <bool PV, bool MAPPED>
+static int launch_norm_bwd(const char* who, const char* label, const NormBwdArgs& a, void* stream) {
+  constexpr bool WIDE = !PV && !MAPPED;
+  constexpr int MAXD = WIDE ? NORM_MAXC * 256 : 1024;
+  VTP_REQUIRE(!a.dxsum || a.dxb, "%s: dx_colsum sums the bf16 output and needs dx_bf16", who);
+  VTP_REQUIRE(a.M > 0 && a.D > 0 && a.D % 4 == 0 && a.D <= MAXD, "%s: need 0 < D <= %d, D %% 4 == 0 (D=%d)", who, MAXD, a.D);
+  VTP_REQUIRE(a.kind == 0 || a.kind == 1, "%s: kind must be 0 or 1", who);
+  const dim3 grid(norm_bwd_blocks(a.M, a.D));
+  norm_dispatch<WIDE>(a.kind, a.D, [&](auto kc, auto nc) {
+    hipLaunchKernelGGL((norm_bwd_kernel<decltype(kc)::value, decltype(nc)::value, PV, MAPPED>), grid, dim3(256), 0, (hipStream_t)stream,
+                       a.dy, a.x, a.w, a.stats, a.dres, a.dx, a.dxb, a.dw, a.db, a.dxsum, a.M, a.D, a.pvec, a.prow0, a.pB, a.pN,
+                       a.dres_rows, a.dres_M, a.m_rows);
+  });
+  return check_launch(label);
+}
+
+extern "C" int vtp_norm_fwd(const float* x, const float* w, const float* b, void* y, float* stats, int M, int D,
+                            float eps, int kind, void* stream) {
+  VTP_REQUIRE(x && w && y, "vtp_norm_fwd: null pointer");
+  return launch_norm_fwd("vtp_norm_fwd", "norm_fwd", {x, w, b, (bf16*)y, nullptr, nullptr, stats, M, D, eps, kind, nullptr}, stream);
+}
+
+extern "C" int vtp_norm_fwd_limit(const float* x, const float* w, const float* b, void* y, float* stats, int M, int D, float eps,
+                                 int kind, const int* m_rows, void* stream) {
+  VTP_REQUIRE(x && w && y && m_rows, "vtp_norm_fwd_limit: null pointer");
+  return launch_norm_fwd("vtp_norm_fwd_limit", "norm_fwd_limit", {x, w, b, (bf16*)y, nullptr, nullptr, stats, M, D, eps, kind, m_rows},
+                         stream);
+}
+
+extern "C" int vtp_norm_fwd_e4m3(const float* x, const float* w, const float* b, void* y8, const float* q_scale, float* stats, int M,
+                                 int D, float eps, int kind, void* stream) {
+  VTP_REQUIRE(x && w && y8 && q_scale, "vtp_norm_fwd_e4m3: null pointer");
+  return launch_norm_fwd("vtp_norm_fwd_e4m3", "norm_fwd_e4m3", {x, w, b, nullptr, (uint8_t*)y8, q_scale, stats, M, D, eps, kind, nullptr},
+                         stream);
+}
+
+// the arguments every backward entry has; the variants set their own fields on top
+static NormBwdArgs norm_bwd_args(const void* dy, const float* x, const float* w, const float* stats, const float* dres, float* dx,
+                                 void* dx_bf16, float* dw, float* db, float* dx_colsum, int M, int D, int kind) {
+  return {(const bf16*)dy, x, w, stats, dres, dx, (bf16*)dx_bf16, dw, db, dx_colsum, M, D, kind, nullptr, 0, 0, 1, nullptr, 0, nullptr};
+}
+
 extern "C" int vtp_norm_bwd(const void* dy, const float* x, const float* w, const float* stats, const float* dres,
                             float* dx, void* dx_bf16, float* dw, float* db, float* dx_colsum, int M, int D, int kind,
                             void* stream) {
   VTP_REQUIRE(dy && x && w && stats && dx, "vtp_norm_bwd: null pointer");
-  VTP_REQUIRE(!dx_colsum || dx_bf16, "vtp_norm_bwd: dx_colsum sums the bf16 output and needs dx_bf16");
-  VTP_REQUIRE(M > 0 && D > 0 && D % 4 == 0 && D <= NORM_MAXC * 256, "vtp_norm_bwd: need 0 < D <= 2048, D %% 4 == 0 (D=%d)", D);
-  VTP_REQUIRE(kind == 0 || kind == 1, "vtp_norm_bwd: kind must be 0 or 1");
-  dim3 grid(norm_bwd_blocks(M, D)), block(256);
-  if (kind == 0)
-    NORM_DISPATCH(norm_bwd_kernel, 0, (const bf16*)dy, x, w, stats, dres, dx, (bf16*)dx_bf16, dw, db, dx_colsum, M, D);
-  else
-    NORM_DISPATCH(norm_bwd_kernel, 1, (const bf16*)dy, x, w, stats, dres, dx, (bf16*)dx_bf16, dw, db, dx_colsum, M, D);
-  return check_launch("norm_bwd");
+  return launch_norm_bwd<false, false>("vtp_norm_bwd", "norm_bwd",
+                                       norm_bwd_args(dy, x, w, stats, dres, dx, dx_bf16, dw, db, dx_colsum, M, D, kind), stream);
 }
 
 // vtp_norm_bwd over the rows [0, min(M, *m_rows)) (m_rows: device int; the grid is that of the static M)
@@ -349,54 +395,20 @@ extern "C" int vtp_norm_bwd_limit(const void* dy, const float* x, const float* w
                                   void* dx_bf16, float* dw, float* db, float* dx_colsum, int M, int D, int kind, const int* m_rows,
                                   void* stream) {
   VTP_REQUIRE(dy && x && w && stats && dx && m_rows, "vtp_norm_bwd_limit: null pointer");
-  VTP_REQUIRE(!dx_colsum || dx_bf16, "vtp_norm_bwd_limit: dx_colsum sums the bf16 output and needs dx_bf16");
-  VTP_REQUIRE(M > 0 && D > 0 && D % 4 == 0 && D <= NORM_MAXC * 256, "vtp_norm_bwd_limit: need 0 < D <= 2048, D %% 4 == 0 (D=%d)", D);
-  VTP_REQUIRE(kind == 0 || kind == 1, "vtp_norm_bwd_limit: kind must be 0 or 1");
-  dim3 grid(norm_bwd_blocks(M, D)), block(256);
-  const bf16* dyb = (const bf16*)dy;
-  bf16* dxb = (bf16*)dx_bf16;
-  if (kind == 0)
-    NORM_DISPATCH(norm_bwd_kernel, 0, dyb, x, w, stats, dres, dx, dxb, dw, db, dx_colsum, M, D, (const float*)nullptr, 0, 0, 1,
-                  (const int*)nullptr, 0, m_rows);
-  else
-    NORM_DISPATCH(norm_bwd_kernel, 1, dyb, x, w, stats, dres, dx, dxb, dw, db, dx_colsum, M, D, (const float*)nullptr, 0, 0, 1,
-                  (const int*)nullptr, 0, m_rows);
-  return check_launch("norm_bwd_limit");
-}
-
-template <int KIND>
-static void launch_norm_bwd_pvec(dim3 grid, hipStream_t s, const bf16* dy, const float* x, const float* w, const float* stats,
-                                 const float* dres, float* dx, bf16* dxb, float* dw, float* db, float* dxsum, int M, int D,
-                                 const float* pvec, int prow0, int pB, int pN) {
-  const int nc = cdiv(D, 256);
-#define NORM_PV(NC) \
-  hipLaunchKernelGGL((norm_bwd_kernel<KIND, NC, true>), grid, dim3(256), 0, s, dy, x, w, stats, dres, dx, dxb, dw, db, dxsum, M, D, \
-                     pvec, prow0, pB, pN)
-  // (no NC = 8 variant: the wide rows leave no registers for the vector's read -- it spilled ~2 100 VGPRs)
-  if (nc <= 1) NORM_PV(1);
-  else if (nc == 2) NORM_PV(2);
-  else if (nc == 3) NORM_PV(3);
-  else NORM_PV(4);
-#undef NORM_PV
+  NormBwdArgs a = norm_bwd_args(dy, x, w, stats, dres, dx, dx_bf16, dw, db, dx_colsum, M, D, kind);
+  a.m_rows = m_rows;
+  return launch_norm_bwd<false, false>("vtp_norm_bwd_limit", "norm_bwd_limit", a, stream);
 }
 
 extern "C" int vtp_norm_bwd_pvec(const void* dy, const float* x, const float* w, const float* stats, const float* dres, float* dx,
                                  void* dx_bf16, float* dw, float* db, float* dx_colsum, const float* pvec, int prow0, int pB, int pN,
                                  int M, int D, int kind, void* stream) {
   VTP_REQUIRE(dy && x && w && stats && dx && pvec, "vtp_norm_bwd_pvec: null pointer");
-  VTP_REQUIRE(!dx_colsum || dx_bf16, "vtp_norm_bwd_pvec: dx_colsum sums the bf16 output and needs dx_bf16");
-  VTP_REQUIRE(M > 0 && D > 0 && D % 4 == 0 && D <= 1024, "vtp_norm_bwd_pvec: need 0 < D <= 1024, D %% 4 == 0 (D=%d)", D);
-  VTP_REQUIRE(kind == 0 || kind == 1, "vtp_norm_bwd_pvec: kind must be 0 or 1");
   VTP_REQUIRE(pB > 0 && pN >= 2 && prow0 >= 0 && (long)prow0 + (long)pB * pN <= M,
               "vtp_norm_bwd_pvec: segment rows [%d, %d + %d*%d) must lie in [0, M=%d), N >= 2", prow0, prow0, pB, pN, M);
-  dim3 grid(norm_bwd_blocks(M, D));
-  if (kind == 0)
-    launch_norm_bwd_pvec<0>(grid, (hipStream_t)stream, (const bf16*)dy, x, w, stats, dres, dx, (bf16*)dx_bf16, dw, db, dx_colsum, M, D,
-                            pvec, prow0, pB, pN);
-  else
-    launch_norm_bwd_pvec<1>(grid, (hipStream_t)stream, (const bf16*)dy, x, w, stats, dres, dx, (bf16*)dx_bf16, dw, db, dx_colsum, M, D,
-                            pvec, prow0, pB, pN);
-  return check_launch("norm_bwd_pvec");
+  NormBwdArgs a = norm_bwd_args(dy, x, w, stats, dres, dx, dx_bf16, dw, db, dx_colsum, M, D, kind);
+  a.pvec = pvec; a.prow0 = prow0; a.pB = pB; a.pN = pN;
+  return launch_norm_bwd<true, false>("vtp_norm_bwd_pvec", "norm_bwd_pvec", a, stream);
 }
 
 extern "C" int vtp_norm_bwd_rows(const void* dy, const float* x, const float* w, const float* stats, const float* dres,
@@ -405,30 +417,10 @@ extern "C" int vtp_norm_bwd_rows(const void* dy, const float* x, const float* w,
   if (!dres_rows)
     return vtp_norm_bwd(dy, x, w, stats, dres, dx, dx_bf16, dw, db, dx_colsum, M, D, kind, stream);
   VTP_REQUIRE(dy && x && w && stats && dx && dres, "vtp_norm_bwd_rows: null pointer (a row map needs dres)");
-  VTP_REQUIRE(!dx_colsum || dx_bf16, "vtp_norm_bwd_rows: dx_colsum sums the bf16 output and needs dx_bf16");
-  VTP_REQUIRE(M > 0 && dres_M > 0 && D > 0 && D % 4 == 0 && D <= 1024,
-              "vtp_norm_bwd_rows: need 0 < D <= 1024, D %% 4 == 0, dres_M > 0 (D=%d dres_M=%d)", D, dres_M);
-  VTP_REQUIRE(kind == 0 || kind == 1, "vtp_norm_bwd_rows: kind must be 0 or 1");
-  dim3 grid(norm_bwd_blocks(M, D)), block(256);
-  const bf16* dyb = (const bf16*)dy;
-  bf16* dxb = (bf16*)dx_bf16;
-  const int nc = cdiv(D, 256);
-#define NORM_ROWS(KIND, NC)                                                                                                         \
-  hipLaunchKernelGGL((norm_bwd_kernel<KIND, NC, false, true>), grid, block, 0, (hipStream_t)stream, dyb, x, w, stats, dres, dx, dxb, dw, \
-                     db, dx_colsum, M, D, (const float*)nullptr, 0, 0, 1, dres_rows, dres_M)
-  // (no NC = 8 variant, as for the pooled-vector entry: the wide rows leave no registers for the mapped read)
-#define NORM_ROWS_KIND(KIND)           \
-  do {                                 \
-    if (nc <= 1) NORM_ROWS(KIND, 1);   \
-    else if (nc == 2) NORM_ROWS(KIND, 2); \
-    else if (nc == 3) NORM_ROWS(KIND, 3); \
-    else NORM_ROWS(KIND, 4);           \
-  } while (0)
-  if (kind == 0) NORM_ROWS_KIND(0);
-  else NORM_ROWS_KIND(1);
-#undef NORM_ROWS_KIND
-#undef NORM_ROWS
-  return check_launch("norm_bwd_rows");
+  VTP_REQUIRE(dres_M > 0, "vtp_norm_bwd_rows: a row map needs dres_M > 0 (dres_M=%d)", dres_M);
+  NormBwdArgs a = norm_bwd_args(dy, x, w, stats, dres, dx, dx_bf16, dw, db, dx_colsum, M, D, kind);
+  a.dres_rows = dres_rows; a.dres_M = dres_M;
+  return launch_norm_bwd<false, true>("vtp_norm_bwd_rows", "norm_bwd_rows", a, stream);
 }
 
 extern "C" int vtp_pool_patch_rows(const void* x, float* out, int B, int N, int D, float scale, void* stream) {

@@ -451,6 +451,13 @@ _NAMES = {
 }
 
 
+class RowPlan(NamedTuple):
+    """packed captions of one segment (Stack.varlen): sequence b is the rows [cu[b], cu[b + 1]) of every token buffer and only the first
+    rows[0] rows hold data"""
+    cu: torch.Tensor    # int32 [B + 1], device
+    rows: torch.Tensor  # int32 [1], device
+
+
 class Stack:
     """A run of pre-norm transformer blocks.  style "vit": SelfAttentionBlock (RoPE attention + SwiGLU FFN);
     style "text": CLIP ResidualAttentionBlock (causal attention, no RoPE, LayerNorm eps 1e-5, erf-GELU MLP of width H)."""
@@ -514,11 +521,15 @@ class Stack:
         # must accumulate like nn.Parameter.grad does, never does).  Saves the 256-KiB read of every output tile in the epilogue of the
         # step's dominant kernel: 38 -> 24 us per last-arriving workgroup (tools/wgrad_timeline.py)
         self.wgrad_overwrite = False
-        # packed captions (TextEngine, causal + arg-max pooling): (cu int32 [B + 1], rows int32 [1]) on the device -- sequence b of the one
-        # segment is the rows [cu[b], cu[b + 1]) of every token buffer and only the first rows[0] rows hold data.  Launch geometry stays
-        # that of the static M = B * T; the kernels read the counts (ops: m_rows / k_rows / the varlen attention).  Set by the owner
-        # before forward() and left in place for the matching backward(); None: padded rows.
-        self.varlen = None
+        # packed captions (TextEngine, causal + arg-max pooling): a RowPlan on the device.  Launch geometry stays that of the static
+        # M = B * T; the kernels read the counts (ops: m_rows / k_rows / the varlen attention).  Set by the owner before forward() and left
+        # in place for the matching backward(); None: padded rows.
+        self.varlen: Optional[RowPlan] = None
+
+    @property
+    def m_rows(self):
+        """device row limit of every row-wise launch: the live-row count of the packed captions, None for padded rows"""
+        return None if self.varlen is None else self.varlen.rows
 
     def _rope_plan(self, ws: Workspace, segs, prefix_tokens: int, M: int):
         """(rope_pos int32 [M], sin, cos) for the fused qkv + RoPE epilogue: rope_pos[m] = row of the concatenated per-segment
@@ -696,7 +707,7 @@ class Stack:
         if self.varlen is not None:
             (r0, Bs, Ns, rp), = rows
             assert rp is None and self.causal
-            ops.attn_fwd_varlen(qkv, qkv[:, D:], qkv[:, 2 * D:], o, lse, self.varlen[0], Bs, Ns, heads, 3 * D, D, ATTN_SCALE)
+            ops.attn_fwd_varlen(qkv, qkv[:, D:], qkv[:, 2 * D:], o, lse, self.varlen.cu, Bs, Ns, heads, 3 * D, D, ATTN_SCALE)
             return
         for r0, Bs, Ns, rp in rows:
             q_s, o_s = qkv[r0:r0 + Bs * Ns], o[r0:r0 + Bs * Ns]
@@ -710,7 +721,7 @@ class Stack:
         """out = (resid +) proj(attn(rope(qkv(norm1(x)))));  returns (xn1, st1, qkv, o, lse).  proj=False: stops behind the attention
         (the caller projects a subset of the rows of o)"""
         D, heads, b = self.D, self.heads, self.blocks[i]
-        mr = None if self.varlen is None else self.varlen[1]
+        mr = self.m_rows
         xn1, st1 = ws.get(t + "xn1", (M, D), BF), ws.get(t + "st1", (M, 2), F32)
         qkv, o = ws.get(t + "qkv", (M, 3 * D), BF), ws.get(t + "o", (M, D), BF)
         lse = ws.get(t + "lse", (M * heads,), F32)  # per segment [B_i, heads, N_i]
@@ -733,7 +744,7 @@ class Stack:
     def _ffn_fwd(self, ws: Workspace, t: str, i: int, x, out, resid, M: int, train: bool):
         """out = (resid +) w3(act(w12 / fc(norm2(x))));  returns (xn2, st2, pre, hid) -- pre (the FFN pre-activations) only in training"""
         D, H, b = self.D, self.H, self.blocks[i]
-        mr = None if self.varlen is None else self.varlen[1]
+        mr = self.m_rows
         xn2, st2 = ws.get(t + "xn2", (M, D), BF), ws.get(t + "st2", (M, 2), F32)
         pre = ws.get(t + "x12", (M, 2 * H if self.swiglu else H), BF) if train else None
         hid = ws.get(t + "hid", (M, H), BF)
@@ -751,7 +762,7 @@ class Stack:
         """dy / dy_b: gradient of the FFN branch output (f32 / bf16 copy); dx (+ dx_b) = dy + the gradient through the branch into its
         input.  fused: the SwiGLU backward rides in the w3 dgrad's epilogue.  probs: collects the grouped weight-gradient problems."""
         D, H, b = self.D, self.H, self.blocks[i]
-        mr = None if self.varlen is None else self.varlen[1]
+        mr = self.m_rows
         dh, dxn = ws.get(bt + "dh", (M, H), BF), ws.get(bt + "dxn", (M, D), BF)
         linear_bwd(ws, "w3", b.w3, dy_b, s.hid, M, dpre if fused else dh, bias_grad_done=bias_done,
                    ls=(b.ls2, b.gls2) if b.ls2 is not None else None, dgrad_swiglu=s.pre if fused else None, defer=probs, m_rows=mr)
@@ -773,7 +784,7 @@ class Stack:
         gradients: the projection's dgrad and weight gradient run on them, d_o is expanded to all M rows for the attention backward
         (every row is a key / value), and norm1's backward picks its residual gradient through the row map."""
         D, heads, b = self.D, self.heads, self.blocks[i]
-        mr = None if self.varlen is None else self.varlen[1]
+        mr = self.m_rows
         d_o, dxn = ws.get(bt + "do", (M, D), BF), ws.get(bt + "dxn", (M, D), BF)
         delta = ws.get(bt + "delta", (M * heads,), F32)
         if s.row_map is not None:
@@ -790,7 +801,7 @@ class Stack:
         if self.varlen is not None:
             (r0, Bs, Ns, rp), = rows
             ops.attn_bwd_varlen(s.qkv, s.qkv[:, D:], s.qkv[:, 2 * D:], s.o, d_o, s.lse, delta, dqkv, dqkv[:, D:], dqkv[:, 2 * D:],
-                                self.varlen[0], Bs, Ns, heads, 3 * D, D, ATTN_SCALE)
+                                self.varlen.cu, Bs, Ns, heads, 3 * D, D, ATTN_SCALE)
             rows = ()
         for r0, Bs, Ns, rp in rows:
             r1 = r0 + Bs * Ns
@@ -1067,7 +1078,7 @@ class Stack:
                     counts = [None]
                 parts = []
                 for kt in counts:
-                    g = ops.WgradGroup(M if kt is None else kt, k_rows=None if vl is None else vl[1])
+                    g = ops.WgradGroup(M if kt is None else kt, k_rows=self.m_rows)
                     for pr in probs + extra:
                         if kt is None or pr.get("Ktok", M) == kt:
                             g.add(pr["dy"], pr["x"], pr["gw"], pr["gb"], pr["N"], pr["K"], pr["swiglu_h"],
