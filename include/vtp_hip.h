@@ -606,6 +606,31 @@ int vtp_preprocess(const void* src_u8, long src_len, void* scratch, long scratch
                    const int* launches, int n_launches, long B, int Ho, int Wo, const float* mean3, const float* std3, float* out,
                    void* out_u8, void* stream);
 
+/* ---- FID (fid.hip): Inception-v3 features in exact fp32 and the Frechet statistics in fp64.  No float atomics, no split sums: every
+ * result repeats bit for bit and does not depend on the batch size.
+ * vtp_conv2d_f32: y[b, oy, ox, c0 + n] = act(bias[n] + sum_{ky, kx, ci} x[b, oy s - ph + ky, ox s - pw + kx, ci] w[n, ky, kx, ci]).
+ *   x f32 NHWC [B, H, W, Cin]; w f32 [Cout, kh, kw, Cin] (BatchNorm folded in); bias f32 [Cout] or NULL; y f32 [B, Ho, Wo, Ctot], of
+ *   which only the channels [c0, c0 + Cout) are written; Ho = (H + 2 ph - kh) / s + 1.  kh, kw in {1, 3, 5, 7}, stride 1 or 2, zero
+ *   padding (ph, pw), relu != 0: max(., 0).  An implicit GEMM on v_mfma_f32_32x32x2_f32: every output element is ONE fmaf chain
+ *   that starts at the bias and runs over k in the order (ky, kx, ci).  x and w 16-byte aligned when Cin % 4 == 0 (16-byte loads
+ *   along Cin); any other Cin (the first layer's 3) takes scalar loads.
+ * vtp_pool3x3_f32: 3 x 3 pooling of x f32 NHWC [B, H, W, C] into the channels [c0, c0 + C) of y [B, Ho, Wo, Ctot].  stride 1 pads by
+ *   1, stride 2 by 0.  mode 0 max (a NaN tap gives NaN, as F.max_pool2d), 1 average / 9 (the padding counts), 2 average over the taps inside.  C, c0, Ctot % 4 == 0.
+ * vtp_global_avgpool_f32: x f32 [B, HW, C] -> y f32 [B, C], the pixels summed in order.
+ * vtp_resize_bilinear_nhwc: y[b, oy, ox, c] = scale * bilinear(x[b, c])(oy, ox) + shift with F.interpolate's align_corners=False
+ *   geometry; x f32 NCHW [B, C, H, W], y f32 NHWC [B, Ho, Wo, C].  Weights are exact rationals, the arithmetic fp64, one rounding.
+ *   With Ho == H, Wo == W it is the NCHW -> NHWC repack.
+ * vtp_fid_accum: sum[i] += feats[r, i] and outer[i, j] = fma(feats[r, i], feats[r, j], outer[i, j]) for r = 0 .. n - 1 in order, in
+ *   fp64; feats f32 [n, D] with row stride ldf, sum f64 [D], outer f64 [D, D].  One thread owns each element: any split of the rows
+ *   over calls leaves the same bits. */
+int vtp_conv2d_f32(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin, int Cout, int kh,
+                   int kw, int stride, int ph, int pw, int relu, int c0, int Ctot, void* stream);
+int vtp_pool3x3_f32(const float* x, float* y, int B, int H, int W, int C, int stride, int mode, int c0, int Ctot, void* stream);
+int vtp_global_avgpool_f32(const float* x, float* y, int B, int HW, int C, void* stream);
+int vtp_resize_bilinear_nhwc(const float* x, float* y, int B, int C, int H, int W, int Ho, int Wo, float scale, float shift,
+                             void* stream);
+int vtp_fid_accum(const float* feats, int ldf, double* sum, double* outer, int n, int D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

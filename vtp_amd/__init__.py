@@ -1,7 +1,8 @@
 """vtp_amd -- MI355X-native (gfx950 / CDNA4) VTP training hot path.
 
 Public surface mirrors the reference (`from vtp.models.vtp_hf import VTPConfig, VTPModel`):
-    from vtp_amd import VTPConfig, VTPModel, VTPTrainer, LinearProbe, ZeroShot, ReconEval, MultiCrop, Preprocess
+    from vtp_amd import VTPConfig, VTPModel, VTPTrainer, LinearProbe, ZeroShot, ReconEval, MultiCrop, Preprocess, FID,
+    InceptionFeatures, FrechetStats, frechet_distance
 Everything below the Python API is hand-written HIP in libvtp_hip.so (C ABI: include/vtp_hip.h)."""
 from .config import VTPConfig  # noqa: F401
 
@@ -40,4 +41,7 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name == "Preprocess":
         from .preprocess import Preprocess
         return Preprocess
+    if name in ("InceptionFeatures", "FrechetStats", "FID", "frechet_distance"):
+        from . import fid
+        return getattr(fid, name)
     raise AttributeError(name)

@@ -143,6 +143,12 @@ SIGNATURES = {
     "vtp_augment_crops": [_P, _L, _I, _I, _P, _L, _I, _P, _P, _P, _P, _L, _P],
     # src_u8 src_len scratch scratch_len jobs tab launches n_launches B Ho Wo mean3 std3 out out_u8 stream
     "vtp_preprocess": [_P, _L, _P, _L, _P, _P, _P, _I, _L, _I, _I, _P, _P, _P, _P, _P],
+    # x w bias y B H W Cin Cout kh kw stride ph pw relu c0 Ctot stream
+    "vtp_conv2d_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "vtp_pool3x3_f32": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],  # x y B H W C stride mode c0 Ctot stream
+    "vtp_global_avgpool_f32": [_P, _P, _I, _I, _I, _P],  # x y B HW C stream
+    "vtp_resize_bilinear_nhwc": [_P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _P],  # x y B C H W Ho Wo scale shift stream
+    "vtp_fid_accum": [_P, _I, _P, _P, _I, _I, _P],  # feats ldf sum outer n D stream
 }
 
 _lib = None

@@ -891,3 +891,95 @@ def preprocess(src_u8, scratch, jobs, tab, launches, out, out_u8, mean, std):
     _lib.check(_lib_().vtp_preprocess(_p(src_u8), src_u8.numel(), _p(scratch), 0 if scratch is None else scratch.numel(), _p(jobs),
                                       _p(tab), ln.ctypes.data_as(ctypes.c_void_p), len(ln), B, Ho, Wo, _f3(mean), _f3(std), _p(out),
                                       _p(out_u8), _s()), "vtp_preprocess")
+
+
+POOL_MAX, POOL_AVG, POOL_AVG_INSIDE = 0, 1, 2  # vtp_pool3x3_f32 modes: max; average / 9; average over the taps inside the image
+
+
+def conv_out_size(H, W, kh, kw, stride, ph, pw):
+    return (H + 2 * ph - kh) // stride + 1, (W + 2 * pw - kw) // stride + 1
+
+
+def _need(t, name, dtype, shape=None, dims=None):
+    """the C entry points see pointers only: dtype, shape and contiguity of a tensor are checked here (the device by _need_gpu, last)"""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+        raise ValueError(f"{name} must be a {dtype} tensor, got {getattr(t, 'dtype', type(t))}")
+    if dims is not None and t.dim() != dims:
+        raise ValueError(f"{name} must have {dims} dimensions, got {tuple(t.shape)}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must be {tuple(shape)}, got {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous, got strides {t.stride()} for {tuple(t.shape)}")
+
+
+def _need_gpu(**tensors):
+    for name, t in tensors.items():
+        if t is not None and not t.is_cuda:
+            raise ValueError(f"{name} must live on the MI355X (got a CPU tensor): there is no CPU path")
+
+
+def conv2d_f32(x, w, bias, y, stride=1, pad=(0, 0), relu=True, c0=0):
+    """exact-fp32 implicit-GEMM convolution (csrc/fid.hip): x f32 NHWC [B, H, W, Cin], w f32 [Cout, kh, kw, Cin], bias f32 [Cout] or
+    None -> the channels [c0, c0 + Cout) of y f32 [B, Ho, Wo, Ctot]; every output is one fmaf chain over (ky, kx, ci)"""
+    _need(x, "x", torch.float32, dims=4)
+    B, H, W, Cin = x.shape
+    _need(w, "w", torch.float32, dims=4)
+    Cout, kh, kw, wc = w.shape
+    if wc != Cin:
+        raise ValueError(f"w must be [Cout, kh, kw, Cin = {Cin}] like x, got {tuple(w.shape)}")
+    if bias is not None:
+        _need(bias, "bias", torch.float32, (Cout,))
+    ho, wo = conv_out_size(H, W, kh, kw, stride, pad[0], pad[1])
+    _need(y, "y", torch.float32, dims=4)
+    if tuple(y.shape[:3]) != (B, ho, wo) or c0 < 0 or c0 + Cout > y.shape[3]:
+        raise ValueError(f"y must be [{B}, {ho}, {wo}, Ctot >= c0 + Cout = {c0 + Cout}], got {tuple(y.shape)}")
+    _need_gpu(x=x, w=w, bias=bias, y=y)
+    _lib.check(_lib_().vtp_conv2d_f32(_p(x), _p(w), _p(bias), _p(y), B, H, W, Cin, Cout, kh, kw, stride, pad[0], pad[1], int(bool(relu)),
+                                      c0, y.shape[3], _s()), "vtp_conv2d_f32")
+
+
+def pool3x3_f32(x, y, stride, mode, c0=0):
+    """3 x 3 pooling of x f32 NHWC [B, H, W, C] into the channels [c0, c0 + C) of y f32 [B, Ho, Wo, Ctot]: stride 1 pads by 1, stride 2
+    by 0; mode POOL_MAX / POOL_AVG / POOL_AVG_INSIDE"""
+    _need(x, "x", torch.float32, dims=4)
+    B, H, W, C = x.shape
+    ho, wo = (H, W) if stride == 1 else ((H - 3) // 2 + 1, (W - 3) // 2 + 1)
+    _need(y, "y", torch.float32, dims=4)
+    if tuple(y.shape[:3]) != (B, ho, wo) or c0 < 0 or c0 + C > y.shape[3]:
+        raise ValueError(f"y must be [{B}, {ho}, {wo}, Ctot >= c0 + C = {c0 + C}], got {tuple(y.shape)}")
+    _need_gpu(x=x, y=y)
+    _lib.check(_lib_().vtp_pool3x3_f32(_p(x), _p(y), B, H, W, C, stride, mode, c0, y.shape[3], _s()), "vtp_pool3x3_f32")
+
+
+def global_avgpool_f32(x, y):
+    """x f32 NHWC [B, H, W, C] -> y f32 [B, C]"""
+    _need(x, "x", torch.float32, dims=4)
+    B, H, W, C = x.shape
+    _need(y, "y", torch.float32, (B, C))
+    _need_gpu(x=x, y=y)
+    _lib.check(_lib_().vtp_global_avgpool_f32(_p(x), _p(y), B, H * W, C, _s()), "vtp_global_avgpool_f32")
+
+
+def resize_bilinear_nhwc(x, y, scale=1.0, shift=0.0):
+    """x f32 NCHW [B, C, H, W] -> y f32 NHWC [B, Ho, Wo, C] = scale * F.interpolate(x, (Ho, Wo), 'bilinear', align_corners=False) +
+    shift; at equal sizes the NCHW -> NHWC repack"""
+    _need(x, "x", torch.float32, dims=4)
+    B, C, H, W = x.shape
+    _need(y, "y", torch.float32, dims=4)
+    if y.shape[0] != B or y.shape[3] != C:
+        raise ValueError(f"y must be [{B}, Ho, Wo, {C}], got {tuple(y.shape)}")
+    _need_gpu(x=x, y=y)
+    _lib.check(_lib_().vtp_resize_bilinear_nhwc(_p(x), _p(y), B, C, H, W, y.shape[1], y.shape[2], scale, shift, _s()),
+               "vtp_resize_bilinear_nhwc")
+
+
+def fid_accum(feats, sum_, outer):
+    """adds the rows of feats f32 [n, D] (row stride >= D), in order, to sum_ f64 [D] and outer f64 [D, D] (x and x x^T); one launch"""
+    if not isinstance(feats, torch.Tensor) or feats.dtype != torch.float32 or feats.dim() != 2 or feats.stride(1) != 1 \
+            or feats.stride(0) < feats.shape[1]:
+        raise ValueError("feats must be an f32 [n, D] tensor with unit column stride and a row stride >= D")
+    n, D = feats.shape
+    _need(sum_, "sum_", torch.float64, (D,))
+    _need(outer, "outer", torch.float64, (D, D))
+    _need_gpu(feats=feats, sum_=sum_, outer=outer)
+    _lib.check(_lib_().vtp_fid_accum(_p(feats), feats.stride(0), _p(sum_), _p(outer), n, D, _s()), "vtp_fid_accum")

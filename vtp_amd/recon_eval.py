@@ -12,8 +12,9 @@ host synchronisation before results() is asked for.
 
 PSNR is averaged over images, SSIM and LPIPS over the batches' means, as the tool does (:386, :392, :395-397, :428-430): a short
 last batch weighs like a full one there.  The per-image means are returned as well.  SSIM is the definition of torchmetrics'
-StructuralSimilarityIndexMeasure(data_range=1.0) (csrc/recon_eval.hip).  rFID is not computed: the two PNG
-folders are what the tool hands pytorch_fid.  There is no CPU path: tensors on the CPU raise."""
+StructuralSimilarityIndexMeasure(data_range=1.0) (csrc/recon_eval.hip, INTEGRATION.md).  rFID: with fid=vtp_amd.FID(...) every
+update also hands the byte images of the two PNG folders to the FID object and results() gains 'fid' (vtp_amd/fid.py); without
+one nothing about it is computed.  There is no CPU path: tensors on the CPU raise."""
 from __future__ import annotations
 
 import os
@@ -77,12 +78,13 @@ def aggregate(acc, with_lpips: bool) -> dict:
 class ReconEval:
     """model: a vtp_amd.VTPModel (None when reconstructions are given: update_pair).  lpips: a vtp_amd.LPIPS or None.  group: a
     process group whose ranks each evaluate their own batches; results() sums the accumulator block over it (the tool's mean of
-    per-rank means when every rank saw as many images and batches, which its DistributedSampler arranges)."""
+    per-rank means when every rank saw as many images and batches, which its DistributedSampler arranges).  fid: a vtp_amd.FID or
+    None; with one, every update feeds it the byte images and results() has 'fid'."""
 
-    def __init__(self, model, lpips=None, group=None, device=None):
+    def __init__(self, model, lpips=None, group=None, device=None, fid=None):
         if not torch.cuda.is_available():
             raise RuntimeError("vtp_amd.ReconEval runs on the MI355X kernels only (no CPU fallback)")
-        self.model, self.lpips, self.group = model, lpips, group
+        self.model, self.lpips, self.group, self.fid = model, lpips, group, fid
         if device is None:
             device = next(model.parameters()).device if model is not None else torch.device("cuda", torch.cuda.current_device())
         self.device = torch.device(device)
@@ -136,14 +138,17 @@ class ReconEval:
         psnr = torch.empty(B, device=dev, dtype=torch.float32)
         ssim = torch.empty(B, device=dev, dtype=torch.float32)
         sse = torch.empty(B, device=dev, dtype=torch.float64)
-        ref_u8 = torch.empty(B, H, W, 3, device=dev, dtype=torch.uint8) if want_u8 else None
-        rec_u8 = torch.empty(B, H, W, 3, device=dev, dtype=torch.uint8) if want_u8 else None
+        need_u8 = want_u8 or self.fid is not None
+        ref_u8 = torch.empty(B, H, W, 3, device=dev, dtype=torch.uint8) if need_u8 else None
+        rec_u8 = torch.empty(B, H, W, 3, device=dev, dtype=torch.uint8) if need_u8 else None
         ops.recon_metrics(x, r, self.sub, self.div, ws["scratch"], ref_u8, rec_u8, ws.get("ref_lp"), ws.get("rec_lp"))
         lp = None
         if self.lpips is not None:
             lp = self.lpips(ws["ref_lp"], ws["rec_lp"]).reshape(B).to(torch.float32).contiguous()  # lpips_metric(orig, recon) (:383)
         ops.recon_finalize(ws["scratch"], B, H, W, psnr, ssim, self._acc, sse, lp)
-        return ReconBatch(psnr, ssim, sse, lp, ref_u8, rec_u8)
+        if self.fid is not None:
+            self.fid.update(ref_u8, rec_u8)
+        return ReconBatch(psnr, ssim, sse, lp, ref_u8 if want_u8 else None, rec_u8 if want_u8 else None)
 
     def accumulators(self) -> torch.Tensor:
         """the accumulator block, summed over the process group with one all-reduce; one copy to the host (CPU f64 [8])"""
@@ -154,7 +159,12 @@ class ReconEval:
         return t.cpu()
 
     def results(self) -> dict:
-        return aggregate(self.accumulators().tolist(), self.lpips is not None)
+        res = aggregate(self.accumulators().tolist(), self.lpips is not None)
+        if self.fid is not None:
+            res["fid"] = self.fid.result()
+        return res
 
     def reset(self) -> None:
         self._acc.zero_()
+        if self.fid is not None:
+            self.fid.reset()
