@@ -631,6 +631,33 @@ int vtp_resize_bilinear_nhwc(const float* x, float* y, int B, int C, int H, int 
                              void* stream);
 int vtp_fid_accum(const float* feats, int ldf, double* sum, double* outer, int n, int D, void* stream);
 
+/* ---- fp32 inference forward (fp32.hip and fp32 variants of the row kernels): what the reference computes with fp32 weights and no
+ * autocast.  Every tensor is f32; the products run on v_mfma_f32_32x32x2_f32.
+ * vtp_gemm_nt_f32: C[M, N] = epi(A[M, K] W[N, K]^T).  Every output element is ONE fmaf chain over k = 0 .. K - 1 (no split of K, no
+ *   atomics): its bits depend on its row of A and its row of W alone -- not on M or the batch the row came with -- and repeat from run
+ *   to run.  Any M >= 1; N and K multiples of 8; lda, ldw multiples of 4; A, W, W2 16-byte aligned.  epi:
+ *     0  C = acc + bias                                   (bias NULL: none)
+ *     1  C = resid + gamma (.) (acc + bias)               (LayerScale gamma [N] or NULL; resid f32 [M, N], row stride ldr; may alias C)
+ *     2  C[M, N] = silu(A W^T + bias) * (A W2^T + bias2)  (SwiGLU; W and W2 are [N, K], N = the hidden width)
+ *     3  C = gelu_erf(acc + bias)        4  C = quick_gelu(acc + bias) = y / (1 + exp(-1.702 y))
+ *   W2 / bias2 belong to epi 2 alone, gamma / resid to epi 1.
+ * vtp_attn_fwd_f32: o = softmax(scale q k^T) v per (batch, head), head dimension 64; element strides as vtp_attn_fwd (batch sb, token
+ *   sn, head h at + 64 h; o: sbo, sno), all multiples of 4, pointers 16-byte aligned.  Any N >= 1: keys past N (and key > query when
+ *   causal != 0) are masked out of the softmax.  Online softmax in fp32; a sequence's result does not depend on the batch around it.
+ * vtp_norm_fwd_f32: vtp_norm_fwd with the un-rounded f32 output.  vtp_rope_qk_f32: apply_rope (attention.py:70-89) in place on the q and
+ *   k thirds of an f32 [B*N, 3*D] buffer: round to bf16, the arithmetic of vtp_rope_qk, widen back; v untouched.
+ * vtp_im2col16_rows_f32 / vtp_pixel_shuffle16_f32 / vtp_pool_patch_rows_f32: the bf16 entry points' data movement on f32 rows. */
+int vtp_gemm_nt_f32(const float* A, int lda, const float* W, int ldw, const float* W2, float* C, int ldc, const float* bias,
+                    const float* bias2, const float* gamma, const float* resid, int ldr, int M, int N, int K, int epilogue, void* stream);
+int vtp_attn_fwd_f32(const float* q, const float* k, const float* v, float* o, int B, int N, int heads, long sb, long sn, long sbo,
+                     long sno, float scale, int causal, void* stream);
+int vtp_norm_fwd_f32(const float* x, const float* w, const float* b, float* y, float* stats, int M, int D, float eps, int kind,
+                     void* stream);
+int vtp_rope_qk_f32(float* qkv, const void* sin, const void* cos, int B, int N, int heads, int prefix, void* stream);
+int vtp_im2col16_rows_f32(const float* img, float* rows, int B, int H, int W, int prefix, void* stream);
+int vtp_pixel_shuffle16_f32(const float* t, float* img, int B, int h, int w, void* stream);
+int vtp_pool_patch_rows_f32(const float* x, float* out, int B, int N, int D, float scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

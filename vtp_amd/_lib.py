@@ -149,6 +149,14 @@ SIGNATURES = {
     "vtp_global_avgpool_f32": [_P, _P, _I, _I, _I, _P],  # x y B HW C stream
     "vtp_resize_bilinear_nhwc": [_P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _P],  # x y B C H W Ho Wo scale shift stream
     "vtp_fid_accum": [_P, _I, _P, _P, _I, _I, _P],  # feats ldf sum outer n D stream
+    # fp32 inference forward.  A lda W ldw W2 C ldc bias bias2 gamma resid ldr M N K epilogue stream
+    "vtp_gemm_nt_f32": [_P, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "vtp_attn_fwd_f32": [_P, _P, _P, _P, _I, _I, _I, _L, _L, _L, _L, _F, _I, _P],
+    "vtp_norm_fwd_f32": [_P, _P, _P, _P, _P, _I, _I, _F, _I, _P],
+    "vtp_rope_qk_f32": [_P, _P, _P, _I, _I, _I, _I, _P],
+    "vtp_im2col16_rows_f32": [_P, _P, _I, _I, _I, _I, _P],
+    "vtp_pixel_shuffle16_f32": [_P, _P, _I, _I, _I, _P],
+    "vtp_pool_patch_rows_f32": [_P, _P, _I, _I, _I, _F, _P],
 }
 
 _lib = None

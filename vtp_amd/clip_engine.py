@@ -36,6 +36,7 @@ class TextEngine:
         # text_projection is stored [width, output_dim] and applied as x @ P (modeling_vtp.py:308): as a Lin with
         # N = width, K = output_dim its bf16 copy `w` is P and `wT` is P^T (the K-contiguous operand of the forward GEMM)
         self.proj = store.lin("text_projection", None, self.D, self.Dout)
+        self.projT32 = None  # fp32 forward: P^T f32 [Dout, D], derived data (enable_fp32), refreshed with the bf16 copies
         self.ws: Dict[tuple, Workspace] = {}
 
     def workspace(self, B) -> Workspace:
@@ -43,9 +44,55 @@ class TextEngine:
             self.ws[B] = Workspace(self.store.device)
         return self.ws[B]
 
-    def forward(self, ids: torch.Tensor, train: bool) -> torch.Tensor:
+    def enable_fp32(self):
+        """derive what the fp32 forward needs beyond the masters: the K-contiguous transpose of text_projection.  Rebuilt wherever the
+        bf16 copies are (a ParamStore prep hook)."""
+        self.stack.fp32_check("text")
+        if self.D % 8 or self.Dout % 8:
+            raise NotImplementedError(f"fp32 forward (text): text_embed_dim must be a multiple of 8 (got {self.D})")
+        if self.projT32 is None:
+            self.projT32 = torch.empty(self.Dout, self.D, dtype=F32, device=self.store.device)
+            if not hasattr(self.store, "prep_hooks"):
+                self.store.prep_hooks = []
+            self.store.prep_hooks.append(self._refresh_fp32)
+        self._refresh_fp32()
+
+    def _refresh_fp32(self):
+        self.projT32.copy_(self.proj.w32.t())
+
+    def _forward_fp32(self, ids: torch.Tensor) -> torch.Tensor:
+        """forward(train=False) in fp32: all B * T rows (no packed captions), Stack._forward_fp32, ln_final and the projection in fp32"""
+        st, D = self.store, self.D
+        B, T = ids.shape
+        if self.projT32 is None:
+            raise RuntimeError("TextEngine: the fp32 forward was not enabled (enable_fp32)")
+        ws = self.workspace(B)
+        x0 = ws.get("f32.x0", (B * T, D), F32)
+        eot = ws.get("f32.eot", (B,), I32)
+        self.stack.varlen = None
+        ops.embed_tokens(ids, st.p("token_embedding.weight"), st.p("positional_embedding"), x0, eot, B, T, D)
+        if self.pool in ("first", "last"):
+            eot.fill_(0 if self.pool == "first" else T - 1)
+        xl = self.stack.forward(ws, x0, [(B, T, None)], 0, False, fp32=True)
+        R = B * T
+        if self.pool != "none":  # ln_final is row-wise: pool first
+            R = B
+            pooled = ws.get("f32.pooled", (B, D), F32)
+            ops.gather_rows(xl, eot, pooled, B, T, D)
+            xl = pooled
+        xn = ws.get("f32.xn_final", (R, D), F32)
+        ops.norm_fwd_f32(xl, st.p("ln_final.weight"), st.p("ln_final.bias"), xn, ws.get("f32.stf", (R, 2), F32), R, D, 1e-5, ops.NORM_LN)
+        feat = ws.get("f32.feat", (R, self.Dout), F32)
+        ops.gemm_nt_f32(xn, self.projT32, feat, M=R, N=self.Dout, K=D)
+        return feat
+
+    def forward(self, ids: torch.Tensor, train: bool, fp32: bool = False) -> torch.Tensor:
         """ids int64 [B, T] (device) -> un-normalised text features f32 [B, Dout]  (modeling_vtp.py:278-310); text_pool_type = "none"
         (text_global_pool's fall-through, text_transformer.py:225-226): every token, f32 [B * T, Dout]."""
+        if fp32:
+            if train:
+                raise RuntimeError("TextEngine: the fp32 forward is an inference pass (train=False)")
+            return self._forward_fp32(ids)
         st = self.store
         B, T = ids.shape
         D = self.D
@@ -173,6 +220,25 @@ class ClipHead:
         self._in = x
         f = ws.get(f"f_img{B}", (B, self.Dt), F32)
         ops.gemm_nt(x, self.vproj.w, f, M=B, N=self.Dt, K=self.vproj.K, lda=lda, epi=EPI_F32)
+        return f
+
+    def image_features_fp32(self, xnf: torch.Tensor, B: int, N: int) -> torch.Tensor:
+        """image_features on the fp32 forward's token rows (f32 [B*N, Dv]), every product in fp32"""
+        ws, D = self.ws, self.Dv
+        if self.feat == "cls":
+            x, lda = xnf, N * D
+        else:
+            x = ws.get(f"f32.pool{B}", (B, D), F32)
+            ops.pool_patch_rows_f32(xnf, x, B, N, D)
+            lda = D
+        K = D
+        if self.trunk is not None:
+            K = self.trunk.bott_dim
+            z = ws.get(f"f32.z{B}", (B, K), F32)
+            ops.gemm_nt_f32(x, self.trunk.bott.w32, z, M=B, N=K, K=D, lda=lda)
+            x, lda = z, K
+        f = ws.get(f"f32.f_img{B}", (B, self.Dt), F32)
+        ops.gemm_nt_f32(x, self.vproj.w32, f, M=B, N=self.Dt, K=K, lda=lda)
         return f
 
     def normalize(self, f: torch.Tensor, tag: str):

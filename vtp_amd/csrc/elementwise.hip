@@ -6,6 +6,53 @@ namespace vtp {
 
 // ---------------------------------------------------------------- RoPE (attention.py:12-23,70-89)
 // work item = (row, part{q,k}, head, 8-pair group): 16 B from the x[0:32) half + 16 B from the x[32:64) half.
+// out = x*cos + rot_half(x)*sin ; rot_half(x) = [-x2, x1]  -- three bf16 roundings like eager
+__device__ __forceinline__ void rope_rot(float a, float b, bf16 c1, bf16 s1, bf16 c2, bf16 s2, bf16& o1, bf16& o2) {
+  o1 = f2bf(bf2f(f2bf(a * bf2f(c1))) + bf2f(f2bf(-b * bf2f(s1))));
+  o2 = f2bf(bf2f(f2bf(b * bf2f(c2))) + bf2f(f2bf(a * bf2f(s2))));
+}
+
+// apply_rope on fp32 q / k (the fp32 forward): attention.py:70-89 casts q and k to the RoPE dtype, rotates there and casts back -- the
+// arithmetic of rope_qk_kernel between an fp32 -> bf16 rounding and the exact widening of its result.  v is not touched.
+__global__ __launch_bounds__(256) void rope_qk_f32_kernel(float* __restrict__ qkv, const bf16* __restrict__ sin_t,
+                                                          const bf16* __restrict__ cos_t, int B, int N, int heads, int prefix) {
+  const int D = heads * 64;
+  const long per_row = 2L * heads * 4;
+  const long total = (long)B * N * per_row;
+  for (long idx = blockIdx.x * 256L + threadIdx.x; idx < total; idx += (long)gridDim.x * 256L) {
+    const long row = idx / per_row;
+    const int rem = (int)(idx - row * per_row);
+    const int n = (int)(row % N);
+    const int part = rem / (heads * 4);
+    const int h = (rem / 4) % heads;
+    const int g = rem & 3;
+    float* p = qkv + row * (3L * D) + (long)part * D + h * 64 + g * 8;
+    f32x4 x1[2] = {*(const f32x4*)p, *(const f32x4*)(p + 4)}, x2[2] = {*(const f32x4*)(p + 32), *(const f32x4*)(p + 36)};
+    if (n < prefix) {  // the un-rotated prefix (cls) rows take the cast to the RoPE dtype and back as well (attention.py:78-79)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        x1[e >> 2][e & 3] = bf2f(f2bf(x1[e >> 2][e & 3]));
+        x2[e >> 2][e & 3] = bf2f(f2bf(x2[e >> 2][e & 3]));
+      }
+    } else {
+      const long t = (long)(n - prefix) * 64 + g * 8;
+      bf16x8 c1 = *(const bf16x8*)(cos_t + t), c2 = *(const bf16x8*)(cos_t + t + 32);
+      bf16x8 s1 = *(const bf16x8*)(sin_t + t), s2 = *(const bf16x8*)(sin_t + t + 32);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        bf16 o1, o2;
+        rope_rot(bf2f(f2bf(x1[e >> 2][e & 3])), bf2f(f2bf(x2[e >> 2][e & 3])), c1[e], s1[e], c2[e], s2[e], o1, o2);
+        x1[e >> 2][e & 3] = bf2f(o1);
+        x2[e >> 2][e & 3] = bf2f(o2);
+      }
+    }
+    *(f32x4*)p = x1[0];
+    *(f32x4*)(p + 4) = x1[1];
+    *(f32x4*)(p + 32) = x2[0];
+    *(f32x4*)(p + 36) = x2[1];
+  }
+}
+
 template <bool INVERSE>
 __global__ __launch_bounds__(256) void rope_qk_kernel(bf16* __restrict__ qkv, const bf16* __restrict__ sin_t,
                                                       const bf16* __restrict__ cos_t, int B, int N, int heads,
@@ -31,9 +78,10 @@ __global__ __launch_bounds__(256) void rope_qk_kernel(bf16* __restrict__ qkv, co
     for (int e = 0; e < 8; ++e) {
       const float a = bf2f(x1[e]), b = bf2f(x2[e]);
       if (!INVERSE) {
-        // out = x*cos + rot_half(x)*sin ; rot_half(x) = [-x2, x1]  -- three bf16 roundings like eager
-        o1[e] = f2bf(bf2f(f2bf(a * bf2f(c1[e]))) + bf2f(f2bf(-b * bf2f(s1[e]))));
-        o2[e] = f2bf(bf2f(f2bf(b * bf2f(c2[e]))) + bf2f(f2bf(a * bf2f(s2[e]))));
+        bf16 r1, r2;
+        rope_rot(a, b, c1[e], s1[e], c2[e], s2[e], r1, r2);
+        o1[e] = r1;
+        o2[e] = r2;
       } else {
         // transpose: dx1 = g1*cos1 + g2*sin2 ; dx2 = g2*cos2 - g1*sin1
         o1[e] = f2bf(bf2f(f2bf(a * bf2f(c1[e]))) + bf2f(f2bf(b * bf2f(s2[e]))));
@@ -48,8 +96,10 @@ __global__ __launch_bounds__(256) void rope_qk_kernel(bf16* __restrict__ qkv, co
 // ---------------------------------------------------------------- im2col for the k=s=16 patch-embed conv
 // work item = (token, c, ky): 16 contiguous pixels -> 16 bf16 at K offset c*256 + ky*16.
 // pre: patch p of image b goes to row b * (h w + pre) + pre + p -- pre = 1 is the token layout of the trunk (row 0 of an image = cls)
-__global__ __launch_bounds__(256) void im2col16_kernel(const float* __restrict__ img, bf16* __restrict__ patches,
+template <typename OUT>  // bf16 GEMM operand rows, or the pixels as they are (the fp32 forward)
+__global__ __launch_bounds__(256) void im2col16_kernel(const float* __restrict__ img, OUT* __restrict__ patches,
                                                        int B, int H, int W, int pre) {
+  typedef __attribute__((ext_vector_type(4))) OUT out4;
   const int h = H / 16, w = W / 16;
   const long total = (long)B * h * w * 48;
   for (long idx = blockIdx.x * 256L + threadIdx.x; idx < total; idx += (long)gridDim.x * 256L) {
@@ -60,11 +110,11 @@ __global__ __launch_bounds__(256) void im2col16_kernel(const float* __restrict__
     const int y = (int)((tok / w) % h);
     const long b = tok / ((long)w * h);
     const float* src = img + ((b * 3 + c) * H + (y * 16 + ky)) * (long)W + x * 16;
-    bf16* dst = patches + (tok + (b + 1) * pre) * 768 + c * 256 + ky * 16;
+    OUT* dst = patches + (tok + (b + 1) * pre) * 768 + c * 256 + ky * 16;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       f32x4 v = *(const f32x4*)(src + 4 * i);
-      *(bf16x4*)(dst + 4 * i) = __builtin_convertvector(v, bf16x4);
+      *(out4*)(dst + 4 * i) = __builtin_convertvector(v, out4);
     }
   }
 }
@@ -89,8 +139,8 @@ __global__ __launch_bounds__(256) void col2im16_kernel(const float* __restrict__
 }
 
 // PixelShuffle(16) of the token-major decoder output (+ optional fused L1 loss / gradient).
-template <int MODE>  // 0: write f32 image; 1: L1 loss + dt; 2: dt = un-shuffled image gradient (`img` holds d_img)
-__global__ __launch_bounds__(256) void shuffle16_kernel(const bf16* __restrict__ t, float* __restrict__ img,
+template <int MODE, typename IN = bf16>  // 0: write f32 image; 1: L1 loss + dt; 2: dt = un-shuffled image gradient (`img` holds d_img)
+__global__ __launch_bounds__(256) void shuffle16_kernel(const IN* __restrict__ t, float* __restrict__ img,
                                                         const float* __restrict__ target, bf16* __restrict__ dt,
                                                         float* __restrict__ loss_sum, int B, int h, int w, float gscale) {
   const int H = h * 16, W = w * 16;
@@ -111,7 +161,8 @@ __global__ __launch_bounds__(256) void shuffle16_kernel(const bf16* __restrict__
         *(bf16x4*)(dt + toff + 4 * q) = __builtin_convertvector(*(const f32x4*)(img + ioff + 4 * q), bf16x4);
         continue;
       }
-      f32x4 v = __builtin_convertvector(*(const bf16x4*)(t + toff + 4 * q), f32x4);
+      typedef __attribute__((ext_vector_type(4))) IN in4;
+      f32x4 v = __builtin_convertvector(*(const in4*)(t + toff + 4 * q), f32x4);
       if (MODE == 0) {
         *(f32x4*)(img + ioff + 4 * q) = v;
       } else {
@@ -704,7 +755,7 @@ extern "C" int vtp_im2col16(const float* img, void* patches, int B, int H, int W
   VTP_REQUIRE(img && patches, "vtp_im2col16: null pointer");
   VTP_REQUIRE(B > 0 && H > 0 && W > 0 && H % 16 == 0 && W % 16 == 0, "vtp_im2col16: H and W must be positive multiples of 16");
   const long items = (long)B * (H / 16) * (W / 16) * 48;
-  hipLaunchKernelGGL(im2col16_kernel, dim3(grid_for(items)), dim3(256), 0, (hipStream_t)stream, img, (bf16*)patches, B, H, W, 0);
+  hipLaunchKernelGGL(im2col16_kernel<bf16>, dim3(grid_for(items)), dim3(256), 0, (hipStream_t)stream, img, (bf16*)patches, B, H, W, 0);
   return check_launch("im2col16");
 }
 
@@ -712,8 +763,25 @@ extern "C" int vtp_im2col16_rows(const float* img, void* rows, int B, int H, int
   VTP_REQUIRE(img && rows, "vtp_im2col16_rows: null pointer");
   VTP_REQUIRE(B > 0 && H > 0 && W > 0 && H % 16 == 0 && W % 16 == 0 && prefix >= 0, "vtp_im2col16_rows: H and W must be positive multiples of 16, prefix >= 0");
   const long items = (long)B * (H / 16) * (W / 16) * 48;
-  hipLaunchKernelGGL(im2col16_kernel, dim3(grid_for(items)), dim3(256), 0, (hipStream_t)stream, img, (bf16*)rows, B, H, W, prefix);
+  hipLaunchKernelGGL(im2col16_kernel<bf16>, dim3(grid_for(items)), dim3(256), 0, (hipStream_t)stream, img, (bf16*)rows, B, H, W, prefix);
   return check_launch("im2col16_rows");
+}
+
+extern "C" int vtp_im2col16_rows_f32(const float* img, float* rows, int B, int H, int W, int prefix, void* stream) {
+  VTP_REQUIRE(img && rows, "vtp_im2col16_rows_f32: null pointer");
+  VTP_REQUIRE(B > 0 && H > 0 && W > 0 && H % 16 == 0 && W % 16 == 0 && prefix >= 0, "vtp_im2col16_rows_f32: H and W must be positive multiples of 16, prefix >= 0");
+  const long items = (long)B * (H / 16) * (W / 16) * 48;
+  hipLaunchKernelGGL(im2col16_kernel<float>, dim3(grid_for(items)), dim3(256), 0, (hipStream_t)stream, img, rows, B, H, W, prefix);
+  return check_launch("im2col16_rows_f32");
+}
+
+extern "C" int vtp_rope_qk_f32(float* qkv, const void* sin, const void* cos, int B, int N, int heads, int prefix, void* stream) {
+  VTP_REQUIRE(qkv && sin && cos, "vtp_rope_qk_f32: null pointer");
+  VTP_REQUIRE(B > 0 && N > 0 && heads > 0 && prefix >= 0 && prefix <= N, "vtp_rope_qk_f32: bad shape (prefix must be in [0,N])");
+  const long items = (long)B * N * 2 * heads * 4;
+  hipLaunchKernelGGL(rope_qk_f32_kernel, dim3(grid_for(items)), dim3(256), 0, (hipStream_t)stream, qkv, (const bf16*)sin, (const bf16*)cos,
+                     B, N, heads, prefix);
+  return check_launch("rope_qk_f32");
 }
 
 extern "C" int vtp_col2im16(const float* dpatches, float* dimg, int B, int H, int W, void* stream) {
@@ -858,6 +926,13 @@ extern "C" int vtp_pixel_shuffle16(const void* t, float* img, int B, int h, int 
   hipLaunchKernelGGL(shuffle16_kernel<0>, dim3(grid_for((long)B * h * w * 48)), dim3(256), 0, (hipStream_t)stream,
                      (const bf16*)t, img, nullptr, nullptr, nullptr, B, h, w, 0.f);
   return check_launch("pixel_shuffle16");
+}
+
+extern "C" int vtp_pixel_shuffle16_f32(const float* t, float* img, int B, int h, int w, void* stream) {
+  VTP_REQUIRE(t && img && B > 0 && h > 0 && w > 0, "vtp_pixel_shuffle16_f32: bad argument");
+  hipLaunchKernelGGL((shuffle16_kernel<0, float>), dim3(grid_for((long)B * h * w * 48)), dim3(256), 0, (hipStream_t)stream, t, img, nullptr,
+                     nullptr, nullptr, B, h, w, 0.f);
+  return check_launch("pixel_shuffle16_f32");
 }
 
 extern "C" int vtp_pixel_unshuffle16(const float* d_img, void* dt, int B, int h, int w, void* stream) {

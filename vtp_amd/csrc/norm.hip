@@ -11,9 +11,9 @@ namespace vtp {
 
 constexpr int NORM_MAXC = 8;  // float4 chunks per lane -> D <= 8*64*4 = 2048 (template NC = ceil(D/256))
 
-template <int KIND, int NC>  // KIND 0 rms, 1 layernorm; NC float4 chunks per lane
+template <int KIND, int NC, typename OUT = bf16>  // KIND 0 rms, 1 layernorm; NC float4 chunks per lane; OUT float: the un-rounded output
 __global__ __launch_bounds__(256) void norm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                       const float* __restrict__ b, bf16* __restrict__ y,
+                                                       const float* __restrict__ b, OUT* __restrict__ y,
                                                        float* __restrict__ stats, int M, int D, float eps,
                                                        uint8_t* __restrict__ y8 = nullptr, const float* __restrict__ q_scale = nullptr,
                                                        const int* __restrict__ m_rows = nullptr) {
@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256) void norm_fwd_kernel(const float* __restrict__
     q = wave_sum(q);
     rstd = rsqrtf(q / D + eps);
   }
-  bf16* yr = y + (size_t)row * D;
+  OUT* yr = y + (size_t)row * D;
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
     const int col = (c * 64 + lane) * 4;
@@ -71,6 +71,10 @@ __global__ __launch_bounds__(256) void norm_fwd_kernel(const float* __restrict__
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = (v[c][e] - mean) * rstd * wv[e] + bv[e];
       }
+      if constexpr (std::is_same_v<OUT, float>) {  // the fp32 forward: the value the bf16 output rounds
+        *(f32x4*)(yr + col) = o;
+        continue;
+      }
       const bf16x4 ob = __builtin_convertvector(o, bf16x4);
       if (y8) {
         const float qs = *q_scale;
@@ -80,7 +84,7 @@ __global__ __launch_bounds__(256) void norm_fwd_kernel(const float* __restrict__
         uint32_t wq = __builtin_amdgcn_cvt_pk_fp8_f32(q[0], q[1], 0u, false);
         wq = __builtin_amdgcn_cvt_pk_fp8_f32(q[2], q[3], wq, true);
         *(uint32_t*)(y8 + (size_t)row * D + col) = wq;
-      } else {
+      } else if constexpr (!std::is_same_v<OUT, float>) {
         *(bf16x4*)(yr + col) = ob;
       }
     }
@@ -233,24 +237,26 @@ __global__ __launch_bounds__(256, 2) void norm_bwd_kernel(const bf16* __restrict
 // flight per wave, and are summed through LDS in a fixed order (deterministic, no atomics)
 constexpr int POOL_WAVES = 8;
 
-__global__ __launch_bounds__(POOL_WAVES * 64) void pool_patch_rows_kernel(const bf16* __restrict__ x, float* __restrict__ out, int N,
+template <typename IN>  // bf16 token rows, or the fp32 forward's
+__global__ __launch_bounds__(POOL_WAVES * 64) void pool_patch_rows_kernel(const IN* __restrict__ x, float* __restrict__ out, int N,
                                                                          int D, float scale) {
+  typedef __attribute__((ext_vector_type(4))) IN in4;
   const int lane = threadIdx.x & 63;
   const int wv = threadIdx.x >> 6;
   const int col = (blockIdx.x * 64 + lane) * 4;
   const int b = blockIdx.y;
   f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
   if (col < D) {
-    const bf16* xb = x + (size_t)b * N * D + col;
+    const IN* xb = x + (size_t)b * N * D + col;
     int t = 1 + wv;
     for (; t + 3 * POOL_WAVES < N; t += 4 * POOL_WAVES) {
-      bf16x4 v[4];
+      in4 v[4];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) v[u] = *(const bf16x4*)(xb + (size_t)(t + u * POOL_WAVES) * D);
+      for (int u = 0; u < 4; ++u) v[u] = *(const in4*)(xb + (size_t)(t + u * POOL_WAVES) * D);
 #pragma unroll
       for (int u = 0; u < 4; ++u) acc += __builtin_convertvector(v[u], f32x4);
     }
-    for (; t < N; t += POOL_WAVES) acc += __builtin_convertvector(*(const bf16x4*)(xb + (size_t)t * D), f32x4);
+    for (; t < N; t += POOL_WAVES) acc += __builtin_convertvector(*(const in4*)(xb + (size_t)t * D), f32x4);
   }
   __shared__ f32x4 red[POOL_WAVES][64];
   red[wv][lane] = acc;
@@ -277,6 +283,7 @@ struct NormFwdArgs {
   float eps;
   int kind;
   const int* m_rows;
+  float* y32 = nullptr;  // the fp32 output instead of y
 };
 
 // everything norm_bwd_kernel takes (pvec .. pN: the pooled-vector variant; dres_rows / dres_M: the row-mapped one)
@@ -317,8 +324,12 @@ static int launch_norm_fwd(const char* who, const char* label, const NormFwdArgs
               NORM_MAXC * 256, a.D);
   VTP_REQUIRE(a.kind == 0 || (a.kind == 1 && a.b), "%s: kind must be 0 (rms) or 1 (layernorm, needs bias)", who);
   norm_dispatch<true>(a.kind, a.D, [&](auto kc, auto nc) {
-    hipLaunchKernelGGL((norm_fwd_kernel<decltype(kc)::value, decltype(nc)::value>), dim3(cdiv(a.M, 4)), dim3(256), 0, (hipStream_t)stream,
-                       a.x, a.w, a.b, a.y, a.stats, a.M, a.D, a.eps, a.y8, a.q_scale, a.m_rows);
+    if (a.y32)
+      hipLaunchKernelGGL((norm_fwd_kernel<decltype(kc)::value, decltype(nc)::value, float>), dim3(cdiv(a.M, 4)), dim3(256), 0,
+                         (hipStream_t)stream, a.x, a.w, a.b, a.y32, a.stats, a.M, a.D, a.eps, nullptr, nullptr, a.m_rows);
+    else
+      hipLaunchKernelGGL((norm_fwd_kernel<decltype(kc)::value, decltype(nc)::value>), dim3(cdiv(a.M, 4)), dim3(256), 0, (hipStream_t)stream,
+                         a.x, a.w, a.b, a.y, a.stats, a.M, a.D, a.eps, a.y8, a.q_scale, a.m_rows);
   });
   return check_launch(label);
 }
@@ -376,6 +387,14 @@ extern "C" int vtp_norm_fwd_e4m3(const float* x, const float* w, const float* b,
                          stream);
 }
 
+extern "C" int vtp_norm_fwd_f32(const float* x, const float* w, const float* b, float* y, float* stats, int M, int D, float eps, int kind,
+                                void* stream) {
+  VTP_REQUIRE(x && w && y, "vtp_norm_fwd_f32: null pointer");
+  NormFwdArgs a = {x, w, b, nullptr, nullptr, nullptr, stats, M, D, eps, kind, nullptr};
+  a.y32 = y;
+  return launch_norm_fwd("vtp_norm_fwd_f32", "norm_fwd_f32", a, stream);
+}
+
 // the arguments every backward entry has; the variants set their own fields on top
 static NormBwdArgs norm_bwd_args(const void* dy, const float* x, const float* w, const float* stats, const float* dres, float* dx,
                                  void* dx_bf16, float* dw, float* db, float* dx_colsum, int M, int D, int kind) {
@@ -427,7 +446,15 @@ extern "C" int vtp_pool_patch_rows(const void* x, float* out, int B, int N, int 
   VTP_REQUIRE(x && out, "vtp_pool_patch_rows: null pointer");
   VTP_REQUIRE(B > 0 && N >= 2 && D > 0 && D % 4 == 0, "vtp_pool_patch_rows: need B > 0, N >= 2, D %% 4 == 0 (B=%d N=%d D=%d)", B, N, D);
   VTP_REQUIRE((long)B * N * D < (1L << 40), "vtp_pool_patch_rows: matrix too large");
-  hipLaunchKernelGGL(pool_patch_rows_kernel, dim3(cdiv(D, 256), B), dim3(POOL_WAVES * 64), 0, (hipStream_t)stream, (const bf16*)x, out,
+  hipLaunchKernelGGL(pool_patch_rows_kernel<bf16>, dim3(cdiv(D, 256), B), dim3(POOL_WAVES * 64), 0, (hipStream_t)stream, (const bf16*)x, out,
                      N, D, scale);
   return check_launch("pool_patch_rows");
+}
+
+extern "C" int vtp_pool_patch_rows_f32(const float* x, float* out, int B, int N, int D, float scale, void* stream) {
+  VTP_REQUIRE(x && out, "vtp_pool_patch_rows_f32: null pointer");
+  VTP_REQUIRE(B > 0 && N >= 2 && D > 0 && D % 4 == 0, "vtp_pool_patch_rows_f32: need B > 0, N >= 2, D %% 4 == 0 (B=%d N=%d D=%d)", B, N, D);
+  VTP_REQUIRE((long)B * N * D < (1L << 40), "vtp_pool_patch_rows_f32: matrix too large");
+  hipLaunchKernelGGL(pool_patch_rows_kernel<float>, dim3(cdiv(D, 256), B), dim3(POOL_WAVES * 64), 0, (hipStream_t)stream, x, out, N, D, scale);
+  return check_launch("pool_patch_rows_f32");
 }

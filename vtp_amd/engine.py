@@ -491,6 +491,9 @@ class Stack:
             b.proj = store.lin(pre + nm["proj_w"], pre + nm["proj_b"], D, D)
             if self.swiglu:
                 b.w12 = store.swiglu(pre + "mlp.", H, D)
+                # the fp32 forward multiplies by the masters themselves: w1 and w2 as two operands of one launch, nothing derived
+                b.w1_32, b.w2_32 = store.p(pre + "mlp.w1.weight").view(H, D), store.p(pre + "mlp.w2.weight").view(H, D)
+                b.b1_32, b.b2_32 = store.p(pre + "mlp.w1.bias"), store.p(pre + "mlp.w2.bias")
                 b.w3 = store.lin(pre + "mlp.w3.weight", pre + "mlp.w3.bias", D, H)
             else:
                 n1, n2 = ("fc1", "fc2") if style == "vit" else ("c_fc", "c_proj")
@@ -838,7 +841,7 @@ class Stack:
                 and getattr(self, "fp8", None) is None and self.D % 8 == 0 and self.D <= 1024
                 and self.blocks[-1].ls1 is None and self.blocks[-1].ls2 is None)
 
-    def forward(self, ws: Workspace, x, segs, prefix_tokens: int, train: bool, tail=None):
+    def forward(self, ws: Workspace, x, segs, prefix_tokens: int, train: bool, tail=None, fp32: bool = False, keep: bool = False):
         """`segs` = [(B_i, N_i, rope_i)]: several batches of different sequence length concatenated along the token-row
         axis (the reference's list path, block.py:235-298 / utils.py:14-25 cat_keep_shapes): every linear / norm runs once
         over all rows, RoPE and attention run per segment on its row range.  In training with a drop plan set (stochastic depth)
@@ -849,6 +852,10 @@ class Stack:
         full row L + idx[t], zero-input rows for the padding.  The kept rows are bit-identical to the full pass."""
         D = self.D
         M = sum(b * n for b, n, _ in segs)
+        if fp32:  # the fp32 inference forward (_forward_fp32): plain full rows, inference only
+            if train or tail is not None or self.varlen is not None:
+                raise RuntimeError("Stack.forward: the fp32 forward is an inference pass over plain full rows (no train, tail or packed rows)")
+            return self._forward_fp32(ws, x, segs, prefix_tokens, M, keep)
         if tail is not None and not self.tail_rows_ok(train):
             raise RuntimeError("Stack.forward: a tail row plan was passed to a pass that cannot take one (tail_rows_ok)")
         if self.varlen is not None and not (self.varlen_ok(M) and tail is None and len(segs) == 1 and segs[0][2] is None):
@@ -961,6 +968,46 @@ class Stack:
             ops.gemm_nt_fp8(a8, w8[2], hid, M=M, N=2 * H, K=D, alpha=al[2], bias=b.w12.b12, epi=EPI_SWIGLU)
             ops.quantize_e4m3(hid, a8, sc[3:4])
             ops.gemm_nt_fp8(a8, w8[3], xout, M=M, N=D, K=H, alpha=al[3], bias=b.w3.bias, resid=xmid, epi=EPI_F32)
+            x = xout
+        return x
+
+    # ---- fp32 inference forward: the reference with fp32 weights and no autocast (oracle/vtp_oracle.py on fp32 tensors)
+    def fp32_check(self, what: str):
+        """the configurations the fp32 forward does not cover raise here -- before any launch, never a silent bf16 pass"""
+        if self.qk_norm:
+            raise NotImplementedError(f"fp32 forward ({what}): QK normalisation (use_qk_norm) is not implemented in fp32")
+        if self.D % 8 or self.H % 8 or self.D != self.heads * 64:
+            raise NotImplementedError(f"fp32 forward ({what}): needs D, H multiples of 8 and head dimension 64 (D={self.D} H={self.H} heads={self.heads})")
+
+    def _forward_fp32(self, ws: Workspace, x, segs, prefix_tokens: int, M: int, keep: bool = False):
+        """Stack.forward(train=False) in fp32 throughout: norms, the four linear maps (operands = the fp32 master parameters, products on
+        the f32-input MFMA, one fmaf chain per output element), attention with an fp32 online softmax, activations and residuals.
+        apply_rope keeps the reference's cast of q and k to the RoPE dtype (attention.py:70-89).  Plain full rows: no tail-row plan, no
+        packed captions, no stochastic depth.  keep: every block's output stays in its own buffer "f32.{i}.xout"."""
+        self.fp32_check(self.style)
+        D, H, heads = self.D, self.H, self.heads
+        xn, st = ws.get("f32.xn", (M, D), F32), ws.get("f32.st", (M, 2), F32)
+        qkv, o = ws.get("f32.qkv", (M, 3 * D), F32), ws.get("f32.o", (M, D), F32)
+        xmid, hid = ws.get("f32.xmid", (M, D), F32), ws.get("f32.hid", (M, H), F32)
+        rows = self._attn_rows(segs)
+        for i, b in enumerate(self.blocks):
+            xout = ws.get(f"f32.{i}.xout" if keep else f"f32.xout{i & 1}", (M, D), F32)
+            ops.norm_fwd_f32(x, b.n1w, b.n1b, xn, st, M, D, self.eps, self.kind)
+            ops.gemm_nt_f32(xn, b.qkv.w32, qkv, M=M, N=3 * D, K=D, bias=b.qkv.bias)
+            for r0, Bs, Ns, rp in rows:
+                q_s, o_s = qkv[r0:r0 + Bs * Ns], o[r0:r0 + Bs * Ns]
+                if rp is not None:
+                    rs, rc = rope_at(rp, i)
+                    ops.rope_qk_f32(q_s, rs, rc, Bs, Ns, heads, prefix_tokens)
+                ops.attn_fwd_f32(q_s, q_s[:, D:], q_s[:, 2 * D:], o_s, Bs, Ns, heads, Ns * 3 * D, 3 * D, Ns * D, D, ATTN_SCALE, self.causal)
+            ops.gemm_nt_f32(o, b.proj.w32, xmid, M=M, N=D, K=D, bias=b.proj.bias, gamma=b.ls1, resid=x, epi=ops.F32_RESID)
+            ops.norm_fwd_f32(xmid, b.n2w, b.n2b, xn, st, M, D, self.eps, self.kind)
+            if self.swiglu:
+                ops.gemm_nt_f32(xn, b.w1_32, hid, M=M, N=H, K=D, w2=b.w2_32, bias=b.b1_32, bias2=b.b2_32, epi=ops.F32_SWIGLU)
+            else:
+                ops.gemm_nt_f32(xn, b.fc.w32, hid, M=M, N=H, K=D, bias=b.fc.bias,
+                                epi=ops.F32_QUICK_GELU if self.quick_gelu else ops.F32_GELU)
+            ops.gemm_nt_f32(hid, b.w3.w32, xout, M=M, N=D, K=H, bias=b.w3.bias, gamma=b.ls2, resid=xmid, epi=ops.F32_RESID)
             x = xout
         return x
 
@@ -1298,17 +1345,19 @@ class TrunkEngine:
             self.ws[key] = Workspace(self.store.device)
         return self.ws[key]
 
-    def forward(self, img: torch.Tensor, train: bool, masks: Optional[torch.Tensor] = None, tag: str = "", rope_aug: Optional[bool] = None):
+    def forward(self, img: torch.Tensor, train: bool, masks: Optional[torch.Tensor] = None, tag: str = "", rope_aug: Optional[bool] = None,
+                fp32: bool = False, keep: bool = False):
         """img f32 [B,3,H,W] -> final-norm tokens xnf bf16 [B*N, D] (N = 1 + hw).  masks: uint8 [B, hw] (1 = replace the
         patch embedding by mask_token, vision_transformer.py:194-196).  `tag` separates the buffers of passes that are in
         flight at the same time with the same shape; self.ctx() returns the handle backward() needs for such passes."""
-        return self.forward_list([(img, masks)], train, tag, rope_aug=rope_aug)
+        return self.forward_list([(img, masks)], train, tag, rope_aug=rope_aug, fp32=fp32, keep=keep)
 
     def tail_rows_ok(self, train: bool) -> bool:
         """may forward_list() take a tail row plan on this pass (Stack.tail_rows_ok)"""
         return self.stack.tail_rows_ok(train)
 
-    def forward_list(self, items, train: bool, tag: str = "", rope_aug: Optional[bool] = None, tail=None):
+    def forward_list(self, items, train: bool, tag: str = "", rope_aug: Optional[bool] = None, tail=None, fp32: bool = False,
+                     keep: bool = False):
         """items = [(img f32 [B_i,3,H_i,W_i], masks_i or None)]: the reference's list forward (forward_features_list,
         vision_transformer.py:221-258): batches of different resolution go through the blocks as ONE row-concatenated
         token buffer (one GEMM / norm launch per layer for all of them, attention + RoPE per segment).  Returns xnf bf16
@@ -1330,6 +1379,10 @@ class TrunkEngine:
             p0 += B * sg.hw
         M, P = r0, p0
         ws = self.workspace((tuple((g.B, g.h, g.w) for g in segs), tag))
+        if fp32:
+            if train or tail is not None:
+                raise RuntimeError("TrunkEngine: the fp32 forward is an inference pass (train=False, no tail row plan)")
+            return self._forward_list_fp32(ws, segs, M, keep)
         # rope_aug: None = follow `train` (RopePositionEmbedding augments when its module is in training mode); the EMA teacher's pass
         # stores nothing for a backward (train=False) but belongs to a training step: its caller passes rope_aug=True
         if self.rope_aug.active and (train if rope_aug is None else rope_aug):
@@ -1361,6 +1414,43 @@ class TrunkEngine:
             ws, segs, M, xl, xnf, stf, patches, self.stack.last_saved, x0, stack_segs
         self._ctx = c
         return xnf
+
+    def _forward_list_fp32(self, ws: Workspace, segs, M: int, keep: bool):
+        """forward_list(train=False) in fp32 (Stack._forward_fp32): returns the final-norm tokens xnf f32 [M, D]; the ctx carries them as
+        xnf32 and no bf16 xnf.  The patch-embed product runs over the token rows (the cls rows multiply zeros and are overwritten by
+        assemble_tokens), in the image's own fp32 pixels."""
+        st, D = self.store, self.D
+        if D % 8:
+            raise NotImplementedError(f"fp32 forward (trunk): vision_embed_dim must be a multiple of 8 (got {D})")
+        self.stack.fp32_check("trunk")
+        patches = ws.get("f32.patches_tok", (M, 768), F32, zero=True)
+        x0 = ws.get("f32.x0", (M, D), F32)
+        for g in segs:
+            pt, xs = patches[g.row0:g.row0 + g.B * g.N], x0[g.row0:g.row0 + g.B * g.N]
+            ops.im2col16_rows_f32(g.img, pt, g.B, g.h * 16, g.w * 16, 1)
+            ops.gemm_nt_f32(pt, self.pe.w32, xs, M=g.B * g.N, N=D, K=768, bias=self.pe.bias)
+            ops.assemble_tokens(xs, st.p(self.prefix + "cls_token"), st.p(self.prefix + "mask_token"), g.masks, g.B, g.N, D)
+        stack_segs = [(g.B, g.N, g.rope) for g in segs]
+        xl = self.stack.forward(ws, x0, stack_segs, 1, False, fp32=True, keep=keep)
+        xnf = ws.get("f32.xnf", (M, D), F32)
+        stf = ws.get("f32.stf", (M, 2), F32)
+        ops.norm_fwd_f32(xl, st.p(self.prefix + "norm.weight"), st.p(self.prefix + "norm.bias") if self.kind == ops.NORM_LN else None, xnf, stf,
+                         M, D, self.eps, self.kind)
+        c = TrunkCtx()
+        c.Mc = c.M = M
+        c.ws, c.segs, c.xl, c.xnf, c.xnf32, c.stf, c.stack_segs = ws, segs, xl, None, xnf, stf, stack_segs
+        self._ctx = c
+        return xnf
+
+    def latents_fp32(self, seg: int = 0) -> torch.Tensor:
+        """bottleneck of the last fp32 forward on the patch rows of item `seg` -> f32 [B, hw, 64] (a view: the product runs over all token
+        rows of the item, the cls rows are dropped)"""
+        c = self._ctx
+        g = c.segs[seg]
+        R = g.B * g.N
+        lat = c.ws.get("f32.lat", (R, self.bott_dim), F32)
+        ops.gemm_nt_f32(c.xnf32[g.row0:g.row0 + R], self.bott.w32, lat, M=R, N=self.bott_dim, K=self.D)
+        return lat.view(g.B, g.N, self.bott_dim)[:, 1:]
 
     def ctx(self):
         return self._ctx
@@ -1501,11 +1591,27 @@ class DecoderEngine:
             self.ws[key] = Workspace(self.store.device)
         return self.ws[key]
 
-    def forward(self, lat: torch.Tensor, B: int, h: int, w: int, train: bool) -> torch.Tensor:
-        """lat bf16 [B*hw, 64] token-major -> t bf16 [B*hw, 768] (pre-PixelShuffle, token-major)."""
+    def forward(self, lat: torch.Tensor, B: int, h: int, w: int, train: bool, fp32: bool = False) -> torch.Tensor:
+        """lat bf16 [B*hw, 64] token-major -> t bf16 [B*hw, 768] (pre-PixelShuffle, token-major).  fp32 (inference only): lat and t f32,
+        every step between them in fp32 (Stack._forward_fp32)."""
         st = self.store
         M, D = B * h * w, self.D
         ws = self.workspace(B, h, w)
+        if fp32:
+            if train:
+                raise RuntimeError("DecoderEngine: the fp32 forward is an inference pass (train=False)")
+            if D % 8 or self.cin % 8:
+                raise NotImplementedError(f"fp32 forward (decoder): widths must be multiples of 8 (D={D}, latent channels={self.cin})")
+            self.stack.fp32_check("decoder")
+            x0 = ws.get("f32.x0", (M, D), F32)
+            ops.gemm_nt_f32(lat, self.pin.w32, x0, M=M, N=D, K=self.cin, bias=self.pin.bias)
+            xl = self.stack.forward(ws, x0, [(B, h * w, rope_tables(self.periods, h, w, st.device))], 0, False, fp32=True)
+            xnf = ws.get("f32.xnf", (M, D), F32)
+            ops.norm_fwd_f32(xl, st.p("pixel_decoder.norm.weight"), st.p("pixel_decoder.norm.bias") if self.kind == ops.NORM_LN else None,
+                             xnf, ws.get("f32.stf", (M, 2), F32), M, D, self.eps, self.kind)
+            t = ws.get("f32.t", (M, 768), F32)
+            ops.gemm_nt_f32(xnf, self.pout.w32, t, M=M, N=768, K=D, bias=self.pout.bias)
+            return t
         x0 = ws.get("x0", (M, D), F32)
         ops.gemm_nt(lat, self.pin.w, x0, M=M, N=D, K=self.cin, bias=self.pin.bias, epi=EPI_F32)
         rope = rope_tables(self.periods, h, w, st.device)

@@ -82,6 +82,38 @@ def _rope_periods(head_dim: int = 64, base: float = 100.0) -> torch.Tensor:
     return base ** (2 * torch.arange(head_dim // 4, dtype=dt) / (head_dim // 2))
 
 
+# ---- fp32 inference forward: which towers can be switched, and which tower every head follows
+FP32_TOWERS = ("trunk", "decoder", "text")
+FP32_HEAD_TOWER = {"feature_bottleneck": "trunk", "visual_proj": "trunk", "pooled_patch_mean": "trunk",
+                   "text_projection": "text", "text_pool": "text"}
+
+
+def fp32_towers(towers, has_decoder: bool = True, has_text: bool = True) -> Tuple[str, ...]:
+    """validated selection of enable_fp32_forward, in the order of FP32_TOWERS: a non-empty set of known tower names, each of which the
+    model was built with"""
+    if isinstance(towers, str):
+        towers = (towers,)
+    sel = list(towers)
+    unknown = [t for t in sel if t not in FP32_TOWERS]
+    if unknown:
+        raise ValueError(f"enable_fp32_forward: unknown tower {unknown[0]!r} (known: {', '.join(FP32_TOWERS)})")
+    if not sel:
+        raise ValueError("enable_fp32_forward: select at least one tower (disable_fp32_forward switches the fp32 forward off)")
+    if "decoder" in sel and not has_decoder:
+        raise ValueError("enable_fp32_forward: the model was built without a pixel decoder (train_reconstruction=False)")
+    if "text" in sel and not has_text:
+        raise ValueError("enable_fp32_forward: the model was built without a text tower (train_clip=False)")
+    return tuple(t for t in FP32_TOWERS if t in sel)
+
+
+def fp32_head(head: str, towers) -> bool:
+    """does `head` run in fp32 under the selection `towers`?  Heads follow their tower (FP32_HEAD_TOWER); the logit matrix of
+    get_clip_logits ("logits") is an fp32 product of fp32 features when both the trunk and the text tower are selected."""
+    if head == "logits":
+        return "trunk" in towers and "text" in towers
+    return FP32_HEAD_TOWER[head] in towers
+
+
 class VTPModel(nn.Module):
     config_class = VTPConfig
 
@@ -283,6 +315,9 @@ class VTPModel(nn.Module):
         """Switch the inference path (eval / no_grad: get_reconstruction_latents, get_latents_decoded_images, features) to fp8
         MFMA GEMMs: one bf16 encode -> decode pass over `calibration_images` records the per-tensor activation maxima, the
         weights are quantised from their own maxima.  Training and the autograd path are untouched (bf16)."""
+        both = set(self.fp32_forward) & {"trunk", "decoder"}
+        if both:
+            raise ValueError(f"enable_fp8_forward: the fp32 forward is enabled on {sorted(both)}; disable_fp32_forward() first")
         self._fp8_on = False
         for stack in self._fp8_stacks():
             stack.fp8_begin_calibration()
@@ -298,6 +333,35 @@ class VTPModel(nn.Module):
         self._fp8_on = False
         for stack in self._fp8_stacks():
             stack.fp8 = None
+        return self
+
+    # ---- fp32 inference forward of the trunk, the pixel decoder and the text tower (engine.Stack._forward_fp32)
+    @property
+    def fp32_forward(self) -> Tuple[str, ...]:
+        """the towers whose inference forward runs in fp32, () by default"""
+        return getattr(self, "_fp32", ())
+
+    def enable_fp32_forward(self, towers=FP32_TOWERS):
+        """Switch the inference path (eval / no_grad: latents, decoded images, features, CLIP features and logits) of the given towers to
+        fp32 -- the reference with fp32 weights and no autocast: fp32 master parameters as operands, every product on the f32-input
+        MFMA, fp32 norms, softmax, activations and residuals; apply_rope keeps its cast to the RoPE dtype.  Heads follow their tower
+        (FP32_HEAD_TOWER).  Training, autograd, VTPTrainer and the SSL forward stay bf16.  ("decoder",) is the recipe of
+        tools/test_reconstruction_hf.py (bf16 encoder, fp32 decoder).  What the fp32 path does not cover raises here."""
+        sel = fp32_towers(towers, self.pixel_decoder is not None, self.visual_proj is not None)
+        if getattr(self, "_fp8_on", False) and set(sel) & {"trunk", "decoder"}:
+            raise ValueError("enable_fp32_forward: the fp8 forward is enabled on the trunk and the decoder; disable_fp8_forward() first")
+        self._engine()
+        if "trunk" in sel:
+            self._trunk.stack.fp32_check("trunk")
+        if "decoder" in sel:
+            self._decoder.stack.fp32_check("decoder")
+        if "text" in sel:
+            self._text.enable_fp32()
+        self._fp32 = sel
+        return self
+
+    def disable_fp32_forward(self):
+        self._fp32 = ()
         return self
 
     def zero_grad(self, set_to_none: bool = False):
@@ -372,6 +436,9 @@ class VTPModel(nn.Module):
         self._fresh()
         img = self._img(image)
         B, _, H, W = img.shape
+        if "trunk" in self.fp32_forward:
+            self._trunk.forward(img, train=False, fp32=True)
+            return self._trunk.latents_fp32().transpose(1, 2).reshape(B, -1, H // 16, W // 16).clone()
         self._trunk.forward(img, train=False)
         lat = self._trunk.latents(out_f32=True)  # [B*hw, 64]
         return lat.view(B, (H // 16) * (W // 16), -1).transpose(1, 2).reshape(B, -1, H // 16, W // 16).clone()
@@ -388,6 +455,14 @@ class VTPModel(nn.Module):
     def _decode_nograd(self, latents: torch.Tensor) -> torch.Tensor:
         self._fresh()
         B, C, h, w = latents.shape
+        if "decoder" in self.fp32_forward:
+            if not latents.is_cuda or C != self._decoder.cin:
+                raise ValueError(f"latents must be a [B, {self._decoder.cin}, h, w] tensor on the MI355X, got {tuple(latents.shape)} on {latents.device}")
+            lat = latents.detach().reshape(B, C, h * w).transpose(1, 2).to(torch.float32).contiguous().view(B * h * w, C)
+            t = self._decoder.forward(lat, B, h, w, train=False, fp32=True)
+            img = torch.empty(B, 3, h * 16, w * 16, dtype=torch.float32, device=lat.device)
+            ops.pixel_shuffle16_f32(t, img, B, h, w)
+            return img
         lat = latents.detach().reshape(B, C, h * w).transpose(1, 2).to(torch.bfloat16).contiguous().view(B * h * w, C)
         t = self._decoder.forward(lat, B, h, w, train=False)
         img = torch.empty(B, 3, h * 16, w * 16, dtype=torch.float32, device=lat.device)
@@ -401,6 +476,16 @@ class VTPModel(nn.Module):
         img = self._img(image)
         B, _, H, W = img.shape
         hw = (H // 16) * (W // 16)
+        if "trunk" in self.fp32_forward:
+            xnf = self._trunk.forward(img, train=False, fp32=True)
+            tok = xnf.view(B, hw + 1, -1)
+            cls_t, patch_t = tok[:, 0].clone(), tok[:, 1:].clone()
+            if use_bottleneck and self._trunk.bott is not None:
+                wb = self.trunk.feature_bottleneck.weight
+                patch_t = self._trunk.latents_fp32().clone()
+                cls_t = torch.empty(B, wb.shape[0], dtype=torch.float32, device=img.device)
+                ops.gemm_nt_f32(xnf, self._trunk.bott.w32, cls_t, M=B, N=wb.shape[0], K=wb.shape[1], lda=(hw + 1) * wb.shape[1])
+            return {"cls_token": cls_t, "patch_tokens": patch_t}
         xnf = self._trunk.forward(img, train=False).view(B, hw + 1, -1).float()
         cls_t, patch_t = xnf[:, 0], xnf[:, 1:]
         if use_bottleneck and self._trunk.bott is not None:
@@ -430,14 +515,26 @@ class VTPModel(nn.Module):
         take = sorted(set(i for i in want if 0 <= i < depth))
         if not take or len(take) != len(want):
             raise AssertionError(f"only {len(take)} / {len(want)} blocks found")
-        tr.forward(img, train=True, tag="intermediate")  # train=True keeps every block's output buffer
+        fp32 = "trunk" in self.fp32_forward
+        if fp32:
+            tr.forward(img, train=False, tag="intermediate", fp32=True, keep=True)
+        else:
+            tr.forward(img, train=True, tag="intermediate")  # train=True keeps every block's output buffer
         c = tr.ctx()
         M, D = c.M, tr.D
         st = self._store
         outs = []
         for i in take:
-            x = c.ws.get(f"{i}.xout", (M, D), torch.float32)
-            if norm:
+            x = c.ws.get(f"f32.{i}.xout" if fp32 else f"{i}.xout", (M, D), torch.float32)
+            if fp32:  # the final norm in fp32 too; a copy: the workspace buffers are reused by the next call
+                if norm:
+                    y = torch.empty(M, D, dtype=torch.float32, device=x.device)
+                    ops.norm_fwd_f32(x, st.p(tr.prefix + "norm.weight"), st.p(tr.prefix + "norm.bias") if tr.kind == ops.NORM_LN else None,
+                                     y, c.ws.get("f32.inter.st", (M, 2), torch.float32), M, D, tr.eps, tr.kind)
+                    x = y
+                else:
+                    x = x.clone()
+            elif norm:
                 y = c.ws.get("inter.y", (M, D), torch.bfloat16)
                 stats = c.ws.get("inter.st", (M, 2), torch.float32)
                 ops.norm_fwd(x, st.p(tr.prefix + "norm.weight"), st.p(tr.prefix + "norm.bias") if tr.kind == ops.NORM_LN else None,
@@ -456,6 +553,8 @@ class VTPModel(nn.Module):
             raise RuntimeError("CLIP not enabled. Set train_clip=True in config.")
         c = self.config
         general = c.vision_clip_feat != "cls" or not c.vision_bottleneck_ae_only
+        if "trunk" in self.fp32_forward and not ag.grad_mode(self):
+            general = False  # the fp32 heads of every variant are ClipHead.image_features_fp32
         if ag.grad_mode(self) or general:
             # tokens from the trunk kernels; the [B, D] pooling / projection / normalisation heads on kernels too (autograd.HeadLinear /
             # SumTokens / L2Normalize: the arithmetic of modeling_vtp.py:262-276, bf16 MFMA with fp32 accumulation like the
@@ -487,9 +586,11 @@ class VTPModel(nn.Module):
         img = self._img(image)
         B, _, H, W = img.shape
         N = (H // 16) * (W // 16) + 1
-        xnf = self._trunk.forward(img, train=False)  # [B*N, D] bf16; cls rows are b*N
-        D = c.vision_embed_dim
-        f = self._clip.image_features(xnf, B, N)
+        if "trunk" in self.fp32_forward:
+            f = self._clip.image_features_fp32(self._trunk.forward(img, train=False, fp32=True), B, N)
+        else:
+            xnf = self._trunk.forward(img, train=False)  # [B*N, D] bf16; cls rows are b*N
+            f = self._clip.image_features(xnf, B, N)
         if normalize:
             f, _ = self._clip.normalize(f, "img")
         return f.clone()
@@ -509,7 +610,7 @@ class VTPModel(nn.Module):
     def _clip_text_nograd(self, text: torch.Tensor, normalize: bool = True) -> torch.Tensor:
         self._fresh()
         ids = self._ids(text)
-        f = self._text.forward(ids, train=False)
+        f = self._text.forward(ids, train=False, fp32="text" in self.fp32_forward)
         if normalize:
             f, _ = self._clip.normalize(f, "txt")
         f = f.clone()

@@ -983,3 +983,68 @@ def fid_accum(feats, sum_, outer):
     _need(outer, "outer", torch.float64, (D, D))
     _need_gpu(feats=feats, sum_=sum_, outer=outer)
     _lib.check(_lib_().vtp_fid_accum(_p(feats), feats.stride(0), _p(sum_), _p(outer), n, D, _s()), "vtp_fid_accum")
+
+
+# ---- fp32 inference forward (fp32.hip): every tensor f32, products on the f32-input MFMA, one fmaf chain per output element
+F32_PLAIN, F32_RESID, F32_SWIGLU, F32_GELU, F32_QUICK_GELU = 0, 1, 2, 3, 4
+
+
+def _need_f32(**tensors):
+    for name, t in tensors.items():
+        if t is not None and (t.dtype != torch.float32 or not t.is_cuda):
+            raise ValueError(f"{name} must be a float32 tensor on the device, got {t.dtype} on {t.device}")
+
+
+def gemm_nt_f32(a, w, c, *, M=None, N=None, K=None, lda=None, ldw=None, ldc=None, w2=None, bias=None, bias2=None, gamma=None,
+                resid=None, ldr=None, epi=F32_PLAIN):
+    """c[M,N] = epi(a[M,K] @ w[N,K]^T) in exact fp32 (vtp_gemm_nt_f32): a, w, c f32, K-contiguous rows with leading dimensions.
+    epi F32_RESID: resid + gamma * (. + bias); F32_SWIGLU: silu(a w^T + bias) * (a w2^T + bias2); F32_GELU / F32_QUICK_GELU."""
+    _need_f32(a=a, w=w, c=c, w2=w2, bias=bias, bias2=bias2, gamma=gamma, resid=resid)
+    M = a.shape[0] if M is None else M
+    K = a.shape[1] if K is None else K
+    N = w.shape[0] if N is None else N
+    lda = a.stride(0) if lda is None else lda
+    ldw = w.stride(0) if ldw is None else ldw
+    ldc = c.stride(0) if ldc is None else ldc
+    if resid is not None and ldr is None:
+        ldr = resid.stride(0)
+    _lib.check(_lib_().vtp_gemm_nt_f32(_p(a), lda, _p(w), ldw, _p(w2), _p(c), ldc, _p(bias), _p(bias2), _p(gamma), _p(resid), ldr or 0,
+                                       M, N, K, epi, _s()), "vtp_gemm_nt_f32")
+
+
+def attn_fwd_f32(q, k, v, o, B, N, heads, sb, sn, sbo, sno, scale, causal=False):
+    """o = softmax(scale q k^T) v, head dimension 64, all f32 (vtp_attn_fwd_f32); strides in elements as attn_fwd"""
+    _need_f32(q=q, k=k, v=v, o=o)
+    _lib.check(_lib_().vtp_attn_fwd_f32(_p(q), _p(k), _p(v), _p(o), B, N, heads, sb, sn, sbo, sno, scale, int(causal), _s()),
+               "vtp_attn_fwd_f32")
+
+
+def norm_fwd_f32(x, w, b, y, stats, M, D, eps, kind):
+    """norm_fwd with the un-rounded f32 output y"""
+    _need_f32(x=x, w=w, b=b, y=y, stats=stats)
+    _lib.check(_lib_().vtp_norm_fwd_f32(_p(x), _p(w), _p(b), _p(y), _p(stats), M, D, eps, kind, _s()), "vtp_norm_fwd_f32")
+
+
+def rope_qk_f32(qkv, sin, cos, B, N, heads, prefix):
+    """apply_rope in place on the q and k thirds of qkv f32 [B*N, 3*heads*64]: rounded to bf16, rotated as rope_qk, widened back"""
+    _need_f32(qkv=qkv)
+    assert sin.dtype == torch.bfloat16 and cos.dtype == torch.bfloat16
+    _lib.check(_lib_().vtp_rope_qk_f32(_p(qkv), _p(sin), _p(cos), B, N, heads, prefix, _s()), "vtp_rope_qk_f32")
+
+
+def im2col16_rows_f32(img, rows, B, H, W, prefix=1):
+    _need_f32(img=img, rows=rows)
+    _lib.check(_lib_().vtp_im2col16_rows_f32(_p(img), _p(rows), B, H, W, prefix, _s()), "vtp_im2col16_rows_f32")
+
+
+def pixel_shuffle16_f32(t, img, B, h, w):
+    _need_f32(t=t, img=img)
+    _lib.check(_lib_().vtp_pixel_shuffle16_f32(_p(t), _p(img), B, h, w, _s()), "vtp_pixel_shuffle16_f32")
+
+
+def pool_patch_rows_f32(x, out, B, N, D, scale=None):
+    """pool_patch_rows on f32 token rows"""
+    _need_f32(x=x, out=out)
+    assert x.is_contiguous() and x.numel() >= B * N * D and out.is_contiguous() and out.numel() >= B * D
+    s = 1.0 / (N - 1) if scale is None else float(scale)
+    _lib.check(_lib_().vtp_pool_patch_rows_f32(_p(x), _p(out), B, N, D, s, _s()), "vtp_pool_patch_rows_f32")

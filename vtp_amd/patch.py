@@ -42,6 +42,20 @@ def patch_model(ref_model, device="cuda"):
             torch.nn.Module.train(ref_model, mode)
         return ref_model
 
+    # the fp32 inference forward: same switch, same meaning; `fp32_forward` on the patched object follows the backing model's
+    def enable_fp32_forward(*a, **kw):
+        ours.enable_fp32_forward(*a, **kw)
+        object.__setattr__(ref_model, "fp32_forward", ours.fp32_forward)
+        return ref_model
+
+    def disable_fp32_forward():
+        ours.disable_fp32_forward()
+        object.__setattr__(ref_model, "fp32_forward", ours.fp32_forward)
+        return ref_model
+
+    object.__setattr__(ref_model, "enable_fp32_forward", enable_fp32_forward)
+    object.__setattr__(ref_model, "disable_fp32_forward", disable_fp32_forward)
+    object.__setattr__(ref_model, "fp32_forward", ours.fp32_forward)
     object.__setattr__(ref_model, "train", train)
     object.__setattr__(ref_model, "eval", lambda: train(False))
     object.__setattr__(ref_model, "_vtp_amd", ours)

@@ -68,6 +68,15 @@ def _attn_bwd(qkv, o, d_o, lse, delta, dqkv, B, N, heads, scale, causal):
                  N * D, D, scale, causal)
 
 
+def _gemm_nt_f32(a, w, c, w2, bias, bias2, gamma, resid, M, N, K, epilogue):
+    ops.gemm_nt_f32(a, w, c, M=M, N=N, K=K, w2=w2, bias=bias, bias2=bias2, gamma=gamma, resid=resid, epi=epilogue)
+
+
+def _attn_fwd_f32(qkv, o, B, N, heads, scale, causal):
+    D = heads * 64
+    ops.attn_fwd_f32(qkv, qkv[:, D:], qkv[:, 2 * D:], o, B, N, heads, N * 3 * D, 3 * D, N * D, D, scale, causal)
+
+
 def _swiglu_bwd(dh, x12, dx12, M, H):
     ops.swiglu_bwd(dh, x12, dx12, M, H)
 
@@ -123,6 +132,9 @@ _define("rope_qk(Tensor(q!) qkv, Tensor sin, Tensor cos, int B, int N, int heads
 _define("attn_fwd(Tensor qkv, Tensor(o!) o, Tensor(l!) lse, int B, int N, int heads, float scale, bool causal) -> ()", _attn_fwd)
 _define("attn_bwd(Tensor qkv, Tensor o, Tensor d_o, Tensor lse, Tensor(d!) delta, Tensor(g!) dqkv, int B, int N, int heads, float scale, "
         "bool causal) -> ()", _attn_bwd)
+_define("gemm_nt_f32(Tensor a, Tensor w, Tensor(c!) c, Tensor? w2, Tensor? bias, Tensor? bias2, Tensor? gamma, Tensor? resid, int M, int N, "
+        "int K, int epilogue) -> ()", _gemm_nt_f32)
+_define("attn_fwd_f32(Tensor qkv, Tensor(o!) o, int B, int N, int heads, float scale, bool causal) -> ()", _attn_fwd_f32)
 _define("swiglu_bwd(Tensor dh, Tensor x12, Tensor(d!) dx12, int M, int H) -> ()", _swiglu_bwd)
 _define("im2col16(Tensor img, Tensor(p!) patches) -> ()", _im2col16)
 _define("pixel_shuffle16(Tensor t, Tensor(i!) img, int B, int h, int w) -> ()", _pixel_shuffle16)
