@@ -614,6 +614,10 @@ int vtp_preprocess(const void* src_u8, long src_len, void* scratch, long scratch
  *   padding (ph, pw), relu != 0: max(., 0).  An implicit GEMM on v_mfma_f32_32x32x2_f32: every output element is ONE fmaf chain
  *   that starts at the bias and runs over k in the order (ky, kx, ci).  x and w 16-byte aligned when Cin % 4 == 0 (16-byte loads
  *   along Cin); any other Cin (the first layer's 3) takes scalar loads.
+ * vtp_conv2d_f32_blocked: the same convolution with the sum over k taken in blocks of 32: every 32 consecutive k form a chain that
+ *   starts at 0, and the block sums are added to the accumulator (which starts at the bias) in k order.  Rounding errors then grow
+ *   with K / 32 + 32 rather than K (the fp32 LPIPS: K up to 4608); an output is still a fixed sequence of operations on its own
+ *   row of x and of w, so it does not depend on the batch and repeats bit for bit.
  * vtp_pool3x3_f32: 3 x 3 pooling of x f32 NHWC [B, H, W, C] into the channels [c0, c0 + C) of y [B, Ho, Wo, Ctot].  stride 1 pads by
  *   1, stride 2 by 0.  mode 0 max (a NaN tap gives NaN, as F.max_pool2d), 1 average / 9 (the padding counts), 2 average over the taps inside.  C, c0, Ctot % 4 == 0.
  * vtp_global_avgpool_f32: x f32 [B, HW, C] -> y f32 [B, C], the pixels summed in order.
@@ -625,6 +629,8 @@ int vtp_preprocess(const void* src_u8, long src_len, void* scratch, long scratch
  *   over calls leaves the same bits. */
 int vtp_conv2d_f32(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin, int Cout, int kh,
                    int kw, int stride, int ph, int pw, int relu, int c0, int Ctot, void* stream);
+int vtp_conv2d_f32_blocked(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin, int Cout, int kh,
+                           int kw, int stride, int ph, int pw, int relu, int c0, int Ctot, void* stream);
 int vtp_pool3x3_f32(const float* x, float* y, int B, int H, int W, int C, int stride, int mode, int c0, int Ctot, void* stream);
 int vtp_global_avgpool_f32(const float* x, float* y, int B, int HW, int C, void* stream);
 int vtp_resize_bilinear_nhwc(const float* x, float* y, int B, int C, int H, int W, int Ho, int Wo, float scale, float shift,
@@ -657,6 +663,26 @@ int vtp_rope_qk_f32(float* qkv, const void* sin, const void* cos, int B, int N, 
 int vtp_im2col16_rows_f32(const float* img, float* rows, int B, int H, int W, int prefix, void* stream);
 int vtp_pixel_shuffle16_f32(const float* t, float* img, int B, int h, int w, void* stream);
 int vtp_pool_patch_rows_f32(const float* x, float* out, int B, int N, int D, float scale, void* stream);
+
+/* ---- LPIPS in exact fp32 for evaluation (lpips_f32.hip): what vtp/utils/lpips.py computes on fp32 tensors outside autocast (the
+ * reconstruction tool's LPIPS_VTP).  Activations are f32 NHWC without borders; the 13 convolutions are vtp_conv2d_f32_blocked.  No float
+ * atomics, nothing depends on the grid or the batch: a pair's value repeats bit for bit whatever it is batched with.
+ * vtp_lpips_scale_nhwc_f32: ScalingLayer (lpips.py:103-114) and the repack: x f32 NCHW [B, 3, H, W] -> y f32 NHWC [B, H, W, Cout],
+ *   y_c = (x_c - shift_c) / scale_c, one fp32 subtraction and one fp32 division.  Cout = 3, or 4: channel 3 is zero (16-byte stores,
+ *   and the first convolution takes 16-byte loads on weights zero-padded to Cin = 4).  shift / scale: host float[3].
+ * vtp_maxpool2_f32: nn.MaxPool2d(2, 2), x f32 NHWC [B, H, W, C] -> y [B, H / 2, W / 2, C]; H, W even, C % 4 == 0, 16-byte aligned.
+ * vtp_lpips_head_f32: one tap.  f f32 [2 n, HW, C]: the ReLU features of image b and of image n + b; w f32 [C] (NetLinLayer).  Per
+ *   pixel in fp32: a = f0 / (sqrt(sum_c f0^2) + 1e-10), b likewise from f1, s = sum_c w_c (a_c - b_c)^2 (an all-zero pixel gives 0).
+ *   part f64 [n, ceil(HW / 256)]: part[b, j] = the sum of s over the pixels [256 j, 256 j + 256) of pair b, in a fixed order.
+ *   C in {64, 128, 256, 512}.
+ * vtp_lpips_finalize_f32: part f64 = the five taps' partial sums back to back, tap k as [n, ceil(HW_k / 256)] with HW_k =
+ *   (H >> k) (W >> k); val[b] = (((r_0 + r_1) + r_2) + r_3) + r_4 in fp32, r_k = float(sum_j part_k[b, j] / HW_k), the segments
+ *   summed in fp64 in a fixed order (lpips.py:90-100: spatial_average, val = res[0]; val += res[l]). */
+int vtp_lpips_scale_nhwc_f32(const float* x, float* y, int B, int H, int W, int Cout, const float* shift, const float* scale,
+                             void* stream);
+int vtp_maxpool2_f32(const float* x, float* y, int B, int H, int W, int C, void* stream);
+int vtp_lpips_head_f32(const float* f, const float* w, double* part, int n, int HW, int C, void* stream);
+int vtp_lpips_finalize_f32(const double* part, float* val, int n, int H, int W, void* stream);
 
 #ifdef __cplusplus
 }

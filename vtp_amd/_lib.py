@@ -145,6 +145,7 @@ SIGNATURES = {
     "vtp_preprocess": [_P, _L, _P, _L, _P, _P, _P, _I, _L, _I, _I, _P, _P, _P, _P, _P],
     # x w bias y B H W Cin Cout kh kw stride ph pw relu c0 Ctot stream
     "vtp_conv2d_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "vtp_conv2d_f32_blocked": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "vtp_pool3x3_f32": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],  # x y B H W C stride mode c0 Ctot stream
     "vtp_global_avgpool_f32": [_P, _P, _I, _I, _I, _P],  # x y B HW C stream
     "vtp_resize_bilinear_nhwc": [_P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _P],  # x y B C H W Ho Wo scale shift stream
@@ -157,6 +158,11 @@ SIGNATURES = {
     "vtp_im2col16_rows_f32": [_P, _P, _I, _I, _I, _I, _P],
     "vtp_pixel_shuffle16_f32": [_P, _P, _I, _I, _I, _P],
     "vtp_pool_patch_rows_f32": [_P, _P, _I, _I, _I, _F, _P],
+    # LPIPS in fp32 (lpips_f32.hip)
+    "vtp_lpips_scale_nhwc_f32": [_P, _P, _I, _I, _I, _I, _P, _P, _P],  # x y B H W Cout shift3 scale3 stream
+    "vtp_maxpool2_f32": [_P, _P, _I, _I, _I, _I, _P],  # x y B H W C stream
+    "vtp_lpips_head_f32": [_P, _P, _P, _I, _I, _I, _P],  # f w part n HW C stream
+    "vtp_lpips_finalize_f32": [_P, _P, _I, _I, _I, _P],  # part val n H W stream
 }
 
 _lib = None

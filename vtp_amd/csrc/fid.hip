@@ -90,7 +90,11 @@ __device__ __forceinline__ void conv_put(float* row, int kq, f32x4 v) {
   *(f32x2*)(p + 4) = f32x2{v[1], v[3]};
 }
 
-template <int NT, bool VEC>
+// BLK: the K sum in blocks.  Each chunk of 32 k is a chain of its own that starts at 0, and the chunk sums are added to the
+// accumulator (which starts at the bias) in k order: a rounding error is then relative to a 32-term partial sum or to one of K / 32
+// running sums, not to one of K -- what the long reductions of VGG16 (K = 576 .. 4608) need to stay as close to fp64 as torch's own
+// fp32 convolutions do.  An output element is still a fixed sequence of operations on its own inputs.
+template <int NT, bool VEC, bool BLK>
 __global__ __launch_bounds__(CV_THREADS) void conv2d_f32_kernel(const ConvArgs a) {
   constexpr int BN = 32 * NT, XQ = CV_BM / 32, WQ = BN / 32;
   __shared__ __attribute__((aligned(16))) float lds[(CV_BM + BN) * CV_LD];
@@ -152,14 +156,34 @@ __global__ __launch_bounds__(CV_THREADS) void conv2d_f32_kernel(const ConvArgs a
     __syncthreads();
     if (k0 + CV_BK < a.K) load_chunk(k0 + CV_BK);
     const float* xrow = xs + (32 * wv + r) * CV_LD + 4 * half;
+    if constexpr (BLK) {
+      f32x16 part[NT];
 #pragma unroll
-    for (int g = 0; g < CV_BK / 8; ++g) {
-      const f32x4 av = *(const f32x4*)(xrow + 8 * g);
+      for (int t = 0; t < NT; ++t)
 #pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        const f32x4 bv = *(const f32x4*)(wsm + (32 * t + r) * CV_LD + 4 * half + 8 * g);
+        for (int i = 0; i < 16; ++i) part[t][i] = 0.f;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) acc[t] = mfma32(av[e], bv[e], acc[t]);
+      for (int g = 0; g < CV_BK / 8; ++g) {
+        const f32x4 av = *(const f32x4*)(xrow + 8 * g);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          const f32x4 bv = *(const f32x4*)(wsm + (32 * t + r) * CV_LD + 4 * half + 8 * g);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) part[t] = mfma32(av[e], bv[e], part[t]);
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < NT; ++t) acc[t] += part[t];
+    } else {
+#pragma unroll
+      for (int g = 0; g < CV_BK / 8; ++g) {
+        const f32x4 av = *(const f32x4*)(xrow + 8 * g);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          const f32x4 bv = *(const f32x4*)(wsm + (32 * t + r) * CV_LD + 4 * half + 8 * g);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) acc[t] = mfma32(av[e], bv[e], acc[t]);
+        }
       }
     }
   }
@@ -321,8 +345,8 @@ using namespace vtp;
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 static const long INT_LIMIT = 2147483647L;
 
-extern "C" int vtp_conv2d_f32(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin, int Cout, int kh,
-                              int kw, int stride, int ph, int pw, int relu, int c0, int Ctot, void* stream) {
+static int conv2d_f32(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin, int Cout, int kh, int kw,
+                      int stride, int ph, int pw, int relu, int c0, int Ctot, bool blocked, void* stream) {
   VTP_REQUIRE(x && w && y, "vtp_conv2d_f32: null pointer (x, w, y)");
   VTP_REQUIRE(B >= 1 && H >= 1 && W >= 1 && Cin >= 1 && Cout >= 1, "vtp_conv2d_f32: bad shape (B, H, W, Cin, Cout >= 1)");
   VTP_REQUIRE((kh == 1 || kh == 3 || kh == 5 || kh == 7) && (kw == 1 || kw == 3 || kw == 5 || kw == 7),
@@ -343,11 +367,27 @@ extern "C" int vtp_conv2d_f32(const float* x, const float* w, const float* bias,
   const bool two = nt32 % 2 == 0;  // an odd count of 32-column tiles runs one tile per wave: no half-empty workgroup column
   const dim3 grid(cdiv(M, CV_BM), two ? nt32 / 2 : nt32);
   hipStream_t s = (hipStream_t)stream;
-  if (two && vec) hipLaunchKernelGGL((conv2d_f32_kernel<2, true>), grid, dim3(CV_THREADS), 0, s, a);
-  else if (two) hipLaunchKernelGGL((conv2d_f32_kernel<2, false>), grid, dim3(CV_THREADS), 0, s, a);
-  else if (vec) hipLaunchKernelGGL((conv2d_f32_kernel<1, true>), grid, dim3(CV_THREADS), 0, s, a);
-  else hipLaunchKernelGGL((conv2d_f32_kernel<1, false>), grid, dim3(CV_THREADS), 0, s, a);
+#define VTP_CONV(NT, VEC)                                                                                                \
+  do {                                                                                                                    \
+    if (blocked) hipLaunchKernelGGL((conv2d_f32_kernel<NT, VEC, true>), grid, dim3(CV_THREADS), 0, s, a);                  \
+    else hipLaunchKernelGGL((conv2d_f32_kernel<NT, VEC, false>), grid, dim3(CV_THREADS), 0, s, a);                         \
+  } while (0)
+  if (two && vec) VTP_CONV(2, true);
+  else if (two) VTP_CONV(2, false);
+  else if (vec) VTP_CONV(1, true);
+  else VTP_CONV(1, false);
+#undef VTP_CONV
   return check_launch("conv2d_f32");
+}
+
+extern "C" int vtp_conv2d_f32(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin, int Cout, int kh,
+                              int kw, int stride, int ph, int pw, int relu, int c0, int Ctot, void* stream) {
+  return conv2d_f32(x, w, bias, y, B, H, W, Cin, Cout, kh, kw, stride, ph, pw, relu, c0, Ctot, false, stream);
+}
+
+extern "C" int vtp_conv2d_f32_blocked(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin, int Cout,
+                                      int kh, int kw, int stride, int ph, int pw, int relu, int c0, int Ctot, void* stream) {
+  return conv2d_f32(x, w, bias, y, B, H, W, Cin, Cout, kh, kw, stride, ph, pw, relu, c0, Ctot, true, stream);
 }
 
 extern "C" int vtp_pool3x3_f32(const float* x, float* y, int B, int H, int W, int C, int stride, int mode, int c0, int Ctot, void* stream) {

@@ -918,9 +918,10 @@ def _need_gpu(**tensors):
             raise ValueError(f"{name} must live on the MI355X (got a CPU tensor): there is no CPU path")
 
 
-def conv2d_f32(x, w, bias, y, stride=1, pad=(0, 0), relu=True, c0=0):
+def conv2d_f32(x, w, bias, y, stride=1, pad=(0, 0), relu=True, c0=0, blocked=False):
     """exact-fp32 implicit-GEMM convolution (csrc/fid.hip): x f32 NHWC [B, H, W, Cin], w f32 [Cout, kh, kw, Cin], bias f32 [Cout] or
-    None -> the channels [c0, c0 + Cout) of y f32 [B, Ho, Wo, Ctot]; every output is one fmaf chain over (ky, kx, ci)"""
+    None -> the channels [c0, c0 + Cout) of y f32 [B, Ho, Wo, Ctot]; every output is one fmaf chain over (ky, kx, ci) -- with
+    blocked=True a chain per 32 consecutive k whose sums are added in k order (vtp_conv2d_f32_blocked: long reductions)"""
     _need(x, "x", torch.float32, dims=4)
     B, H, W, Cin = x.shape
     _need(w, "w", torch.float32, dims=4)
@@ -934,8 +935,9 @@ def conv2d_f32(x, w, bias, y, stride=1, pad=(0, 0), relu=True, c0=0):
     if tuple(y.shape[:3]) != (B, ho, wo) or c0 < 0 or c0 + Cout > y.shape[3]:
         raise ValueError(f"y must be [{B}, {ho}, {wo}, Ctot >= c0 + Cout = {c0 + Cout}], got {tuple(y.shape)}")
     _need_gpu(x=x, w=w, bias=bias, y=y)
-    _lib.check(_lib_().vtp_conv2d_f32(_p(x), _p(w), _p(bias), _p(y), B, H, W, Cin, Cout, kh, kw, stride, pad[0], pad[1], int(bool(relu)),
-                                      c0, y.shape[3], _s()), "vtp_conv2d_f32")
+    fn, name = (_lib_().vtp_conv2d_f32_blocked, "vtp_conv2d_f32_blocked") if blocked else (_lib_().vtp_conv2d_f32, "vtp_conv2d_f32")
+    _lib.check(fn(_p(x), _p(w), _p(bias), _p(y), B, H, W, Cin, Cout, kh, kw, stride, pad[0], pad[1], int(bool(relu)), c0, y.shape[3], _s()),
+               name)
 
 
 def pool3x3_f32(x, y, stride, mode, c0=0):
@@ -1048,3 +1050,60 @@ def pool_patch_rows_f32(x, out, B, N, D, scale=None):
     assert x.is_contiguous() and x.numel() >= B * N * D and out.is_contiguous() and out.numel() >= B * D
     s = 1.0 / (N - 1) if scale is None else float(scale)
     _lib.check(_lib_().vtp_pool_patch_rows_f32(_p(x), _p(out), B, N, D, s, _s()), "vtp_pool_patch_rows_f32")
+
+
+# ---- LPIPS in fp32 (lpips_f32.hip): f32 NHWC activations without borders around conv2d_f32
+LPIPS_HEAD_SEG = 256  # pixels per partial sum of lpips_head_f32
+
+
+def lpips_head_segments(HW):
+    return (HW + LPIPS_HEAD_SEG - 1) // LPIPS_HEAD_SEG
+
+
+def lpips_scale_nhwc_f32(x, y, shift, scale):
+    """ScalingLayer + repack: x f32 NCHW [B, 3, H, W] -> y f32 NHWC [B, H, W, 3 or 4] = (x - shift_c) / scale_c (one subtraction, one
+    division: torch's bits); a fourth channel is written as zeros"""
+    _need(x, "x", torch.float32, dims=4)
+    B, C, H, W = x.shape
+    if C != 3:
+        raise ValueError(f"x must be [B, 3, H, W], got {tuple(x.shape)}")
+    _need(y, "y", torch.float32, dims=4)
+    if tuple(y.shape[:3]) != (B, H, W) or y.shape[3] not in (3, 4):
+        raise ValueError(f"y must be [{B}, {H}, {W}, 3 or 4], got {tuple(y.shape)}")
+    _need_gpu(x=x, y=y)
+    _lib.check(_lib_().vtp_lpips_scale_nhwc_f32(_p(x), _p(y), B, H, W, y.shape[3], _f3(shift), _f3(scale), _s()),
+               "vtp_lpips_scale_nhwc_f32")
+
+
+def maxpool2_f32(x, y):
+    """F.max_pool2d(., 2, 2) on f32 NHWC: x [B, H, W, C] -> y [B, H / 2, W / 2, C]; H, W even, C % 4 == 0"""
+    _need(x, "x", torch.float32, dims=4)
+    B, H, W, C = x.shape
+    if H % 2 or W % 2 or C % 4:
+        raise ValueError(f"x must be [B, H, W, C] with H, W even and C a multiple of 4, got {tuple(x.shape)}")
+    _need(y, "y", torch.float32, (B, H // 2, W // 2, C))
+    _need_gpu(x=x, y=y)
+    _lib.check(_lib_().vtp_maxpool2_f32(_p(x), _p(y), B, H, W, C, _s()), "vtp_maxpool2_f32")
+
+
+def lpips_head_f32(f, w, part):
+    """one LPIPS tap in fp32: f f32 NHWC [2 n, H, W, C] (features of image b and of image n + b), w f32 [C] -> part f64
+    [n, lpips_head_segments(H W)]: per pair the fp64 sums of the per-pixel distances over segments of 256 pixels"""
+    _need(f, "f", torch.float32, dims=4)
+    NB, H, W, C = f.shape
+    if NB % 2:
+        raise ValueError(f"f must hold 2 n images (n of the input, then n of the target), got {tuple(f.shape)}")
+    _need(w, "w", torch.float32, (C,))
+    _need(part, "part", torch.float64, (NB // 2, lpips_head_segments(H * W)))
+    _need_gpu(f=f, w=w, part=part)
+    _lib.check(_lib_().vtp_lpips_head_f32(_p(f), _p(w), _p(part), NB // 2, H * W, C, _s()), "vtp_lpips_head_f32")
+
+
+def lpips_finalize_f32(part, val, n, H, W):
+    """val f32 [n] = (((r_0 + r_1) + r_2) + r_3) + r_4, r_k = float(sum of tap k's segment sums / (H_k W_k)); part f64 = the five
+    [n, segments_k] blocks of lpips_head_f32 back to back for an H x W input"""
+    total = n * sum(lpips_head_segments((H >> k) * (W >> k)) for k in range(5))
+    _need(part, "part", torch.float64, (total,))
+    _need(val, "val", torch.float32, (n,))
+    _need_gpu(part=part, val=val)
+    _lib.check(_lib_().vtp_lpips_finalize_f32(_p(part), _p(val), n, H, W, _s()), "vtp_lpips_finalize_f32")
