@@ -179,6 +179,17 @@ def test_non_square_quick_gelu_last_pool_and_pooled_feature():
     run_all(m, img, text, pool="last", quick=True, tag="64x96 ")
 
 
+def test_wide_trunks():
+    """one tower at each wide preset's width (1152 / 18 heads / ratio 3.7778, 1280 / 20, 1536 / 24): norm_fwd_f32 in its 8-chunk
+    instantiation, fp32 GEMMs with N and K tails"""
+    m = _model(seed=6, vision_embed_dim=1152, vision_num_heads=18, vision_depth=1, vision_mlp_ratio=3.777777778, decoder_embed_dim=1280,
+               decoder_num_heads=20, decoder_depth=1, text_embed_dim=1536, text_num_heads=24, text_depth=1)
+    g = torch.Generator().manual_seed(24)
+    img = torch.randn(2, 3, 64, 96, generator=g)
+    text = torch.randint(0, 512, (2, 16), generator=g)
+    run_all(m, img, text, heads=(18, 20, 24), tag="wide ")
+
+
 def test_pooled_bottlenecked_feature_none_pool_and_intermediate_layers():
     from oracle import vtp_oracle as O
     m = _model(seed=5, vision_clip_feat="pooled", vision_bottleneck_ae_only=False, text_pool_type="none", text_embed_cls=True)

@@ -44,7 +44,9 @@ def check(out, ref, name, bf16_out=True, scale=1e-3):
 
 # ----------------------------------------------------------------------------------------------------------- GEMM
 @pytest.mark.parametrize("M,N,K", [(256, 256, 128), (8224, 2304, 768), (257, 384, 128), (129, 344, 128), (300, 128, 344),
-                                   (1000, 64, 768), (64, 768, 64)])
+                                   (1000, 64, 768), (64, 768, 64),
+                                   # the wide trunks (1152 / 1280 / 1536): N no multiple of 256, 18 k-tiles, K and N tails of H = 2904
+                                   (514, 1152, 1152), (514, 3456, 1152), (4112, 1152, 2904), (514, 3840, 1280), (514, 1536, 4096)])
 def test_gemm_bias_bf16(M, N, K):
     o = ops()
     g = torch.Generator(device=DEV).manual_seed(M * 7 + N * 3 + K)
@@ -99,7 +101,7 @@ def interleave(w1, w2):
     return out
 
 
-@pytest.mark.parametrize("M,D,H", [(257, 128, 344), (1028, 768, 2048)])
+@pytest.mark.parametrize("M,D,H", [(257, 128, 344), (1028, 768, 2048), (514, 1152, 2904), (514, 1280, 3416)])
 def test_gemm_swiglu(M, D, H):
     o = ops()
     g = torch.Generator(device=DEV).manual_seed(5)
@@ -595,7 +597,10 @@ def test_clip_loss_with_emulated_ranks(world, Bl, D):
 
 # ----------------------------------------------------------------------------------------------------------- TN GEMM (wgrad)
 @pytest.mark.parametrize("Mo,No,K,splits", [(128, 128, 64, 1), (768, 768, 8224, 11), (2304, 768, 8224, 4), (344, 128, 515, 1),
-                                            (64, 768, 8192, 3), (128, 688, 1000, 2)])
+                                            (64, 768, 8192, 3), (128, 688, 1000, 2),
+                                            # the wide trunks' weight gradients at 1620 token rows, 2 slices: what ops.gemm_tn_splits
+                                            # gives for them (pinned by test_wide_rows_gpu.test_gemm_tn_rows_use_the_engines_splits)
+                                            (1152, 2904, 1620, 2), (3456, 1152, 1620, 2), (1536, 4096, 515, 1)])
 def test_gemm_tn_matches_reference(Mo, No, K, splits):
     """C[Mo,No] = A[K,Mo]^T B[K,No] (weight gradient from untransposed activations) incl. token/column tails."""
     o = ops()
@@ -682,7 +687,8 @@ def test_gemm_qkv_rope_bit_identical_to_gemm_then_rope(cfg):
         f"cfg {cfg}: {int((out.view(torch.int16) != ref.view(torch.int16)).sum())} elements differ"
 
 
-@pytest.mark.parametrize("M,H,D", [(8192, 2048, 768), (2500, 344 - 344 % 8, 128), (16448, 2048, 768), (130, 1024, 384)])
+@pytest.mark.parametrize("M,H,D", [(8192, 2048, 768), (2500, 344 - 344 % 8, 128), (16448, 2048, 768), (130, 1024, 384),
+                                   (1620, 2904, 1152)])
 def test_gemm_dgrad_swiglu_fused_equals_two_kernels(M, H, D):
     """w3 dgrad with swiglu_bwd in its epilogue == vtp_gemm_nt (bf16 dh) followed by vtp_swiglu_bwd, bit for bit (the fused epilogue
     rounds dh to bf16 at the same point), on the 8-phase and on the ring tile configurations, with row / column tails"""

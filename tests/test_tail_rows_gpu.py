@@ -71,7 +71,7 @@ def test_row_map_gather_expand_bit_exact(M, L, T, D, n_pad):
 
 
 @pytest.mark.parametrize("kind", [0, 1])
-@pytest.mark.parametrize("D", [256, 768])
+@pytest.mark.parametrize("D", [256, 768, 1024, 772])  # 1024, 772: four chunks (full, ragged) -- the mapped row is read after the reductions
 def test_norm_bwd_mapped_residual_gradient(kind, D):
     """M = 70 rows of which 9 take a residual-gradient row of the compact buffer"""
     o = ops()
