@@ -96,9 +96,10 @@ int vtp_set_gemm_dynamic(int on);
  * (0 = every CU); delay_ticks > 0 starts every second workgroup of an XCD that many 10-ns ticks late (lock-step experiments).
  * Process-global; not part of the reference-facing surface. */
 int vtp_gemm_debug(void* timing, int grid_limit, int delay_ticks);
-/* diagnostics (tools/attn_bwd_timeline.py): `timing` = device buffer of 2 x [workgroups][16 waves][4] 64-bit s_memrealtime stamps
- * {start, operands staged, loop done, gradients stored} written by the resident attention backward kernels (dQ kernel, then the
- * dK/dV kernel), null = off.  Process-global; not part of the reference-facing surface. */
+/* diagnostics (tools/attn_timing.py, tools/attn_bwd_timeline.py; VTP_DIAG=1 for anything but all off): `timing` = device buffer of
+ * [workgroups][16 waves][8] 64-bit s_memrealtime stamps, null = off: slots 0..6 of the resident attention forward, slots 0..3 {start,
+ * operands staged, loop done, gradients stored} of the backward kernels (per-head backward: 2 x the buffer, dQ kernel, then the
+ * dK/dV kernel).  Process-global; not part of the reference-facing surface. */
 /* diagnostics (tools/cu_thief.py; VTP_DIAG=1): nwg workgroups that hold one CU each (160 KiB LDS) for ticks x 10 ns on `stream` -- the
  * footprint of a communication kernel beside the step; out: null or nwg u64 (ticks held) */
 int vtp_cu_thief(int nwg, int ticks, void* out, void* stream);

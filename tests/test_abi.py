@@ -82,13 +82,24 @@ def test_missing_library_is_a_loud_error(monkeypatch, tmp_path):
 
 
 def test_diagnostics_hooks_are_refused_without_vtp_diag(monkeypatch):
-    """vtp_gemm_debug feeds production kernels process-wide -- anything but 'all off' needs VTP_DIAG=1 (host-only check)"""
+    """vtp_gemm_debug, vtp_attn_debug and vtp_cu_thief feed or crowd production kernels process-wide -- anything but 'all
+    off' needs VTP_DIAG=1 (host-only checks: nothing here launches)"""
     from vtp_amd import _lib
     lib = _lib.load()
     monkeypatch.delenv("VTP_DIAG", raising=False)
     assert lib.vtp_gemm_debug(None, 0, 0) == 0
     assert lib.vtp_gemm_debug(None, 0, 100) != 0 and b"VTP_DIAG" in lib.vtp_last_error()
     assert lib.vtp_gemm_debug(None, 64, 0) != 0
+    assert lib.vtp_attn_debug(None, 0, 0, 0) == 0
+    for args in ((None, 0, -1, 0), (None, 64, 0, 0)):
+        assert lib.vtp_attn_debug(*args) != 0 and b"VTP_DIAG" in lib.vtp_last_error(), args
+    assert lib.vtp_cu_thief(1, 0, None, None) != 0 and b"VTP_DIAG" in lib.vtp_last_error()  # (with the variable set it would launch)
     monkeypatch.setenv("VTP_DIAG", "1")
     assert lib.vtp_gemm_debug(None, 0, -5) != 0  # the 'no stores' mode is gone
     assert lib.vtp_gemm_debug(None, 64, 0) == 0 and lib.vtp_gemm_debug(None, 0, 0) == 0
+    try:
+        for args in ((None, 0, -1, 0), (None, 64, 0, 0)):
+            assert lib.vtp_attn_debug(*args) == 0, args
+        assert lib.vtp_attn_debug(None, -64, 0, 0) != 0 and lib.vtp_attn_debug(None, 0, 0, -5) != 0
+    finally:
+        assert lib.vtp_attn_debug(None, 0, 0, 0) == 0

@@ -86,10 +86,12 @@ def _need_gpu():
 
 
 @pytest.fixture
-def attn_debug():
-    """the library; whatever the test sets with vtp_attn_debug, the default dispatch (None, 0, 0, 0) is restored after it"""
+def attn_debug(monkeypatch):
+    """the library, in a process that asked for diagnostics (VTP_DIAG=1: the forced per-head path is a diagnostics switch); whatever
+    the test sets with vtp_attn_debug, the default dispatch (None, 0, 0, 0) is restored after it"""
     from vtp_amd import _lib
     lib = _lib.load()
+    monkeypatch.setenv("VTP_DIAG", "1")
     try:
         yield lib
     finally:
@@ -335,3 +337,79 @@ def test_either_side_of_resident_boundary(N, causal):
     """N = 320 is the last resident shape; 321 and up, and causal at any N, take the tiled kernels (attention.hip)"""
     assert (paths(N, 2, 2, causal)[0] == "tiled") == (N > RES_MAXN or causal)
     _bar(2, N, 2, causal=causal, seed=900 + N)
+
+
+# ---------------------------------------------------------------------------------------------------- timeline stamps
+SENTINEL = -1  # the stamps are 100 MHz wall-clock ticks: positive
+
+
+def _stamp_plan(N, B, heads, bwd, per_head):
+    """[kernels][workgroups][16 waves][8] bool: the slots the launch owes (attention_resident.hip, restated): a wave's stamps are a
+    prefix of its kernel's slots -- forward 0..4, and 5, 6 where the odd last tile is split; backward 0..3, a wave without a row
+    block (per-head kernels) leaves after slot 1; the two-pass forward writes none"""
+    nw = (N + 31) // 32
+    fwd_path, bwd_path = paths(N, B, heads, per_head_bwd=per_head)
+    if not bwd:
+        if fwd_path.startswith("F3"):
+            return torch.zeros(1, B * heads, 16, 8, dtype=torch.bool)
+        want = torch.zeros(1, B * heads, 16, 8, dtype=torch.bool)
+        want[:, :, :max(1, nw // 2), :7 if fwd_path.startswith("F2") else 5] = True
+        return want
+    if bwd_path in ("B1", "B2"):
+        want = torch.zeros(1, B * heads, 16, 8, dtype=torch.bool)
+        want[:, :, :PB_WAVES if bwd_path == "B2" else 2, :4] = True
+        return want
+    wpb = res_waves_per_block(nw, B * heads)
+    nz = (nw + wpb - 1) // wpb
+    want = torch.zeros(2, nz, B * heads, 16, 8, dtype=torch.bool)  # workgroup = (z x images + image) x heads + head
+    for z in range(nz):
+        for w in range(wpb):
+            want[:, z, :, w, :4 if z * wpb + w < nw else 2] = True
+    return want.view(2, nz * B * heads, 16, 8)
+
+
+@pytest.mark.parametrize("N,bwd,per_head,fp,bp", [(257, False, False, "F2/1", "B2"), (64, False, False, "F1", "B1"),
+                                                  (320, False, False, "F3 split", "B3 split"), (257, True, False, "F2/1", "B2"),
+                                                  (257, True, True, "F2/1", "B3 split")])
+def test_stamps_leave_results_alone_and_stay_in_their_slots(N, bwd, per_head, fp, bp, attn_debug):
+    """vtp_attn_debug stamps, [workgroup][16 waves][8] per kernel: the launch with stamps computes bit for bit what the launch
+    without them does, every slot the launch owes is written and non-decreasing in slot order, and everything else in the buffer
+    (waves not launched, slots the kernel does not use, the 128 entries behind the last workgroup) keeps its sentinel"""
+    from vtp_amd import _lib
+    o = ops()
+    B, heads = 2, 2
+    D = heads * 64
+    assert paths(N, B, heads, per_head_bwd=per_head) == (fp, bp)
+    want = _stamp_plan(N, B, heads, bwd, per_head).to(DEV)
+    assert bool(want.any()) == (not (not bwd and fp.startswith("F3")))
+    qkv, d_o = _inputs(B, N, heads, 1200 + N)
+    wpw = -1 if per_head else 0
+    tbuf = torch.full((want.numel() + 128,), SENTINEL, dtype=torch.int64, device=DEV)
+
+    def run(timing):
+        out = torch.full((B * N, D), NAN, dtype=torch.bfloat16, device=DEV)
+        lse = torch.full((B, heads, N), NAN, device=DEV)
+        dqkv = torch.full((B * N, 3 * D), NAN, dtype=torch.bfloat16, device=DEV)
+        delta = torch.full((B, heads, N), NAN, device=DEV)
+        _lib.check(attn_debug.vtp_attn_debug(None if bwd else timing, 0, wpw, 0), "vtp_attn_debug")
+        o.attn_fwd(qkv, qkv[:, D:], qkv[:, 2 * D:], out, lse, B, N, heads, N * 3 * D, 3 * D, N * D, D, SCALE, False)
+        _lib.check(attn_debug.vtp_attn_debug(timing if bwd else None, 0, wpw, 0), "vtp_attn_debug")
+        o.attn_bwd(qkv, qkv[:, D:], qkv[:, 2 * D:], out, d_o, lse, delta, dqkv, dqkv[:, D:], dqkv[:, 2 * D:], B, N, heads,
+                   N * 3 * D, 3 * D, N * D, D, SCALE, False)
+        torch.cuda.synchronize()
+        _lib.check(attn_debug.vtp_attn_debug(None, 0, 0, 0), "vtp_attn_debug")
+        return out, lse, dqkv
+
+    plain = run(None)
+    assert torch.equal(tbuf, torch.full_like(tbuf, SENTINEL))
+    stamped = run(tbuf.data_ptr())
+    for nm, a, c in zip(("out", "lse", "dq/dk/dv"), plain, stamped):
+        assert torch.isfinite(a.float()).all(), nm
+        assert torch.equal(_bits(a), _bits(c)), f"{nm}: the stamped launch differs from the plain one"
+    got = tbuf[:want.numel()].view(want.shape)
+    written = got != SENTINEL
+    assert torch.equal(written, want), f"{int((written & ~want).sum())} stray stamps, {int((want & ~written).sum())} missing"
+    assert torch.all(tbuf[want.numel():] == SENTINEL), "stamps behind the last workgroup"
+    assert torch.all(got[want] > 0)
+    step = got[..., 1:] - got[..., :-1]
+    assert torch.all(step[want[..., 1:]] >= 0), "a wave's stamps run backwards"

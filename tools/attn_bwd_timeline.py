@@ -4,6 +4,7 @@ Usage (GPU box): python tools/attn_bwd_timeline.py [B N heads] > gpurun_out/attn
 import os
 import sys
 
+os.environ.setdefault("VTP_DIAG", "1")  # vtp_attn_debug: process-global hooks of production kernels
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
@@ -52,7 +53,7 @@ def run(lib, B, N, h):
     nwg = B * h * ((nblk + wpb - 1) // wpb)
     if WPB == 0 and (nblk in (8, 2) or (nblk == 9 and N - 256 <= 2) or (nblk == 3 and N - 64 <= 2)):  # fused kernel: one workgroup per head
         nwg = B * h
-    tbuf = torch.zeros(2 * nwg_max * 64, dtype=torch.int64, device=dev)
+    tbuf = torch.zeros(2 * nwg_max * 128, dtype=torch.int64, device=dev)  # [workgroups][16 waves][8]
     lib.vtp_attn_debug(tbuf.data_ptr(), PAD, WPB, STAG)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
@@ -64,7 +65,7 @@ def run(lib, B, N, h):
     t = tbuf.cpu().double() / 100.0  # us
     fused = WPB == 0 and (nblk in (8, 2) or (nblk == 9 and N - 256 <= 2) or (nblk == 3 and N - 64 <= 2))
     for ki, name in enumerate(("fused",) if fused else ("dQ", "dK/dV")):
-        seg = t[ki * nwg * 64:(ki + 1) * nwg * 64].view(nwg, 16, 4)
+        seg = t[ki * nwg * 128:(ki + 1) * nwg * 128].view(nwg, 16, 8)
         act = seg[:, :, 1] > 0
         t0 = seg[:, :, 0][seg[:, :, 0] > 0].min()
         done = seg[:, :, 3]

@@ -14,9 +14,9 @@
 // v2 work split does not cover).  Backward: one fused kernel at 33 .. 66 and 225 .. 258 tokens (attn_bwd_fused_kernel: the shapes of the
 // step), dQ and dK/dV kernels otherwise; delta and the inverse RoPE are fused in both.
 #include "common.h"
+#include "diag.h"
 #include <algorithm>
 #include <cstdio>
-#include <cstdlib>
 #include "vtp_hip.h"
 
 namespace vtp {
@@ -30,22 +30,22 @@ struct AttnResArgs {
   const bf16 *q, *k, *v, *o, *d_o;
   bf16 *out, *dq, *dk, *dv;
   float* lse;
-  float* delta;           // written by the dQ kernel (rowsum(dO * O)), read by the dK/dV kernel that follows it
+  float* delta;           // backward: rowsum(dO * O), written by the dQ kernel (or phase), read by the dK/dV kernel that follows it
   const bf16 *rope_sin, *rope_cos;  // [hw, 64] tables or null: dq / dk leave inverse-rotated (gradient w.r.t. the un-rotated q, k)
   int rope_prefix;
   int B, N, heads, npad;  // npad = N rounded up to 32
   long sb, sn, sbo, sno;
   float scale;
   int stagger;            // experiment: start every second workgroup of the first round this many 10-ns ticks late
-  long long* timing;      // diagnostics (vtp_attn_debug): [workgroup][16 waves][4] s_memrealtime stamps of the backward kernels, or null
+  unsigned long long* timing;  // diagnostics (vtp_attn_debug): [workgroup][16 waves][8] stamps (diag.h), or null
 };
 
-// phase stamps of the backward kernels: 0 start, 1 operands staged, 2 loop done, 3 gradients stored
-#define BWD_STAMP(i)                                                                                                     \
-  do {                                                                                                                   \
-    if (__builtin_expect(p.timing != nullptr, 0) && lane == 0)                                                           \
-      p.timing[((((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 16 + wave) * 4 + (i)] = wall_clock64(); \
-  } while (0)
+// stamp i of a wave, slot [workgroup][16 waves][8].  Backward: 0 start, 1 operands staged, 2 loop done, 3 gradients stored;
+// forward: 0 start, 1 first data, 2 barrier, 3 end of the key loop, 4 stores, 5 odd-tile share, 6 merge barrier
+__device__ __forceinline__ void attn_stamp(const AttnResArgs& p, size_t wg, int lane, int wave, int i) {
+  if (__builtin_expect(p.timing != nullptr, 0) && lane == 0) diag_stamp(p.timing, (wg * 16 + wave) * 8 + i);
+}
+__device__ __forceinline__ int grid_wg() { return (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x; }  // per-head kernels
 
 __device__ __forceinline__ int swz_key(int r) { return (((r >> 1) & 1) << 2) | ((r >> 2) & 3); }
 
@@ -458,13 +458,6 @@ __device__ __forceinline__ void stage_block_asm(const bf16* kbase, const bf16* v
   }
 }
 
-// phase stamps of one workgroup (VTP_ATTN_TIMING=1: the launcher passes a buffer in p.delta and prints the cycle counts)
-#define ATTN_TSTAMP(i)                                                                            \
-  do {                                                                                            \
-    if (p.delta && blockIdx.x == 3 && blockIdx.y == 5 && lane == 0)                               \
-      ((long long*)p.delta)[wave * 8 + (i)] = __builtin_readcyclecounter();                       \
-  } while (0)
-
 __global__ __launch_bounds__(256, 2) void attn_fwd_res2_kernel(const AttnResArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* Ks = smem;
@@ -474,7 +467,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_res2_kernel(const AttnResArgs
   const int h = blockIdx.x, b = blockIdx.y;
   const bf16* qb = p.q + (long)b * p.sb + h * 64;
   const int ntiles = p.npad >> 5, nkb = ntiles, q0 = wave * 64;
-  ATTN_TSTAMP(0);
+  auto stamp = [&p, lane, wave](int i) { attn_stamp(p, blockIdx.y * gridDim.x + blockIdx.x, lane, wave, i); };
+  stamp(0);
   const bool split_last = (ntiles & 1) && ntiles > 1;  // the launcher guarantees N - 32 (ntiles - 1) <= RES_SPLIT_COLS then
   const int qL = (ntiles - 1) * 32;
   bf16x8 qf[2][4], qfl[1][4];
@@ -497,10 +491,10 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_res2_kernel(const AttnResArgs
   stage_block_asm(kbase, vbase, p.sn, p.N, 0, img, wave, nwaves, lane);
   if (nkb > 1) stage_block_asm(kbase, vbase, p.sn, p.N, 1, img, wave, nwaves, lane);
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-  ATTN_TSTAMP(1);
+  stamp(1);
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
-  ATTN_TSTAMP(2);
+  stamp(2);
   for (int kb = 2; kb < nkb; ++kb) stage_block_asm(kbase, vbase, p.sn, p.N, kb, img, wave, nwaves, lane);
   const int stream_ops = 2 * ((4 - wave + nwaves - 1) / nwaves);  // this wave's DMA operations per key block
   const float sc2 = p.scale * LOG2E_R;
@@ -515,7 +509,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_res2_kernel(const AttnResArgs
       attn_key_loop<1>(Ks, Vs, *(const bf16x8(*)[1][4])&qf, p.N, nkb, 0, 1, sc2, lane, o1, *(float(*)[1])&m, *(float(*)[1])&l,
                        stream_ops);
     }
-    ATTN_TSTAMP(3);
+    stamp(3);
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       if (t == 1 && !two) break;
@@ -526,7 +520,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_res2_kernel(const AttnResArgs
       if (valid && hi == 0 && p.lse) p.lse[srow0 + qi] = (m[t] + log2f(lt)) * LN2_R;
     }
   }
-  ATTN_TSTAMP(4);
+  stamp(4);
   if (!split_last) return;
   // ---- the odd last tile: this wave's share of the key blocks, then the merge
   const int cols = p.N - qL;  // valid queries of the tile
@@ -546,9 +540,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_res2_kernel(const AttnResArgs
       }
     }
   }
-  ATTN_TSTAMP(5);
+  stamp(5);
   __syncthreads();
-  ATTN_TSTAMP(6);
+  stamp(6);
   if (wave != 0) return;
   {
     const int c = min(lane & 31, cols - 1);
@@ -582,14 +576,9 @@ __global__ __launch_bounds__(640) void attn_bwd_dq_res_kernel(const AttnResArgs 
   char* Vs = smem + p.npad * 128;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6, hi = lane >> 5;
   const int h = blockIdx.x, b = blockIdx.y;
-  BWD_STAMP(0);
-  if (__builtin_expect(p.stagger > 0, 0)) {
-    const int wg = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    if (wg < 256 && ((wg >> 3) & 1)) {
-      const unsigned long long t0 = wall_clock64();
-      while (wall_clock64() - t0 < (unsigned long long)p.stagger) __builtin_amdgcn_s_sleep(16);
-    }
-  }
+  auto stamp = [&p, lane, wave](int i) { attn_stamp(p, grid_wg(), lane, wave, i); };
+  stamp(0);
+  if (__builtin_expect(p.stagger > 0, 0) && grid_wg() < 256 && ((grid_wg() >> 3) & 1)) diag_delay(p.stagger);
   stage_resident(p.k + (long)b * p.sb + h * 64, p.sn, p.N, p.npad, Ks, wave, nwaves, lane);
   stage_resident(p.v + (long)b * p.sb + h * 64, p.sn, p.N, p.npad, Vs, wave, nwaves, lane);
   const int q0 = (blockIdx.z * nwaves + wave) * 32, qi = q0 + (lane & 31), qc = min(qi, p.N - 1);
@@ -619,7 +608,7 @@ __global__ __launch_bounds__(640) void attn_bwd_dq_res_kernel(const AttnResArgs 
   }
   wait_all_dma();
   __syncthreads();
-  BWD_STAMP(1);
+  stamp(1);
   if (q0 >= p.npad) return;
   const float sc2 = p.scale * LOG2E_R;
   const f32x2 sc2v = {sc2, sc2}, nlse = {-lse2, -lse2}, scv = {p.scale, p.scale}, ndlt = {-dlt * p.scale, -dlt * p.scale};
@@ -661,7 +650,7 @@ __global__ __launch_bounds__(640) void attn_bwd_dq_res_kernel(const AttnResArgs 
       dq[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr(Ks, db, kb * 32, 1, lane), d1, dq[db], 0, 0, 0);
     }
   }
-  BWD_STAMP(2);
+  stamp(2);
   if (qi < p.N) {
   bf16* drow = p.dq + (long)b * p.sb + (long)qi * p.sn + h * 64;
   const bool rot = p.rope_sin && qi >= p.rope_prefix;
@@ -677,7 +666,7 @@ __global__ __launch_bounds__(640) void attn_bwd_dq_res_kernel(const AttnResArgs 
     store_grad_pair(drow, 8 * g + 4 * hi, lo, hv, rot ? p.rope_sin : nullptr, p.rope_cos, t);
   }
   }
-  BWD_STAMP(3);
+  stamp(3);
 }
 
 // ------------------------------------------------------------------------------------------------ backward: dK, dV
@@ -689,14 +678,9 @@ __global__ __launch_bounds__(640) void attn_bwd_dkv_res_kernel(const AttnResArgs
   float* dlt_s = lse_s + p.npad;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6, hi = lane >> 5;
   const int h = blockIdx.x, b = blockIdx.y;
-  BWD_STAMP(0);
-  if (__builtin_expect(p.stagger > 0, 0)) {
-    const int wg = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    if (wg < 256 && ((wg >> 3) & 1)) {
-      const unsigned long long t0 = wall_clock64();
-      while (wall_clock64() - t0 < (unsigned long long)p.stagger) __builtin_amdgcn_s_sleep(16);
-    }
-  }
+  auto stamp = [&p, lane, wave](int i) { attn_stamp(p, grid_wg(), lane, wave, i); };
+  stamp(0);
+  if (__builtin_expect(p.stagger > 0, 0) && grid_wg() < 256 && ((grid_wg() >> 3) & 1)) diag_delay(p.stagger);
   stage_resident(p.q + (long)b * p.sb + h * 64, p.sn, p.N, p.npad, Qs, wave, nwaves, lane);
   stage_resident(p.d_o + (long)b * p.sbo + h * 64, p.sno, p.N, p.npad, Gs, wave, nwaves, lane);
   const long srow0 = ((long)b * p.heads + h) * p.N;
@@ -718,7 +702,7 @@ __global__ __launch_bounds__(640) void attn_bwd_dkv_res_kernel(const AttnResArgs
   }
   wait_all_dma();
   __syncthreads();
-  BWD_STAMP(1);
+  stamp(1);
   if (k0 >= p.npad) return;
   const float sc2 = p.scale * LOG2E_R;
   const f32x2 sc2v = {sc2, sc2}, scv = {p.scale, p.scale};
@@ -783,7 +767,7 @@ __global__ __launch_bounds__(640) void attn_bwd_dkv_res_kernel(const AttnResArgs
       dk[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr_at(tq0, tq1, 1), d1, dk[db], 0, 0, 0);
     }
   }
-  BWD_STAMP(2);
+  stamp(2);
   if (ki < p.N) {
   bf16* krow = p.dk + (long)b * p.sb + (long)ki * p.sn + h * 64;
   bf16* vrow = p.dv + (long)b * p.sb + (long)ki * p.sn + h * 64;
@@ -803,7 +787,7 @@ __global__ __launch_bounds__(640) void attn_bwd_dkv_res_kernel(const AttnResArgs
     store_grad_pair(vrow, 8 * g + 4 * hi, c0, c1, nullptr, nullptr, 0);
   }
   }
-  BWD_STAMP(3);
+  stamp(3);
 }
 
 // ------------------------------------------------------------------------------------------------ backward, fused
@@ -876,11 +860,6 @@ __device__ __forceinline__ float row_delta(const bf16x8 (&of)[4], const bf16x8 (
     for (int e = 0; e < 8; ++e) dlt += bf2f(of[ks][e]) * bf2f(dof[ks][e]);
   return dlt + __shfl_xor(dlt, 32, 64);
 }
-
-#define PB_STAMP(i)                                                                                                   \
-  do {                                                                                                                \
-    if (__builtin_expect(p.timing != nullptr, 0) && lane == 0) p.timing[((size_t)hid * 16 + wave) * 4 + (i)] = wall_clock64(); \
-  } while (0)
 
 // one (key block, query block) step of the dK / dV computation, the lane being a key: s / dp from the Q / dO row fragments at LDS
 // offset `qoff` (dO image `img` bytes behind), P and dS with the per-query -lse / -delta from LDS, dv += dO^T P, dk += Q^T dS
@@ -972,7 +951,8 @@ __global__ __launch_bounds__(64 * W) void attn_bwd_fused_kernel(const AttnResArg
   float* xk = xq + (W + 1) * PB_XROWS * 64;
   float* xv = xk + (W + 1) * PB_XROWS * 64;
   const int hid = blockIdx.x, b = hid / p.heads, h = hid - b * p.heads;
-  PB_STAMP(0);
+  auto stamp = [&p, lane, wave, hid](int i) { attn_stamp(p, hid, lane, wave, i); };
+  stamp(0);
   stage_image_asm(p.q + (long)b * p.sb + h * 64, p.sn, p.N, p.npad, QO, wave, W, lane);
   stage_image_asm(p.d_o + (long)b * p.sbo + h * 64, p.sno, p.N, p.npad, GO, wave, W, lane);
   stage_image_asm(p.k + (long)b * p.sb + h * 64, p.sn, p.N, p.npad, KO, wave, W, lane);
@@ -1008,7 +988,7 @@ __global__ __launch_bounds__(64 * W) void attn_bwd_fused_kernel(const AttnResArg
   }
   wait_all_dma();
   __syncthreads();
-  PB_STAMP(1);
+  stamp(1);
   // ------------------------------------------------------------------------------------------ phase 1: dQ (the lane is a query)
   {
     bf16x8 qf[4], dof[4];
@@ -1065,7 +1045,7 @@ __global__ __launch_bounds__(64 * W) void attn_bwd_fused_kernel(const AttnResArg
     }
   }
   __syncthreads();  // lse_s / dlt_s and the 9th block's dq slots are complete
-  PB_STAMP(2);
+  stamp(2);
   if (odd && (int)threadIdx.x < nx * 8) {
     const int row = threadIdx.x >> 3, d0 = 4 * (threadIdx.x & 7), qrow = 32 * W + row;
     f32x4 lo = {0.f, 0.f, 0.f, 0.f}, hv = {0.f, 0.f, 0.f, 0.f};
@@ -1141,7 +1121,7 @@ __global__ __launch_bounds__(64 * W) void attn_bwd_fused_kernel(const AttnResArg
       store_grad_pair(p.dv + (long)b * p.sb + (long)krow_i * p.sn + h * 64, d0, c0, c1, nullptr, nullptr, 0);
     }
   }
-  PB_STAMP(3);
+  stamp(3);
 }
 
 // a head with >= 4 row blocks is split over two workgroups (each stages the whole K / V or Q / dO image, 2 x 37 KB at N = 257):
@@ -1157,10 +1137,10 @@ static void set_lds(K kern, int bytes) {
   hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
-static long long* g_attn_timing = nullptr;
-static int g_attn_wpb = 0;      // diagnostics: > 0 per-head kernels with that many waves per workgroup, -1 per-head kernels, 0 default
-static int g_attn_lds_pad = 0;
-static int g_attn_stagger = 0;  // diagnostics: extra dynamic LDS bytes per backward workgroup (occupancy experiments)
+static unsigned long long* g_attn_timing = nullptr;  // diagnostics (vtp_attn_debug)
+static int g_attn_wpb = 0;      // > 0 per-head backward kernels with that many waves per workgroup, -1 per-head kernels, 0 default
+static int g_attn_lds_pad = 0;  // extra dynamic LDS bytes per backward workgroup (occupancy experiments)
+static int g_attn_stagger = 0;
 
 // host side, called by vtp_attn_fwd / vtp_attn_bwd (attention.hip) for non-causal N <= RES_MAXN
 int attn_resident_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B, int N, int heads, long sb,
@@ -1168,6 +1148,7 @@ int attn_resident_fwd(const void* q, const void* k, const void* v, void* o, floa
   AttnResArgs a = {};
   a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.out = (bf16*)o; a.lse = lse;
   a.B = B; a.N = N; a.heads = heads; a.npad = (N + 31) / 32 * 32; a.sb = sb; a.sn = sn; a.sbo = sbo; a.sno = sno; a.scale = scale;
+  a.timing = g_attn_timing;
   static bool attr = false;
   if (!attr) {
     set_lds(attn_fwd_res_kernel, 2 * RES_MAXN * 128);
@@ -1182,24 +1163,12 @@ int attn_resident_fwd(const void* q, const void* k, const void* v, void* o, floa
     if ((!odd || cols <= RES_SPLIT_COLS) && ntiles / 2 <= 4) {  // two query tiles per wave, single pass, odd last tile split over the key blocks
       const int waves = std::max(1, ntiles / 2);
       const int lds = 2 * a.npad * 128 + (odd ? waves * cols * 2 * 34 * 4 : 0);
-      static long long* tbuf = nullptr;
-      static const bool timing = getenv("VTP_ATTN_TIMING") != nullptr;
-      if (timing && !tbuf && hipMalloc((void**)&tbuf, 64 * 8) != hipSuccess) tbuf = nullptr;
-      if (timing) a.delta = (float*)tbuf;
-      hipLaunchKernelGGL(attn_fwd_res2_kernel, dim3(heads, B), dim3(64 * waves), lds, s, a);
-      if (timing && tbuf) {  // diagnosis only: synchronous
+      if (a.timing) {  // diagnosis only
         int occ = -1;
         (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, attn_fwd_res2_kernel, 64 * waves, lds);
         fprintf(stderr, "[attn timing] workgroups per CU by the runtime's count: %d (lds %d B, %d waves)\n", occ, lds, waves);
-        long long hbuf[64];
-        (void)hipStreamSynchronize(s);
-        (void)hipMemcpy(hbuf, tbuf, sizeof hbuf, hipMemcpyDeviceToHost);
-        for (int w = 0; w < waves; ++w) {
-          fprintf(stderr, "[attn timing] wave %d:", w);
-          for (int i = 1; i < 7; ++i) fprintf(stderr, " t%d=%lld", i, hbuf[w * 8 + i] - hbuf[0]);
-          fprintf(stderr, "\n");
-        }
       }
+      hipLaunchKernelGGL(attn_fwd_res2_kernel, dim3(heads, B), dim3(64 * waves), lds, s, a);
       return check_launch("attn_fwd_resident2");
     }
   }
@@ -1253,19 +1222,24 @@ int attn_resident_bwd(const void* q, const void* k, const void* v, const void* o
             (int)block.x / 64, 2 * a.npad * 128, 2 * a.npad * 128 + 8 * a.npad);
   }
   hipLaunchKernelGGL(attn_bwd_dq_res_kernel, grid, block, 2 * a.npad * 128 + g_attn_lds_pad, s, a);
-  if (a.timing) a.timing += (size_t)grid.x * grid.y * grid.z * 64;  // second half of the buffer: the dK / dV kernel
+  if (a.timing) a.timing += (size_t)grid.x * grid.y * grid.z * 16 * 8;  // second half of the buffer: the dK / dV kernel
   hipLaunchKernelGGL(attn_bwd_dkv_res_kernel, grid, block, 2 * a.npad * 128 + 8 * a.npad + g_attn_lds_pad, s, a);
   return check_launch("attn_bwd_resident");
 }
 
 }  // namespace vtp
 
-// diagnostics (tools/attn_bwd_timeline.py): device buffer of 2 x [workgroups][16 waves][4] 64-bit s_memrealtime stamps written by
-// the resident backward kernels (dQ kernel first, dK/dV kernel behind it), or null = off.  Process-global.
+// diagnostics (tools/attn_timing.py, tools/attn_bwd_timeline.py): process-global hooks of the resident kernels, gated as vtp_gemm_debug.
+// `timing` = device buffer of [workgroups][16 waves][8] u64 stamps (100 MHz) of attn_fwd_res2_kernel (slots 0..6) and the backward
+// kernels (0..3), or null; the other three: g_attn_lds_pad, g_attn_wpb, AttnResArgs.stagger.  The buffer must hold workgroups of the
+// launch x 128 values, twice that for the per-head backward (dQ kernel, then dK/dV) -- the kernels index it by workgroup and do not check.
 extern "C" int vtp_attn_debug(void* timing, int lds_pad, int waves_per_wg, int stagger_ticks) {
-  vtp::g_attn_stagger = stagger_ticks;
-  vtp::g_attn_wpb = waves_per_wg;
-  vtp::g_attn_timing = (long long*)timing;
+  const bool off = timing == nullptr && lds_pad == 0 && waves_per_wg == 0 && stagger_ticks == 0;
+  if (!off && !vtp::diag_allowed("vtp_attn_debug")) return VTP_ERR_ARG;
+  VTP_REQUIRE(lds_pad >= 0 && stagger_ticks >= 0, "vtp_attn_debug: negative LDS pad / stagger");
+  vtp::g_attn_timing = (unsigned long long*)timing;
   vtp::g_attn_lds_pad = lds_pad;
-  return 0;
+  vtp::g_attn_wpb = waves_per_wg;
+  vtp::g_attn_stagger = stagger_ticks;
+  return VTP_OK;
 }

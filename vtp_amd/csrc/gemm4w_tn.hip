@@ -17,6 +17,7 @@
 // 8, 32-bit operand offsets.
 #include "gemm_common.h"
 #include "gemm_group.h"
+#include "diag.h"
 #include "gemm4w_tn_ktile.inc"
 
 namespace vtp {
@@ -78,7 +79,7 @@ __device__ __forceinline__ void w4t_segment(const GroupArgs& ga, int tile, int k
   // diagnostics (vtp_gemm_debug, tools/wgrad_timeline.py): 100-MHz stamps per workgroup -- [0] start, [1] first operands landed,
   // [2] k loop done, [3] published + ticket drawn, [4] done, [5] tile, [6] K slice, [7] XCC id
   auto stamp = [&](int which) {
-    if (__builtin_expect(ga.timing != nullptr, 0) && tid == 0) ga.timing[(size_t)blockIdx.x * 8 + which] = wall_clock64();
+    if (__builtin_expect(ga.timing != nullptr, 0) && tid == 0) diag_stamp(ga.timing, (size_t)blockIdx.x * 8 + which);
   };
   if (__builtin_expect(ga.timing != nullptr, 0) && tid == 0) {
     ga.timing[(size_t)blockIdx.x * 8 + 5] = (unsigned long long)tile;

@@ -25,6 +25,7 @@
 //   * dedicated 32 KiB epilogue staging (4 KiB per wave) beside the 128 KiB ring: 160 KiB = all of a CU's LDS, 1 workgroup / CU.
 #include "gemm_common.h"
 #include "gemm_group.h"
+#include "diag.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -347,10 +348,7 @@ __device__ __forceinline__ void gemm8p_body(const GemmArgs& p, int bx, int zslic
     __builtin_amdgcn_sched_barrier(0);
   };
 
-  if (__builtin_expect(p.dbg_delay > 0, 0) && ((blockIdx.x >> 3) & 1)) {
-    const unsigned long long t0 = wall_clock64();
-    while (wall_clock64() - t0 < (unsigned long long)p.dbg_delay) __builtin_amdgcn_s_sleep(16);
-  }
+  if (__builtin_expect(p.dbg_delay > 0, 0) && ((blockIdx.x >> 3) & 1)) diag_delay(p.dbg_delay);
   // ---------------------------------------------------------------- prologue: 7 half-tiles in flight, the first 4 landed
   {
     int m0s, n0s;
@@ -372,7 +370,7 @@ __device__ __forceinline__ void gemm8p_body(const GemmArgs& p, int bx, int zslic
   unsigned long long cyc0 = 0;
   auto stamp = [&](int ti, int which) {
     if (__builtin_expect(p.timing != nullptr, 0) && tid == 0 && ti < 16) {
-      p.timing[((size_t)blockIdx.x * 16 + ti) * 4 + which] = wall_clock64();
+      diag_stamp(p.timing, ((size_t)blockIdx.x * 16 + ti) * 4 + which);
       // slot 3: shader cycles (s_memtime) the k loop took -- with the 100 MHz stamps this gives the clock the CU ran at
       if (which == 0) cyc0 = clock64();
       if (which == 1) p.timing[((size_t)blockIdx.x * 16 + ti) * 4 + 3] = clock64() - cyc0;
@@ -386,7 +384,9 @@ __device__ __forceinline__ void gemm8p_body(const GemmArgs& p, int bx, int zslic
     if constexpr (TRANS) do_csum = p.colsum != nullptr && wc == 0 && n0 == 0;
     if (wr == 1) seg_barrier();  // group 1 runs one barrier behind group 0 through this tile's k loop
     for (int kt = 0; kt < nk; ++kt, ++ktg) {
-      if (__builtin_expect(p.timing != nullptr, 0) && tid == 0 && ti == 1 && kt < 16)  // diagnostics: start of every k-tile of tile 1
+      // diagnostics: start of every k-tile of tile 1.  Not diag_stamp(): as a call's argument the slot (a load of gridDim) is formed
+      // before the clock is read, and that order alone moves the SGPR allocation of every kernel of this file
+      if (__builtin_expect(p.timing != nullptr, 0) && tid == 0 && ti == 1 && kt < 16)
         p.timing[(size_t)(gridDim.x + blockIdx.x) * 64 + kt] = wall_clock64();
       const char* kb = smem + (ktg & 1) * (4 * P8_SLOT);
       Frags b1, b2, a1[2], a2[2];
@@ -804,11 +804,7 @@ extern "C" int vtp_gemm_debug(void* timing, int grid_limit, int delay_ticks) {
   // diagnostics (VTP_DIAG=1 in its environment: the tools/ scripts set it); the "no stores" mode of round 3 is gone.  The stamp
   // buffer must hold (workgroups of the launch + 256) x 64 u64 values -- the kernels index it by workgroup and do not check.
   const bool off = timing == nullptr && grid_limit == 0 && delay_ticks == 0;
-  const char* diag = getenv("VTP_DIAG");
-  if (!off && !(diag && diag[0] == '1')) {
-    vtp::set_error("vtp_gemm_debug: diagnostics hooks need VTP_DIAG=1 in the environment");
-    return VTP_ERR_ARG;
-  }
+  if (!off && !vtp::diag_allowed("vtp_gemm_debug")) return VTP_ERR_ARG;
   if (delay_ticks < 0 || grid_limit < 0) {
     vtp::set_error("vtp_gemm_debug: negative grid limit / delay");
     return VTP_ERR_ARG;

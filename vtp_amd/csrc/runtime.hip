@@ -1,5 +1,6 @@
 // Error plumbing shared by every entry point of libvtp_hip.so.
 #include "common.h"
+#include "diag.h"
 #include "vtp_hip.h"
 #include <stdarg.h>
 #include <stdio.h>
@@ -37,11 +38,7 @@ __global__ __launch_bounds__(512) void cu_thief_kernel(int ticks, unsigned long 
 }
 }  // namespace vtp
 extern "C" int vtp_cu_thief(int nwg, int ticks, void* out, void* stream) {
-  const char* diag = getenv("VTP_DIAG");
-  if (!(diag && diag[0] == '1')) {
-    vtp::set_error("vtp_cu_thief: diagnostics hooks need VTP_DIAG=1 in the environment");
-    return VTP_ERR_ARG;
-  }
+  if (!vtp::diag_allowed("vtp_cu_thief")) return VTP_ERR_ARG;
   if (nwg < 1 || nwg > 256 || ticks < 0 || ticks > 100000000) {
     vtp::set_error("vtp_cu_thief: 1..256 workgroups, 0..1 s");
     return VTP_ERR_ARG;
