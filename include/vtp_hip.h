@@ -685,6 +685,44 @@ int vtp_maxpool2_f32(const float* x, float* y, int B, int H, int W, int C, void*
 int vtp_lpips_head_f32(const float* f, const float* w, double* part, int n, int HW, int C, void* stream);
 int vtp_lpips_finalize_f32(const double* part, float* val, int n, int H, int W, void* stream);
 
+/* ---- weighted k-NN classification on frozen features (knn.hip): the DINO / DINOv2 evaluation protocol (k = 10, 20, 100, 200,
+ * temperature 0.07, top-1 / top-5), restated from the papers' description; neither code base is a reference of this project, so
+ * parity with those programs is unpinned.  Everything in exact fp32, no float atomics, no host synchronisation.
+ *
+ * vtp_knn_topk merges the chunk X f32 [N, D] (row stride ldx) of the bank, whose row 0 has the global index index_base, into the
+ * running neighbour lists of the queries Q f32 [B, D] (row stride ldq).  Replaces torch.matmul over bank chunks + topk + cat +
+ * topk; the [B, N] similarities are never written (except to sims_out).
+ *   s[b, n] = the fmaf chain over k = 0 .. D-1 ascending, the bits of element [b, n] of vtp_gemm_nt_f32(Q, X) with the plain
+ *   epilogue, whatever B, N, the chunk or the grid (no split of k).
+ *   State, in and out: sims f32 [B, K] and idx int64 [B, K], contiguous: per query the first K bank rows seen so far under
+ *   (similarity descending, global index ascending), in that order.  An empty entry is (-inf, -1) and empties come last: start
+ *   from all-empty lists; there is no separate count.  The result is identical bit for bit whatever the chunking of the bank,
+ *   the number of splits, B or the launch geometry.  Inputs are finite by contract; a NaN similarity is never selected.
+ *   splits: the bank chunk is cut into that many slices, one workgroup per (slice, 128 queries); 0 picks a count that fills the
+ *   chip.  workspace holds the slices' partial lists: vtp_knn_workspace_bytes(B, K, splits) bytes (for splits = 0: enough for
+ *   whatever the heuristic picks at this B), 16-byte aligned; contents need not be kept between calls.
+ *   sims_out (may be NULL): f32 [B, N], row stride lds: the chunk's similarities, for tests.
+ *   Limits (those of vtp_gemm_nt_f32): D a positive multiple of 8, ldq and ldx multiples of 4, Q and X 16-byte aligned;
+ *   1 <= K <= 256, 0 <= splits <= 1024.
+ * vtp_knn_workspace_bytes returns the bytes, or -1 (bad argument, or more than 2 GiB: pass fewer queries per call).
+ *
+ * vtp_knn_vote turns the lists into statistics in one launch.  Replaces softmax + one_hot + mul + cumsum + topk(5) + eq + sum.
+ *   labels int32 [n_total]: the class of every bank row; a neighbour whose index or label is out of range votes for nothing.
+ *   targets int64 [B]; ks: HOST int[nk], ascending, 1 <= ks[m] <= K, nk <= 8; inv_T = 1 / temperature; num_classes >= 5.
+ *   w_j = expf((s_j - s_0) * inv_T) (the protocol's softmax over the list without its common denominator: the same ranking);
+ *   the score of class c at k = the sum of w_j over the first k neighbours with label c, added in neighbour order; a class without
+ *   a neighbour has score 0.  Classes are ranked by (score descending, class index ascending), so a target with score 0 comes
+ *   behind every positive class and every score-0 class of lower index.
+ *   counts    int64 [nk, 3] += (top-1 hits, top-5 hits, rows), integer atomics only                       -- may be NULL
+ *   rank_out  int32 [B, nk]   the number of classes ranked before the target; num_classes for a target outside
+ *                             [0, num_classes), which is a miss at every k and still a row                 -- may be NULL
+ *   pred_out  int32 [B, nk, 5] the five best classes                                                      -- may be NULL */
+int vtp_knn_workspace_bytes(int B, int K, int splits);
+int vtp_knn_topk(const float* Q, int ldq, const float* X, int ldx, long index_base, int B, int N, int D, int K, float* sims,
+                 long* idx, void* workspace, long workspace_bytes, int splits, float* sims_out, int lds, void* stream);
+int vtp_knn_vote(const float* sims, const long* idx, const int* labels, long n_total, const long* targets, const int* ks, int nk,
+                 float inv_T, int num_classes, int B, int K, long* counts, int* rank_out, int* pred_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

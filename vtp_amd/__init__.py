@@ -1,7 +1,7 @@
 """vtp_amd -- MI355X-native (gfx950 / CDNA4) VTP training hot path.
 
 Public surface mirrors the reference (`from vtp.models.vtp_hf import VTPConfig, VTPModel`):
-    from vtp_amd import VTPConfig, VTPModel, VTPTrainer, LinearProbe, ZeroShot, ReconEval, MultiCrop, Preprocess, FID,
+    from vtp_amd import VTPConfig, VTPModel, VTPTrainer, LinearProbe, ZeroShot, Knn, ReconEval, MultiCrop, Preprocess, FID,
     InceptionFeatures, FrechetStats, frechet_distance
 Everything below the Python API is hand-written HIP in libvtp_hip.so (C ABI: include/vtp_hip.h)."""
 from .config import VTPConfig  # noqa: F401
@@ -32,6 +32,9 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name == "ZeroShot":
         from .zeroshot import ZeroShot
         return ZeroShot
+    if name == "Knn":
+        from .knn import Knn
+        return Knn
     if name == "ReconEval":
         from .recon_eval import ReconEval
         return ReconEval

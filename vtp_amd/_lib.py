@@ -163,6 +163,12 @@ SIGNATURES = {
     "vtp_maxpool2_f32": [_P, _P, _I, _I, _I, _I, _P],  # x y B H W C stream
     "vtp_lpips_head_f32": [_P, _P, _P, _I, _I, _I, _P],  # f w part n HW C stream
     "vtp_lpips_finalize_f32": [_P, _P, _I, _I, _I, _P],  # part val n H W stream
+    # weighted k-NN evaluation (knn.hip)
+    "vtp_knn_workspace_bytes": [_I, _I, _I],  # B K splits -> bytes, or -1
+    # Q ldq X ldx index_base B N D K sims idx workspace workspace_bytes splits sims_out lds stream
+    "vtp_knn_topk": [_P, _I, _P, _I, _L, _I, _I, _I, _I, _P, _P, _P, _L, _I, _P, _I, _P],
+    # sims idx labels n_total targets ks nk inv_T num_classes B K counts rank_out pred_out stream
+    "vtp_knn_vote": [_P, _P, _P, _L, _P, _P, _I, _F, _I, _I, _I, _P, _P, _P, _P],
 }
 
 _lib = None

@@ -836,6 +836,65 @@ def zs_topk(f, wt, targets, scale, B, C, D, counts, per_class=None, rank=None, p
                                    _p(rank), _p(pred), _p(logits), 0 if logits is None else logits.stride(0), _s()), "vtp_zs_topk")
 
 
+KNN_MAX_K = 256
+
+
+def knn_workspace_bytes(B, K, splits=0):
+    """bytes of workspace knn_topk needs for B queries, lists of K and that many splits (0: whatever the heuristic may pick at this
+    B); ValueError for arguments the kernel refuses or a workspace above 2 GiB"""
+    n = _lib_().vtp_knn_workspace_bytes(B, K, splits)
+    if n < 0:
+        raise ValueError(_lib_().vtp_last_error().decode(errors="replace"))
+    return n
+
+
+def knn_topk(q, x, index_base, K, sims, idx, workspace, splits=0, sims_out=None):
+    """merges the bank chunk x f32 [N, D] (global index of its row 0: index_base) into the neighbour lists sims f32 [B, K] / idx
+    int64 [B, K] of the queries q f32 [B, D]: the first K bank rows by (similarity descending, index ascending), empty entries
+    (-inf, -1) last; similarities with the bits of gemm_nt_f32(q, x).  q and x may be column slices of wider matrices (row strides
+    from the tensors).  workspace: uint8, knn_workspace_bytes(B, K, splits) bytes.  sims_out f32 [B, N]: the chunk's similarities."""
+    for name, t, dt in (("q", q, torch.float32), ("x", x, torch.float32), ("sims", sims, torch.float32), ("idx", idx, torch.int64),
+                        ("workspace", workspace, torch.uint8), ("sims_out", sims_out, torch.float32)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dt):
+            raise ValueError(f"{name} must be a {dt} tensor, got {getattr(t, 'dtype', type(t))}")
+    _need_gpu(q=q, x=x, sims=sims, idx=idx, workspace=workspace, sims_out=sims_out)
+    if q.dim() != 2 or x.dim() != 2 or q.shape[1] != x.shape[1] or q.stride(1) != 1 or x.stride(1) != 1:
+        raise ValueError(f"q and x must be [B, D] and [N, D] with unit column stride, got {tuple(q.shape)} and {tuple(x.shape)}")
+    B, D = q.shape
+    N = x.shape[0]
+    _need(sims, "sims", torch.float32, (B, K))
+    _need(idx, "idx", torch.int64, (B, K))
+    if sims_out is not None and (tuple(sims_out.shape) != (B, N) or sims_out.stride(1) != 1):
+        raise ValueError(f"sims_out must be [{B}, {N}] with unit column stride, got {tuple(sims_out.shape)}")
+    _lib.check(_lib_().vtp_knn_topk(_p(q), q.stride(0), _p(x), x.stride(0), int(index_base), B, N, D, K, _p(sims), _p(idx),
+                                    _p(workspace), workspace.numel(), splits, _p(sims_out),
+                                    0 if sims_out is None else sims_out.stride(0), _s()), "vtp_knn_topk")
+
+
+def knn_vote(sims, idx, labels, targets, ks, inv_T, num_classes, counts=None, rank_out=None, pred_out=None):
+    """the weighted vote over neighbour lists sims f32 [B, K] / idx int64 [B, K] (knn_topk): labels int32 [N_total] of the bank rows,
+    targets int64 [B], ks ascending ints <= K (at most 8): counts int64 [nk, 3] += (top-1 hits, top-5 hits, rows); optional
+    rank_out int32 [B, nk] (classes ranked before the target; num_classes for a target out of range), pred_out int32 [B, nk, 5]"""
+    import ctypes
+    _need(sims, "sims", torch.float32, dims=2)
+    B, K = sims.shape
+    ks = [int(k) for k in ks]
+    nk = len(ks)
+    _need(idx, "idx", torch.int64, (B, K))
+    _need(labels, "labels", torch.int32, dims=1)
+    _need(targets, "targets", torch.int64, (B,))
+    if counts is not None:
+        _need(counts, "counts", torch.int64, (nk, 3))
+    if rank_out is not None:
+        _need(rank_out, "rank_out", torch.int32, (B, nk))
+    if pred_out is not None:
+        _need(pred_out, "pred_out", torch.int32, (B, nk, 5))
+    _need_gpu(sims=sims, idx=idx, labels=labels, targets=targets, counts=counts, rank_out=rank_out, pred_out=pred_out)
+    ks_c = (ctypes.c_int * max(nk, 1))(*ks)
+    _lib.check(_lib_().vtp_knn_vote(_p(sims), _p(idx), _p(labels), labels.numel(), _p(targets), ctypes.cast(ks_c, ctypes.c_void_p), nk,
+                                    inv_T, num_classes, B, K, _p(counts), _p(rank_out), _p(pred_out), _s()), "vtp_knn_vote")
+
+
 def recon_scratch_size(B, H, W):
     """number of f64 elements the scratch of recon_metrics / recon_finalize must hold for a [B, 3, H, W] batch (two per tile of
     window positions); ValueError for a shape the kernels refuse (H or W below 11, W % 4 != 0, B < 1)"""
