@@ -723,6 +723,40 @@ int vtp_knn_topk(const float* Q, int ldq, const float* X, int ldx, long index_ba
 int vtp_knn_vote(const float* sims, const long* idx, const int* labels, long n_total, const long* targets, const int* ks, int nk,
                  float inv_T, int num_classes, int B, int K, long* counts, int* rank_out, int* pred_out, void* stream);
 
+/* ---- k-NN manifold precision / recall of two feature sets (precision_recall.hip): the estimate of Kynkaanniemi et al. 2019 that
+ * the ADM evaluation suite reports with k = 3, restated from the paper's description; neither ADM's evaluator nor the authors' code
+ * is a reference of this project, so parity with those programs is unpinned.  Everything in exact fp32, no float atomics, no host
+ * synchronisation.
+ *   s(a, b)  = the fmaf chain over k = 0 .. D-1 ascending, the bits of vtp_gemm_nt_f32 with the plain epilogue; n(a) = s(a, a).
+ *   d2(a, b) = max((n(a) + n(b)) - 2 s(a, b), 0): symmetric bit for bit, exactly 0 for two identical rows.  A NaN stays a NaN, is
+ *   never selected and never a hit; inputs are finite by contract.
+ *
+ * vtp_pr_sqnorm: out[i] = n(row i of X f32 [N, D], row stride ldx).
+ *
+ * vtp_pr_knn_dist merges the chunk X f32 [N, D] (row stride ldx, norms xn f32 [N]) of a bank into dist f32 [B, 8], contiguous and
+ * 16-byte aligned: per query of Q f32 [B, D] (row stride ldq, norms qn f32 [B]) the 8 smallest d2 seen so far, ascending, +inf for
+ * an empty entry.  dist is in/out: fill it with +inf before the first chunk.  The radius of a row for neighbourhood size k <= 8 is
+ * column k - 1 of its list against its own set.  Only values are kept: the result is identical bit for bit whatever the chunking
+ * of the bank, the number of splits, B or the launch geometry.
+ *   query_base >= 0 turns self-exclusion on: the pair with query_base + b == index_base + n is skipped (by index, not by value: a
+ *   duplicate row elsewhere counts, at distance 0); query_base = -1 turns it off (two different sets).  index_base >= 0.
+ *   splits: the chunk is cut into that many slices, one workgroup per (slice, 128 queries); 0 picks a count that fills the chip.
+ *   workspace holds the slices' partial lists: vtp_pr_workspace_bytes(B, splits) = splits * B * 32 bytes (for splits = 0: enough
+ *   for whatever the heuristic picks at this B), 16-byte aligned; contents need not be kept between calls.
+ *   d2_out (may be NULL): f32 [B, N], row stride ldo: the chunk's distances (the excluded pair included), for tests.
+ *   Limits: D a positive multiple of 8, ldq and ldx multiples of 4 and >= D, Q and X 16-byte aligned; 0 <= splits <= 1024.
+ * vtp_pr_workspace_bytes returns the bytes, or -1 (bad argument, or more than 2 GiB: pass fewer queries per call).
+ *
+ * vtp_pr_cover: hits int32 [B]: hits[b] += the number of rows n of the chunk with d2(q_b, x_n) <= r2[n] (r2 f32 [N]: the squared
+ * radii of the bank rows).  One integer atomic per query and workgroup: exact and order-free.  Limits as vtp_pr_knn_dist. */
+int vtp_pr_workspace_bytes(int B, int splits);
+int vtp_pr_sqnorm(const float* X, int ldx, int N, int D, float* out, void* stream);
+int vtp_pr_knn_dist(const float* Q, int ldq, const float* qn, const float* X, int ldx, const float* xn, long query_base,
+                    long index_base, int B, int N, int D, float* dist, void* workspace, long workspace_bytes, int splits,
+                    float* d2_out, int ldo, void* stream);
+int vtp_pr_cover(const float* Q, int ldq, const float* qn, const float* X, int ldx, const float* xn, const float* r2, int B, int N,
+                 int D, int* hits, int splits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

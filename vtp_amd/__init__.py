@@ -2,7 +2,7 @@
 
 Public surface mirrors the reference (`from vtp.models.vtp_hf import VTPConfig, VTPModel`):
     from vtp_amd import VTPConfig, VTPModel, VTPTrainer, LinearProbe, ZeroShot, Knn, ReconEval, MultiCrop, Preprocess, FID,
-    InceptionFeatures, FrechetStats, frechet_distance
+    InceptionFeatures, FrechetStats, frechet_distance, PrecisionRecall
 Everything below the Python API is hand-written HIP in libvtp_hip.so (C ABI: include/vtp_hip.h)."""
 from .config import VTPConfig  # noqa: F401
 
@@ -47,4 +47,7 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name in ("InceptionFeatures", "FrechetStats", "FID", "frechet_distance"):
         from . import fid
         return getattr(fid, name)
+    if name == "PrecisionRecall":
+        from .precision_recall import PrecisionRecall
+        return PrecisionRecall
     raise AttributeError(name)

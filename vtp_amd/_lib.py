@@ -169,6 +169,12 @@ SIGNATURES = {
     "vtp_knn_topk": [_P, _I, _P, _I, _L, _I, _I, _I, _I, _P, _P, _P, _L, _I, _P, _I, _P],
     # sims idx labels n_total targets ks nk inv_T num_classes B K counts rank_out pred_out stream
     "vtp_knn_vote": [_P, _P, _P, _L, _P, _P, _I, _F, _I, _I, _I, _P, _P, _P, _P],
+    # k-NN manifold precision / recall (precision_recall.hip)
+    "vtp_pr_workspace_bytes": [_I, _I],  # B splits -> bytes, or -1
+    "vtp_pr_sqnorm": [_P, _I, _I, _I, _P, _P],  # X ldx N D out stream
+    # Q ldq qn X ldx xn query_base index_base B N D dist workspace workspace_bytes splits d2_out ldo stream
+    "vtp_pr_knn_dist": [_P, _I, _P, _P, _I, _P, _L, _L, _I, _I, _I, _P, _P, _L, _I, _P, _I, _P],
+    "vtp_pr_cover": [_P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _P, _I, _P],  # Q ldq qn X ldx xn r2 B N D hits splits stream
 }
 
 _lib = None

@@ -7,12 +7,12 @@
 //
 // vtp_knn_topk, first kernel (knn_topk_kernel).  Grid = bank splits x row blocks of 128 queries; 256 threads.
 //   Tile.  A workgroup walks its slice of the chunk in tiles of 128 bank rows and computes S^T[bank row][query] = X Q^T with the
-//     main loop of vtp_gemm_nt_f32 (fp32.hip): 128 x 128 tile, four waves in 2 x 2, each 2 x 2 MFMA tiles of 32 x 32 on
-//     v_mfma_f32_32x32x2_f32, K slabs of 16 staged through LDS transposed ([k][row]), two buffers, the loads of slab t + 1 in flight
-//     under the MFMAs of slab t.  The bank rows are the A operand and the queries the B operand, so a query sits on a lane and its
-//     candidates are accumulator registers.  A product is commutative and the chain runs over k = 0 .. D-1 ascending with no split
-//     of k: s[b, n] has the bits of element [b, n] of vtp_gemm_nt_f32(Q, X) with the plain epilogue, whatever B, N, the tile, the
-//     chunk or the grid.
+//     main loop of vtp_gemm_nt_f32 (tile_f32.h, shared with precision_recall.hip): 128 x 128 tile, four waves in 2 x 2, each
+//     2 x 2 MFMA tiles of 32 x 32 on v_mfma_f32_32x32x2_f32, K slabs of 16 staged through LDS transposed ([k][row]), two buffers,
+//     the loads of slab t + 1 in flight under the MFMAs of slab t.  The bank rows are the A operand and the queries the B
+//     operand, so a query sits on a lane and its candidates are accumulator registers.  A product is commutative and the chain
+//     runs over k = 0 .. D-1 ascending with no split of k: s[b, n] has the bits of element [b, n] of vtp_gemm_nt_f32(Q, X) with
+//     the plain epilogue, whatever B, N, the tile, the chunk or the grid.
 //   Selection.  Every query of the row block has a threshold in LDS: its current K-th neighbour (similarity, global index), or
 //     (-inf, -1) while the list is short.  A lane compares its 64 accumulator values with the thresholds of its two queries; a
 //     survivor is appended to the query's LDS buffer (32 entries: similarity and row within the chunk; the slot comes from an LDS
@@ -42,6 +42,7 @@
 //   Only integer atomics touch the counters.
 #include "common.h"
 #include "mfma_f32.h"
+#include "tile_f32.h"
 #include "vtp_hip.h"
 
 #include <limits.h>
@@ -49,10 +50,7 @@
 
 namespace vtp {
 
-constexpr int KN_BM = 128, KN_BQ = 128, KN_BK = 16;  // bank rows per tile, queries per row block, K slab
-constexpr int KN_KQ = KN_BK / 4;                     // 16-byte loads per tile row and slab
-constexpr int KN_IT = KN_KQ / 2;                     // loads per thread, operand and slab
-constexpr int KN_LD = 128 + 16 / KN_KQ;              // as GF_LD (fp32.hip): the k groups of a wave's write land on disjoint banks
+constexpr int KN_BM = TF_BM, KN_BQ = TF_BQ, KN_BK = TF_BK, KN_KQ = TF_KQ, KN_IT = TF_IT, KN_LD = TF_LD;  // the tile loop: tile_f32.h
 constexpr int KN_CAP = 32;                           // buffered survivors per query between two merges
 constexpr int KN_MAXK = 256;
 constexpr int KN_MERGE_FLAT = 8;  // up to this many splits one merge stage
@@ -197,8 +195,6 @@ __global__ __launch_bounds__(256, 2) void knn_topk_kernel(const KnnArgs g) {
     lr[it] = r;
     bp[it] = r < nq ? g.Q + (size_t)(q0 + r) * g.ldq + 4 * kq : nullptr;
   }
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-  const int nslab = (g.D + KN_BK - 1) / KN_BK;
   const int tile_lo = split * g.tiles_per_split;
   const int tile_hi = tile_lo + g.tiles_per_split < g.tiles ? tile_lo + g.tiles_per_split : g.tiles;
 
@@ -207,55 +203,8 @@ __global__ __launch_bounds__(256, 2) void knn_topk_kernel(const KnnArgs g) {
     const float* ap[KN_IT];
 #pragma unroll
     for (int it = 0; it < KN_IT; ++it) ap[it] = n0 + lr[it] < g.N ? g.X + (size_t)(n0 + lr[it]) * g.ldx + 4 * kq : nullptr;
-    f32x4 ar[KN_IT], br[KN_IT];
-    auto load_slab = [&](int k0) {
-      const bool kin = k0 + 4 * kq < g.D;
-#pragma unroll
-      for (int it = 0; it < KN_IT; ++it) {
-        ar[it] = (ap[it] && kin) ? *(const f32x4*)(ap[it] + k0) : zero4;
-        br[it] = (bp[it] && kin) ? *(const f32x4*)(bp[it] + k0) : zero4;
-      }
-    };
-    auto store_slab = [&](int buf) {
-#pragma unroll
-      for (int it = 0; it < KN_IT; ++it)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          L.As[buf][4 * kq + e][lr[it]] = ar[it][e];
-          L.Bs[buf][4 * kq + e][lr[it]] = br[it][e];
-        }
-    };
     f32x16 acc[2][2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int v = 0; v < 2; ++v)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[u][v][r] = 0.f;
-
-    load_slab(0);
-    store_slab(0);
-    __syncthreads();
-    for (int t = 0; t < nslab; ++t) {
-      const int buf = t & 1;
-      if (t + 1 < nslab) load_slab((t + 1) * KN_BK);  // in flight under the MFMAs below
-#pragma unroll
-      for (int kk = 0; kk < KN_BK / 2; ++kk) {
-        const int k = 2 * kk + half;
-        float a[2], b[2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          a[u] = L.As[buf][k][wm * 64 + u * 32 + j];
-          b[u] = L.Bs[buf][k][wn * 64 + u * 32 + j];
-        }
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-          for (int v = 0; v < 2; ++v) acc[u][v] = mfma32(a[u], b[v], acc[u][v]);
-      }
-      if (t + 1 < nslab) store_slab(buf ^ 1);
-      __syncthreads();
-    }
+    tile_f32_product(ap, bp, lr, kq, g.D, L.As, L.Bs, wm, wn, j, half, acc);
 
     // lane = query wn * 64 + v * 32 + j, register = bank row wm * 64 + u * 32 + acc_row(r, half) of the tile
     if (g.sims_out) {

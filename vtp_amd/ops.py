@@ -895,6 +895,79 @@ def knn_vote(sims, idx, labels, targets, ks, inv_T, num_classes, counts=None, ra
                                     inv_T, num_classes, B, K, _p(counts), _p(rank_out), _p(pred_out), _s()), "vtp_knn_vote")
 
 
+PR_MAX_K = 8
+
+
+def _pr_rows(**tensors):
+    """f32 [n, D] matrices with unit column stride (row strides go to the kernel); the device is checked by _need_gpu, last"""
+    for name, t in tensors.items():
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise ValueError(f"{name} must be a {torch.float32} tensor, got {getattr(t, 'dtype', type(t))}")
+        if t.dim() != 2 or t.stride(1) != 1:
+            raise ValueError(f"{name} must be [n, D] with unit column stride, got {tuple(t.shape)} with strides {t.stride()}")
+
+
+def pr_workspace_bytes(B, splits=0):
+    """bytes of workspace pr_knn_dist needs for B queries and that many splits (0: whatever the heuristic may pick at this B):
+    splits * B * 32; ValueError for arguments the kernel refuses or a workspace above 2 GiB"""
+    n = _lib_().vtp_pr_workspace_bytes(B, splits)
+    if n < 0:
+        raise ValueError(_lib_().vtp_last_error().decode(errors="replace"))
+    return n
+
+
+def pr_sqnorm(x, out):
+    """out f32 [N] = the squared norm of every row of x f32 [N, D]: one fmaf chain over k ascending, the bits of the diagonal of
+    gemm_nt_f32(x, x).  x may be a column slice of a wider matrix."""
+    _pr_rows(x=x)
+    N, D = x.shape
+    _need(out, "out", torch.float32, (N,))
+    _need_gpu(x=x, out=out)
+    _lib.check(_lib_().vtp_pr_sqnorm(_p(x), x.stride(0), N, D, _p(out), _s()), "vtp_pr_sqnorm")
+
+
+def pr_knn_dist(q, qn, x, xn, dist, workspace, query_base=-1, index_base=0, splits=0, d2_out=None):
+    """merges the bank chunk x f32 [N, D] (norms xn f32 [N], global index of its row 0: index_base) into dist f32 [B, PR_MAX_K]: per
+    query of q f32 [B, D] (norms qn f32 [B]) the 8 smallest d2 = max(qn + xn - 2 q.x, 0) seen so far, ascending, +inf for an empty
+    entry (fill dist with +inf before the first chunk).  query_base >= 0: the pair with query_base + b == index_base + n is skipped
+    (a set against itself); -1: no exclusion.  q and x may be column slices of wider matrices.  workspace: uint8,
+    pr_workspace_bytes(B, splits) bytes.  d2_out f32 [B, N]: the chunk's distances."""
+    _pr_rows(q=q, x=x)
+    if q.shape[1] != x.shape[1]:
+        raise ValueError(f"q and x must be [B, D] and [N, D], got {tuple(q.shape)} and {tuple(x.shape)}")
+    B, D = q.shape
+    N = x.shape[0]
+    _need(qn, "qn", torch.float32, (B,))
+    _need(xn, "xn", torch.float32, (N,))
+    _need(dist, "dist", torch.float32, (B, PR_MAX_K))
+    _need(workspace, "workspace", torch.uint8, dims=1)
+    if d2_out is not None:
+        _pr_rows(d2_out=d2_out)
+        if tuple(d2_out.shape) != (B, N):
+            raise ValueError(f"d2_out must be [{B}, {N}], got {tuple(d2_out.shape)}")
+    _need_gpu(q=q, qn=qn, x=x, xn=xn, dist=dist, workspace=workspace, d2_out=d2_out)
+    _lib.check(_lib_().vtp_pr_knn_dist(_p(q), q.stride(0), _p(qn), _p(x), x.stride(0), _p(xn), int(query_base), int(index_base), B, N, D,
+                                       _p(dist), _p(workspace), workspace.numel(), splits, _p(d2_out),
+                                       0 if d2_out is None else d2_out.stride(0), _s()), "vtp_pr_knn_dist")
+
+
+def pr_cover(q, qn, x, xn, r2, hits, splits=0):
+    """hits int32 [B] += per query of q f32 [B, D] (norms qn) the number of rows n of the bank chunk x f32 [N, D] (norms xn) with
+    d2(q_b, x_n) <= r2[n] (r2 f32 [N]: the squared radii of the bank rows); integer atomics only"""
+    _pr_rows(q=q, x=x)
+    if q.shape[1] != x.shape[1]:
+        raise ValueError(f"q and x must be [B, D] and [N, D], got {tuple(q.shape)} and {tuple(x.shape)}")
+    B, D = q.shape
+    N = x.shape[0]
+    _need(qn, "qn", torch.float32, (B,))
+    _need(xn, "xn", torch.float32, (N,))
+    _need(r2, "r2", torch.float32, (N,))
+    _need(hits, "hits", torch.int32, (B,))
+    _need_gpu(q=q, qn=qn, x=x, xn=xn, r2=r2, hits=hits)
+    _lib.check(_lib_().vtp_pr_cover(_p(q), q.stride(0), _p(qn), _p(x), x.stride(0), _p(xn), _p(r2), B, N, D, _p(hits), splits, _s()),
+               "vtp_pr_cover")
+
+
 def recon_scratch_size(B, H, W):
     """number of f64 elements the scratch of recon_metrics / recon_finalize must hold for a [B, 3, H, W] batch (two per tile of
     window positions); ValueError for a shape the kernels refuse (H or W below 11, W % 4 != 0, B < 1)"""
