@@ -80,7 +80,7 @@ def test_maxpool_fwd_bwd():
     F.max_pool2d(yr, 2, 2).backward(dp)
     ref = ((yr.grad + tap).to(BF).float()) * (y > 0)
     got = _unstack(dys, NB, H, W, C)
-    assert float((got - ref).abs().max()) <= 2.0 ** -7 * float(ref.abs().max())
+    assert torch.equal(got, ref)  # routing, one fp32 add and one rounding to bf16: reproducible value for value
 
 
 @pytest.fixture(scope="module")

@@ -188,7 +188,10 @@ __global__ __launch_bounds__(256) void lpips_tap_kernel(const bf16* __restrict__
     float d = 0.f, tsum = 0.f, dn[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      const float df = fa[e] * inv0 - ft[e] * inv1;
+      // two statements: in one expression the compiler contracts the subtraction into fma(fa, inv0, -(ft * inv1)), which for
+      // f0 == f1 leaves the rounding error of fa * inv0 in place of 0 -- a noise gradient and an atomic where there is no distance
+      const float n0 = fa[e] * inv0, n1 = ft[e] * inv1;
+      const float df = n0 - n1;
       d += ww[e] * df * df;
       dn[e] = 2.f * gscale * ww[e] * df;
       tsum += dn[e] * fa[e];
