@@ -757,6 +757,28 @@ int vtp_pr_knn_dist(const float* Q, int ldq, const float* qn, const float* X, in
 int vtp_pr_cover(const float* Q, int ldq, const float* qn, const float* X, int ldx, const float* xn, const float* r2, int B, int N,
                  int D, int* hits, int splits, void* stream);
 
+/* ---- Inception Score (inception_score.hip): Salimans et al. 2016, the figure the ADM evaluation suite reports beside FID, restated
+ * from the papers' definition; neither ADM's evaluator nor its TF graph is a reference of this project, so parity with that program
+ * is unpinned.  With p_i = softmax(logits_i) and the rows cut in order into splits of split_size rows:
+ *   KL_s = (1 / n_s) sum_i sum_c p_ic (log p_ic - log m_c), m_c = (1 / n_s) sum_i p_ic, IS = mean_s exp(KL_s), accumulated as
+ *   H_s = sum_i h_i with h_i = sum_c p_ic (l_ic - lse_i) and S_sc = sum_i p_ic:  KL_s = (H_s - sum_c S_sc log(S_sc / n_s)) / n_s.
+ * Everything in fp64, no float atomics, no host synchronisation.
+ *
+ * vtp_is_rows: logits f32 [B, ldl], of which the columns c < C count (the buffer may be wider: the padded columns of a GEMM) ->
+ *   p f64 [B, ldp] (columns c < C written) and h f64 [B].  Per row: m = max_c l_c, j the first column that holds it, d_c = l_c - m
+ *   (exact), z = sum_{c != j} exp(d_c), Z = 1 + z, log Z = log1p(z) (a row certain of one class keeps its log Z), p_c = exp(d_c) / Z,
+ *   h = sum_c p_c (d_c - log Z) (= sum_c p_c (l_c - lse) with lse = m + log Z; never p log p: a p_c that underflows to 0 contributes
+ *   0).  One wave per row, lanes stride over c, lane sums in column order, a fixed butterfly: the bits of a row depend on that row
+ *   alone, not on B or on its place in the batch.  Logits are finite by contract.
+ * vtp_is_accum: row i of the update (p f64 [B, ldp], h f64 [B]) is global row row_base + i and belongs to slot
+ *   (row_base + i) / split_size of state f64 [n_slots, 1 + C], a slot being [H_s | S_s0 .. S_s,C-1].  The thread that owns an
+ *   element of a slot adds its rows in ascending order (the scheme of vtp_fid_accum): any split of the same rows over updates
+ *   leaves the same bits, an update that straddles a split boundary included.  The row counts n_s are the caller's to keep.
+ *   split_size >= 1 (LONG_MAX: one split), row_base >= 0, the last row's slot < n_slots, at most 65535 slots per update. */
+int vtp_is_rows(const float* logits, int ldl, int B, int C, double* p, int ldp, double* h, void* stream);
+int vtp_is_accum(const double* p, int ldp, const double* h, long row_base, long split_size, int B, int C, double* state, int n_slots,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,7 @@
 
 Public surface mirrors the reference (`from vtp.models.vtp_hf import VTPConfig, VTPModel`):
     from vtp_amd import VTPConfig, VTPModel, VTPTrainer, LinearProbe, ZeroShot, Knn, ReconEval, MultiCrop, Preprocess, FID,
-    InceptionFeatures, FrechetStats, frechet_distance, PrecisionRecall
+    InceptionFeatures, FrechetStats, frechet_distance, PrecisionRecall, InceptionScore, GenEval
 Everything below the Python API is hand-written HIP in libvtp_hip.so (C ABI: include/vtp_hip.h)."""
 from .config import VTPConfig  # noqa: F401
 
@@ -50,4 +50,10 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name == "PrecisionRecall":
         from .precision_recall import PrecisionRecall
         return PrecisionRecall
+    if name in ("InceptionScore", "inception_score_from_sums"):
+        from . import inception_score
+        return getattr(inception_score, name)
+    if name == "GenEval":
+        from .gen_eval import GenEval
+        return GenEval
     raise AttributeError(name)

@@ -175,6 +175,9 @@ SIGNATURES = {
     # Q ldq qn X ldx xn query_base index_base B N D dist workspace workspace_bytes splits d2_out ldo stream
     "vtp_pr_knn_dist": [_P, _I, _P, _P, _I, _P, _L, _L, _I, _I, _I, _P, _P, _L, _I, _P, _I, _P],
     "vtp_pr_cover": [_P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _P, _I, _P],  # Q ldq qn X ldx xn r2 B N D hits splits stream
+    # Inception Score (inception_score.hip)
+    "vtp_is_rows": [_P, _I, _I, _I, _P, _I, _P, _P],  # logits ldl B C p ldp h stream
+    "vtp_is_accum": [_P, _I, _P, _L, _L, _I, _I, _P, _I, _P],  # p ldp h row_base split_size B C state n_slots stream
 }
 
 _lib = None

@@ -16,7 +16,8 @@ description of those classes and is not pinned against the package.
 Compute (csrc/fid.hip): activations are NHWC f32; each of the 94 convolutions is one vtp_conv2d_f32 launch with BatchNorm folded
 into its weight and bias (fp64 on the host, once per weight version) and writes straight into its channel slice of the block's
 concatenated output.  Every output element is one fmaf chain, so features do not depend on the batch an image came in.  There is
-no CPU path and no host synchronisation in forward()."""
+no CPU path and no host synchronisation in forward().  forward_taps() is the same pass plus the spatial features of sFID (one more
+launch); vtp_amd/gen_eval.py builds the generation metrics on it."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional, Tuple
@@ -92,6 +93,7 @@ def _inception_convs() -> List[Tuple[str, int, int, Tuple[int, int], int, Tuple[
 
 INCEPTION_CONVS = _inception_convs()
 MIN_SIDE = 75  # the smallest input that leaves one pixel in front of the global pool
+TAP_CONV, TAP_CHANNELS = "Mixed_6d.branch1x1", 7  # forward_taps: the spatial features of sFID
 
 
 def fold_conv_bn(w, gamma, beta, mean, var, eps: float = BN_EPS):
@@ -148,6 +150,7 @@ class InceptionFeatures(nn.Module):
         self._prepped = None
         self._w: Dict[str, torch.Tensor] = {}
         self._b: Dict[str, torch.Tensor] = {}
+        self._tap_w: Optional[torch.Tensor] = None
 
     # ------------------------------------------------------------------------------------------------ weights
     def _block(self, name: str) -> nn.Module:
@@ -201,6 +204,9 @@ class InceptionFeatures(nn.Module):
                                 blk.bn.running_mean.detach().cpu(), blk.bn.running_var.detach().cpu())
             self._w[name] = w.permute(0, 2, 3, 1).contiguous().to(F32).to(dev)
             self._b[name] = b.to(F32).to(dev)
+        # the sFID tap (forward_taps): the first TAP_CHANNELS filters of Mixed_6d.branch1x1 as they are, no BatchNorm folded in
+        w = self._block(TAP_CONV).conv.weight.detach()[:TAP_CHANNELS]
+        self._tap_w = w.cpu().permute(0, 2, 3, 1).contiguous().to(F32).to(dev)
         self._prepped = ver
 
     # ------------------------------------------------------------------------------------------------ compute
@@ -281,6 +287,18 @@ class InceptionFeatures(nn.Module):
     @torch.no_grad()
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """x f32 [B, 3, H, W] in [0, 1] on the device -> the 2048 pool features f32 [B, 2048]"""
+        return self._run(x, False)[0]
+
+    @torch.no_grad()
+    def forward_taps(self, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """the pass of forward() with the sFID tap: (pool f32 [B, 2048], the bits forward() returns; spatial f32 [B, h, w, 7]).
+        spatial is what the ADM evaluation suite names mixed_6/conv:0[..., :7]: the raw output (no BatchNorm, no ReLU) of the first 7
+        filters of Mixed_6d.branch1x1 on the input of Mixed_6d, NHWC -- 17 x 17 x 7 = 2023 values per image at 299 x 299, flattened
+        in that order.  One more vtp_conv2d_f32 launch; the layout follows the published graph names and is not pinned against
+        that program."""
+        return self._run(x, True)
+
+    def _run(self, x: torch.Tensor, taps: bool) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         if not x.is_cuda:
             raise ValueError("x must live on the MI355X (got a CPU tensor): there is no CPU path")
         if x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1:
@@ -309,14 +327,18 @@ class InceptionFeatures(nn.Module):
         a = self._block_a("Mixed_5c", a, 64, avg)
         a = self._block_a("Mixed_5d", a, 64, avg)
         a = self._block_b("Mixed_6a", a)
+        spatial = None
         for n in ("Mixed_6b", "Mixed_6c", "Mixed_6d", "Mixed_6e"):
+            if taps and n == TAP_CONV.split(".")[0]:
+                spatial = torch.empty(B, a.shape[1], a.shape[2], TAP_CHANNELS, device=x.device, dtype=F32)
+                ops.conv2d_f32(a, self._tap_w, None, spatial, relu=False)
             a = self._block_c(n, a, avg)
         a = self._block_d("Mixed_7a", a)
         a = self._block_e("Mixed_7b", a, avg)
         a = self._block_e("Mixed_7c", a, ops.POOL_MAX if fidv else ops.POOL_AVG)
         out = torch.empty(B, FEATURE_DIM, device=x.device, dtype=F32)
         ops.global_avgpool_f32(a, out)
-        return out
+        return out, spatial
 
 
 # ---------------------------------------------------------------------------------------------------------------------- statistics

@@ -968,6 +968,38 @@ def pr_cover(q, qn, x, xn, r2, hits, splits=0):
                "vtp_pr_cover")
 
 
+IS_ONE_SPLIT = (1 << 63) - 1  # split_size of is_accum for "one split over everything"
+
+
+def is_rows(logits, C, p, h):
+    """per row of logits f32 [B, ld >= C] (unit column stride; only the columns c < C count) the softmax p f64 [B, C] and
+    h f64 [B] = sum_c p_c (l_c - lse) in fp64 (vtp_is_rows): one wave per row, a row's bits depend on that row alone"""
+    if not isinstance(logits, torch.Tensor) or logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("logits must be an f32 [B, >= C] tensor with unit column stride")
+    B = logits.shape[0]
+    if not 1 <= C <= logits.shape[1]:
+        raise ValueError(f"C must be 1 .. {logits.shape[1]} (the width of logits), got {C}")
+    _need(p, "p", torch.float64, (B, C))
+    _need(h, "h", torch.float64, (B,))
+    _need_gpu(logits=logits, p=p, h=h)
+    _lib.check(_lib_().vtp_is_rows(_p(logits), logits.stride(0), B, C, _p(p), p.stride(0), _p(h), _s()), "vtp_is_rows")
+
+
+def is_accum(p, h, state, row_base, split_size=None):
+    """adds the rows of p f64 [B, C] and h f64 [B], global rows row_base .. row_base + B - 1, to the slots [H | S_0 .. S_C-1] of
+    state f64 [n_slots, 1 + C]: row r goes to slot r // split_size (None: slot 0), rows in order, one thread per element
+    (vtp_is_accum): any split of the same rows over calls leaves the same bits"""
+    _need(p, "p", torch.float64, dims=2)
+    B, C = p.shape
+    _need(h, "h", torch.float64, (B,))
+    _need(state, "state", torch.float64, dims=2)
+    if state.shape[1] != 1 + C:
+        raise ValueError(f"state must be [n_slots, 1 + C = {1 + C}], got {tuple(state.shape)}")
+    _need_gpu(p=p, h=h, state=state)
+    _lib.check(_lib_().vtp_is_accum(_p(p), p.stride(0), _p(h), int(row_base), IS_ONE_SPLIT if split_size is None else int(split_size),
+                                    B, C, _p(state), state.shape[0], _s()), "vtp_is_accum")
+
+
 def recon_scratch_size(B, H, W):
     """number of f64 elements the scratch of recon_metrics / recon_finalize must hold for a [B, 3, H, W] batch (two per tile of
     window positions); ValueError for a shape the kernels refuse (H or W below 11, W % 4 != 0, B < 1)"""
