@@ -757,6 +757,41 @@ int vtp_pr_knn_dist(const float* Q, int ldq, const float* qn, const float* X, in
 int vtp_pr_cover(const float* Q, int ldq, const float* qn, const float* X, int ldx, const float* xn, const float* r2, int B, int N,
                  int D, int* hits, int splits, void* stream);
 
+/* ---- Cross-modal retrieval on the CLIP heads (retrieval.hip): image -> text and text -> image recall@K on a captioned set, the
+ * evaluation the CLIP paper reports on Flickr30k and MSCOCO-5k, restated from the papers' description; neither CLIP_benchmark nor
+ * OpenCLIP is a reference of this project, so parity with those programs is unpinned.  Everything in exact fp32, integer atomics
+ * only, no host synchronisation.
+ *   s(i, j) = the fmaf chain over k = 0 .. D-1 ascending, the bits of element [i, j] of vtp_gemm_nt_f32(Q, X) with the plain
+ *   epilogue (no split of k).  Gallery rows are ordered by (similarity descending, gallery index ascending), a total order.
+ *   (s*, j*) = the first ground-truth row of a query under that order; rank = #{j : s(i, j) > s*} + #{j < j* : s(i, j) == s*}.  No
+ *   ground-truth row is ever counted.  A query without ground truth has (s*, j*) = (-inf, -1) and rank = the gallery size: a miss
+ *   at every K and still a row.  Inputs are finite by contract; a NaN similarity never beats anything and is never chosen as s*.
+ *
+ * vtp_retr_best: per query of Q f32 [B, D] (row stride ldq) the best of its ground-truth rows in the WHOLE gallery X f32
+ * [n_total, D] (row stride ldx): best_s f32 [B], best_j int64 [B].  The lists are a CSR: gt_ptr int32 [B + 1], ascending, values in
+ * [0, nnz], the list of query b being gt_idx[gt_ptr[b] .. gt_ptr[b + 1]); gt_idx int64 [nnz] holds gallery rows in any order; an
+ * index outside [0, n_total) is ignored; an empty list gives (-inf, -1).  Among equal similarities the lower row wins.  Work is cut
+ * over (query, list entry) pairs.  Limits: D a positive multiple of 8, ldq and ldx multiples of 4 and >= D, Q and X 16-byte
+ * aligned, n_total <= 2^31 - 1 (a rank is an int32).
+ *
+ * vtp_retr_rank: one sweep of the chunk X f32 [N, D] of the gallery, whose row 0 has the global index index_base, over the queries:
+ * beats int32 [B] += the number of chunk rows strictly before (best_s[b], best_j[b]) under the order above; best_j[b] == -1 counts
+ * every row of the chunk.  beats is in/out: zero it before the first chunk; after the last one it is the rank.  One integer atomic
+ * per query and workgroup: the result is identical whatever the chunking of the gallery, the number of splits, B or the grid.
+ *   splits: the chunk is cut into that many slices, one workgroup per (slice, 128 queries); 0 picks a count that fills the chip.
+ *   sims_out (may be NULL): f32 [B, N], row stride lds: the chunk's similarities, for tests.
+ *   Limits (those of vtp_knn_topk): D a positive multiple of 8, ldq and ldx multiples of 4 and >= D, Q and X 16-byte aligned,
+ *   0 <= splits <= 1024; index_base + N <= 2^31 - 1.
+ *
+ * vtp_retr_count: counts int64 [nk + 1]: counts[m] += #{b : beats[b] < ks[m]}, counts[nk] += B.  ks: HOST int[nk], positive and
+ * ascending, nk <= 8.  rank (may be NULL): int32, rank[rank_offset + b] = beats[b]: the ranks of a whole evaluation stay on the
+ * device. */
+int vtp_retr_best(const float* Q, int ldq, const float* X, int ldx, long n_total, const int* gt_ptr, const long* gt_idx, int nnz, int B,
+                  int D, float* best_s, long* best_j, void* stream);
+int vtp_retr_rank(const float* Q, int ldq, const float* X, int ldx, long index_base, int B, int N, int D, const float* best_s,
+                  const long* best_j, int* beats, int splits, float* sims_out, int lds, void* stream);
+int vtp_retr_count(const int* beats, int B, const int* ks, int nk, long* counts, int* rank, long rank_offset, void* stream);
+
 /* ---- Inception Score (inception_score.hip): Salimans et al. 2016, the figure the ADM evaluation suite reports beside FID, restated
  * from the papers' definition; neither ADM's evaluator nor its TF graph is a reference of this project, so parity with that program
  * is unpinned.  With p_i = softmax(logits_i) and the rows cut in order into splits of split_size rows:

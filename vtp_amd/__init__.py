@@ -2,7 +2,7 @@
 
 Public surface mirrors the reference (`from vtp.models.vtp_hf import VTPConfig, VTPModel`):
     from vtp_amd import VTPConfig, VTPModel, VTPTrainer, LinearProbe, ZeroShot, Knn, ReconEval, MultiCrop, Preprocess, FID,
-    InceptionFeatures, FrechetStats, frechet_distance, PrecisionRecall, InceptionScore, GenEval
+    InceptionFeatures, FrechetStats, frechet_distance, PrecisionRecall, InceptionScore, GenEval, Retrieval
 Everything below the Python API is hand-written HIP in libvtp_hip.so (C ABI: include/vtp_hip.h)."""
 from .config import VTPConfig  # noqa: F401
 
@@ -56,4 +56,7 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name == "GenEval":
         from .gen_eval import GenEval
         return GenEval
+    if name == "Retrieval":
+        from .retrieval import Retrieval
+        return Retrieval
     raise AttributeError(name)

@@ -175,6 +175,11 @@ SIGNATURES = {
     # Q ldq qn X ldx xn query_base index_base B N D dist workspace workspace_bytes splits d2_out ldo stream
     "vtp_pr_knn_dist": [_P, _I, _P, _P, _I, _P, _L, _L, _I, _I, _I, _P, _P, _L, _I, _P, _I, _P],
     "vtp_pr_cover": [_P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _P, _I, _P],  # Q ldq qn X ldx xn r2 B N D hits splits stream
+    # image-text retrieval (retrieval.hip)
+    "vtp_retr_best": [_P, _I, _P, _I, _L, _P, _P, _I, _I, _I, _P, _P, _P],  # Q ldq X ldx n_total gt_ptr gt_idx nnz B D best_s best_j stream
+    # Q ldq X ldx index_base B N D best_s best_j beats splits sims_out lds stream
+    "vtp_retr_rank": [_P, _I, _P, _I, _L, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P],
+    "vtp_retr_count": [_P, _I, _P, _I, _P, _P, _L, _P],  # beats B ks nk counts rank rank_offset stream
     # Inception Score (inception_score.hip)
     "vtp_is_rows": [_P, _I, _I, _I, _P, _I, _P, _P],  # logits ldl B C p ldp h stream
     "vtp_is_accum": [_P, _I, _P, _L, _L, _I, _I, _P, _I, _P],  # p ldp h row_base split_size B C state n_slots stream

@@ -1,4 +1,4 @@
-// The 128 x 128 exact-fp32 tile product that knn.hip and precision_recall.hip share: the main loop of vtp_gemm_nt_f32 (fp32.hip) with
+// The 128 x 128 exact-fp32 tile product that knn.hip, precision_recall.hip and retrieval.hip share: the main loop of vtp_gemm_nt_f32 (fp32.hip) with
 // the bank rows as the A operand and the queries as the B operand, so a query sits on a lane and its candidates are accumulator
 // registers.  256 threads, four waves in 2 x 2 (wm, wn), each 2 x 2 MFMA tiles of 32 x 32 on v_mfma_f32_32x32x2_f32, K slabs of 16
 // staged through LDS transposed ([k][row]), two buffers, the loads of slab t + 1 in flight under the MFMAs of slab t.  The chain of

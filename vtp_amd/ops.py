@@ -968,6 +968,69 @@ def pr_cover(q, qn, x, xn, r2, hits, splits=0):
                "vtp_pr_cover")
 
 
+RETR_MAX_KS = 8  # recall levels per retr_count call
+
+
+def retr_best(q, x, gt_ptr, gt_idx, best_s, best_j):
+    """per query of q f32 [B, D] the best of its ground-truth rows in the whole gallery x f32 [N, D]: best_s f32 [B] and best_j int64
+    [B], the first under (similarity descending, row ascending); (-inf, -1) for an empty list.  The lists are a CSR: gt_ptr int32
+    [B + 1] ascending, gt_idx int64 [nnz] gallery rows (one outside [0, N) is ignored).  Similarities with the bits of
+    gemm_nt_f32(q, x).  q and x may be column slices of wider matrices."""
+    _pr_rows(q=q, x=x)
+    if q.shape[1] != x.shape[1]:
+        raise ValueError(f"q and x must be [B, D] and [N, D], got {tuple(q.shape)} and {tuple(x.shape)}")
+    B, D = q.shape
+    N = x.shape[0]
+    _need(gt_ptr, "gt_ptr", torch.int32, (B + 1,))
+    _need(gt_idx, "gt_idx", torch.int64, dims=1)
+    _need(best_s, "best_s", torch.float32, (B,))
+    _need(best_j, "best_j", torch.int64, (B,))
+    _need_gpu(q=q, x=x, gt_ptr=gt_ptr, gt_idx=gt_idx, best_s=best_s, best_j=best_j)
+    nnz = gt_idx.numel()
+    _lib.check(_lib_().vtp_retr_best(_p(q), q.stride(0), _p(x), x.stride(0), N, _p(gt_ptr), _p(gt_idx) if nnz else None, nnz, B, D,
+                                     _p(best_s), _p(best_j), _s()), "vtp_retr_best")
+
+
+def retr_rank(q, x, index_base, best_s, best_j, beats, splits=0, sims_out=None):
+    """beats int32 [B] += per query of q f32 [B, D] the number of rows of the gallery chunk x f32 [N, D] (global index of its row 0:
+    index_base) strictly before (best_s[b], best_j[b]) under (similarity descending, global row ascending); best_j[b] == -1 counts
+    every row.  Integer atomics only.  sims_out f32 [B, N]: the chunk's similarities (the bits of gemm_nt_f32(q, x))."""
+    _pr_rows(q=q, x=x)
+    if q.shape[1] != x.shape[1]:
+        raise ValueError(f"q and x must be [B, D] and [N, D], got {tuple(q.shape)} and {tuple(x.shape)}")
+    B, D = q.shape
+    N = x.shape[0]
+    _need(best_s, "best_s", torch.float32, (B,))
+    _need(best_j, "best_j", torch.int64, (B,))
+    _need(beats, "beats", torch.int32, (B,))
+    if sims_out is not None:
+        _pr_rows(sims_out=sims_out)
+        if tuple(sims_out.shape) != (B, N):
+            raise ValueError(f"sims_out must be [{B}, {N}], got {tuple(sims_out.shape)}")
+    _need_gpu(q=q, x=x, best_s=best_s, best_j=best_j, beats=beats, sims_out=sims_out)
+    _lib.check(_lib_().vtp_retr_rank(_p(q), q.stride(0), _p(x), x.stride(0), int(index_base), B, N, D, _p(best_s), _p(best_j), _p(beats),
+                                     splits, _p(sims_out), 0 if sims_out is None else sims_out.stride(0), _s()), "vtp_retr_rank")
+
+
+def retr_count(beats, ks, counts, rank=None, rank_offset=0):
+    """counts int64 [nk + 1] += (#{beats < k} for k of ks, rows); ks ascending positive ints (at most 8).  rank int32 [>= rank_offset
+    + B]: rank[rank_offset + b] = beats[b]."""
+    import ctypes
+    _need(beats, "beats", torch.int32, dims=1)
+    B = beats.shape[0]
+    ks = [int(k) for k in ks]
+    nk = len(ks)
+    _need(counts, "counts", torch.int64, (nk + 1,))
+    if rank is not None:
+        _need(rank, "rank", torch.int32, dims=1)
+        if rank_offset < 0 or rank_offset + B > rank.shape[0]:
+            raise ValueError(f"rank holds {rank.shape[0]} entries, rows {rank_offset} .. {rank_offset + B} asked for")
+    _need_gpu(beats=beats, counts=counts, rank=rank)
+    ks_c = (ctypes.c_int * max(nk, 1))(*ks)
+    _lib.check(_lib_().vtp_retr_count(_p(beats), B, ctypes.cast(ks_c, ctypes.c_void_p), nk, _p(counts), _p(rank), int(rank_offset), _s()),
+               "vtp_retr_count")
+
+
 IS_ONE_SPLIT = (1 << 63) - 1  # split_size of is_accum for "one split over everything"
 
 
