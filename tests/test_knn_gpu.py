@@ -156,6 +156,20 @@ def test_chunks_layouts_and_batches_give_the_same_lists():
         assert same((s128[:B], i128[:B]), want), splits
 
 
+def test_a_split_without_a_tile_changes_nothing():
+    """81 tiles in one row block: the heuristic (splits=0) takes 9 splits of 9 tiles -- it drops the split that 10 splits of 9 tiles
+    leave without a tile -- and a forced count of 10 launches that empty split.  Both give the lists of a single split."""
+    _gpu()
+    case = (5, 10300, 8, 5, 4.0, 2)
+    K = 10
+    q, x, _, _ = clustered_case(*case)
+    S, order = oracle(case)
+    want = (torch.gather(S, 1, order[:, :K]), order[:, :K])
+    qd, xd = q.to(DEV), x.to(DEV)
+    for splits in (0, 1, 10):
+        assert same(run_topk(qd, [(xd, 0)], K, splits), want), splits
+
+
 # ---------------------------------------------------------------------------------------------------------------- 3. ties
 def test_exact_ties_follow_the_bank_index():
     _gpu()

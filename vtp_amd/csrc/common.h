@@ -42,6 +42,19 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+__device__ __forceinline__ int wave_sum_int(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// The total order (value descending, index ascending) of every ranking here (torch.topk with the lower index first among equals):
+// a strictly before b.  An empty entry (-inf, -1) is before nothing and every finite value is before it; a NaN is before nothing
+// and nothing is before it.  I is the index type of the caller: int where the indices are 32-bit, long for global rows.
+template <typename I>
+__device__ __forceinline__ bool before(float av, I ai, float bv, I bi) {
+  return av > bv || (av == bv && ai < bi);
+}
 
 // block-wide sum for blocks of NW waves; `red` is NW floats of LDS.  All threads get the result.
 template <int NW>
@@ -108,6 +121,6 @@ __device__ __forceinline__ float quick_gelu_grad(float x) {
 }
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
-
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }  // the address of a 16-byte load or store
 
 }  // namespace vtp

@@ -342,7 +342,6 @@ __global__ __launch_bounds__(256) void fid_accum_kernel(const float* __restrict_
 
 using namespace vtp;
 
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 static const long INT_LIMIT = 2147483647L;
 
 static int conv2d_f32(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin, int Cout, int kh, int kw,

@@ -7,6 +7,7 @@
 //                     atomics, one wave per 32 query rows; a query's result depends on its own sequence alone.
 #include "common.h"
 #include "mfma_f32.h"
+#include "tile_f32.h"
 #include "vtp_hip.h"
 
 #include <math.h>
@@ -14,22 +15,14 @@
 namespace vtp {
 
 // ---------------------------------------------------------------------------------------------------------------- GEMM
-// Workgroup = 128 x 128 output tile, four waves in 2 x 2, each 2 x 2 MFMA tiles of 32 x 32 (four independent accumulators keep the
-// matrix pipe at its issue rate).  K runs in slabs of 16: the slab's A and W rows go to LDS transposed ([k][row], so the lanes of an
-// MFMA operand read consecutive words), two LDS buffers; the global loads of slab t + 1 are issued before the MFMAs of slab t and
-// written to the other buffer behind them -- one barrier per slab.  Rows / columns past M / N and k past K load zeros (K % 4 == 0
-// keeps a 16-byte load inside its row; a zero product leaves the chain's value unchanged).
+// Workgroup = 128 x 128 output tile, computed by tile_f32_product (tile_f32.h: the one main loop, which the bank sweeps of knn.hip,
+// precision_recall.hip and retrieval.hip call as well): four waves in 2 x 2, each 2 x 2 MFMA tiles of 32 x 32, K in slabs of 16
+// through two transposed LDS buffers, one barrier per slab.  The kernel chooses the rows: A rows m0 .. and W rows n0 .. of the
+// tile, null (read as zeros) past M / N.
 // SwiGLU: the tile's 128 W rows are 64 rows of w1 and the same 64 rows of w2, laid out so that a wave's tile column 0 is x1 and its
 // tile column 1 is x2 of the same hidden columns: the epilogue pairs acc[.][0] with acc[.][1] lane by lane and the block covers 64
 // hidden columns.
-#ifndef VTP_F32_BK
-#define VTP_F32_BK 16
-#endif
-constexpr int GF_BM = 128, GF_BN = 128, GF_BK = VTP_F32_BK;
-constexpr int GF_KQ = GF_BK / 4;         // 16-byte loads per tile row and slab
-constexpr int GF_IT = GF_KQ / 2;         // loads per thread, operand and slab: 128 rows x GF_KQ / 256 threads
-constexpr int GF_LD = 128 + 16 / GF_KQ;  // 4 * GF_LD % 32 == 64 / GF_KQ: the GF_KQ k groups of a wave's write land on disjoint banks twice over
-static_assert(GF_BK == 16 || GF_BK == 32, "K slab of 16 or 32");
+constexpr int GF_BM = TF_BM, GF_BN = TF_BQ;  // the output tile; the K slab and the LDS layout are those of tile_f32.h
 
 enum { GF_PLAIN = 0, GF_RESID = 1, GF_SWIGLU = 2, GF_GELU = 3, GF_QUICK_GELU = 4 };
 
@@ -44,21 +37,21 @@ __device__ __forceinline__ float silu_exact(float x) { return x / (1.f + expf(-x
 
 template <int EPI>
 __global__ __launch_bounds__(256) void gemm_nt_f32_kernel(const GemmF32Args g) {
-  __shared__ float As[2][GF_BK][GF_LD];
-  __shared__ float Bs[2][GF_BK][GF_LD];
+  __shared__ float As[2][TF_BK][TF_LD];
+  __shared__ float Bs[2][TF_BK][TF_LD];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1, j = lane & 31, half = lane >> 5;
   const int m0 = blockIdx.y * GF_BM;
   const int n0 = blockIdx.x * (EPI == GF_SWIGLU ? GF_BN / 2 : GF_BN);
 
-  // the GF_IT 16-byte loads of this thread per operand and slab: tile row lr[it], k offset 4 * kq
-  const int kq = tid & (GF_KQ - 1);
-  const float* ap[GF_IT];
-  const float* bp[GF_IT];
-  int lr[GF_IT];
+  // the TF_IT 16-byte loads of this thread per operand and slab: tile row lr[it], k offset 4 * kq
+  const int kq = tid & (TF_KQ - 1);
+  const float* ap[TF_IT];
+  const float* bp[TF_IT];
+  int lr[TF_IT];
 #pragma unroll
-  for (int it = 0; it < GF_IT; ++it) {
-    const int r = tid / GF_KQ + (256 / GF_KQ) * it;
+  for (int it = 0; it < TF_IT; ++it) {
+    const int r = tid / TF_KQ + (256 / TF_KQ) * it;
     lr[it] = r;
     const int m = m0 + r;
     ap[it] = m < g.M ? g.A + (size_t)m * g.lda + 4 * kq : nullptr;
@@ -70,58 +63,8 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_kernel(const GemmF32Args g) {
       bp[it] = n < g.N ? g.W + (size_t)n * g.ldw + 4 * kq : nullptr;
     }
   }
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-  f32x4 ar[GF_IT], br[GF_IT];
-  auto load_slab = [&](int k0) {
-    const bool kin = k0 + 4 * kq < g.K;
-#pragma unroll
-    for (int it = 0; it < GF_IT; ++it) {
-      ar[it] = (ap[it] && kin) ? *(const f32x4*)(ap[it] + k0) : zero4;
-      br[it] = (bp[it] && kin) ? *(const f32x4*)(bp[it] + k0) : zero4;
-    }
-  };
-  auto store_slab = [&](int buf) {
-#pragma unroll
-    for (int it = 0; it < GF_IT; ++it)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        As[buf][4 * kq + e][lr[it]] = ar[it][e];
-        Bs[buf][4 * kq + e][lr[it]] = br[it][e];
-      }
-  };
-
   f32x16 acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-
-  const int nslab = (g.K + GF_BK - 1) / GF_BK;
-  load_slab(0);
-  store_slab(0);
-  __syncthreads();
-  for (int t = 0; t < nslab; ++t) {
-    const int buf = t & 1;
-    if (t + 1 < nslab) load_slab((t + 1) * GF_BK);  // in flight under the MFMAs below
-#pragma unroll
-    for (int kk = 0; kk < GF_BK / 2; ++kk) {
-      const int k = 2 * kk + half;
-      float a[2], b[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        a[u] = As[buf][k][wm * 64 + u * 32 + j];
-        b[u] = Bs[buf][k][wn * 64 + u * 32 + j];
-      }
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int v = 0; v < 2; ++v) acc[u][v] = mfma32(a[u], b[v], acc[u][v]);
-    }
-    if (t + 1 < nslab) store_slab(buf ^ 1);
-    __syncthreads();
-  }
+  tile_f32_product(ap, bp, lr, kq, g.K, As, Bs, wm, wn, j, half, acc);
 
   // epilogue: lane = output column, register = output row
   if (EPI == GF_SWIGLU) {
@@ -267,8 +210,6 @@ __global__ __launch_bounds__(64) void attn_fwd_f32_kernel(const float* __restric
 
 }  // namespace vtp
 using namespace vtp;
-
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 extern "C" int vtp_gemm_nt_f32(const float* A, int lda, const float* W, int ldw, const float* W2, float* C, int ldc, const float* bias,
                                const float* bias2, const float* gamma, const float* resid, int ldr, int M, int N, int K, int epi,

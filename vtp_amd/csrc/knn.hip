@@ -6,8 +6,9 @@
 //                  replaces softmax + one_hot + cumsum + topk(5) + eq + sum.
 //
 // vtp_knn_topk, first kernel (knn_topk_kernel).  Grid = bank splits x row blocks of 128 queries; 256 threads.
-//   Tile.  A workgroup walks its slice of the chunk in tiles of 128 bank rows and computes S^T[bank row][query] = X Q^T with the
-//     main loop of vtp_gemm_nt_f32 (tile_f32.h, shared with precision_recall.hip): 128 x 128 tile, four waves in 2 x 2, each
+//   Tile.  A workgroup walks its slice of the chunk in tiles of 128 bank rows (the bank sweep of tile_f32.h, the one walk that
+//     precision_recall.hip and retrieval.hip run as well) and computes S^T[bank row][query] = X Q^T with the main loop of
+//     vtp_gemm_nt_f32 itself (tile_f32_product, which fp32.hip calls too): 128 x 128 tile, four waves in 2 x 2, each
 //     2 x 2 MFMA tiles of 32 x 32 on v_mfma_f32_32x32x2_f32, K slabs of 16 staged through LDS transposed ([k][row]), two buffers,
 //     the loads of slab t + 1 in flight under the MFMAs of slab t.  The bank rows are the A operand and the queries the B
 //     operand, so a query sits on a lane and its candidates are accumulator registers.  A product is commutative and the chain
@@ -50,16 +51,10 @@
 
 namespace vtp {
 
-constexpr int KN_BM = TF_BM, KN_BQ = TF_BQ, KN_BK = TF_BK, KN_KQ = TF_KQ, KN_IT = TF_IT, KN_LD = TF_LD;  // the tile loop: tile_f32.h
-constexpr int KN_CAP = 32;                           // buffered survivors per query between two merges
+constexpr int KN_CAP = 32;  // buffered survivors per query between two merges
 constexpr int KN_MAXK = 256;
 constexpr int KN_MERGE_FLAT = 8;  // up to this many splits one merge stage
-constexpr int KN_MAX_SPLITS = 1024, KN_AUTO_SPLITS = 256, KN_AUTO_BLOCKS = 512, KN_AUTO_TILES = 8;
-
-// (similarity descending, index ascending): a strictly before b.  An empty entry (-inf, -1) is before nothing and every finite
-// similarity is before it.
-__device__ __forceinline__ bool kn_before(float as, long ai, float bs, long bi) { return as > bs || (as == bs && ai < bi); }
-__device__ __forceinline__ bool kn_before32(float as, int ai, float bs, int bi) { return as > bs || (as == bs && ai < bi); }
+constexpr int KN_MIN_TILES = 8;   // tiles a split keeps (sweep_splits): its lists are zeroed, merged through memory and folded
 
 // wave-level ordering of LDS traffic: what the lanes of this wave wrote is visible to its other lanes afterwards
 __device__ __forceinline__ void kn_wave_sync() {
@@ -69,24 +64,24 @@ __device__ __forceinline__ void kn_wave_sync() {
 }
 
 struct KnnArgs {
-  const float *Q, *X;
+  SweepArgs sw;
   float* part_s;  // [splits][B][K]
   long* part_i;   // [splits][B][K]
   float* sims_out;
   long index_base;
-  int ldq, ldx, lds, B, N, D, K, tiles, tiles_per_split;
+  int lds, K;
 };
 
 struct KnnLds {
-  float As[2][KN_BK][KN_LD];  // bank rows
-  float Bs[2][KN_BK][KN_LD];  // queries
-  float cand_s[KN_BQ][KN_CAP];
-  int cand_n[KN_BQ][KN_CAP];  // row within the chunk
-  long thr_i[KN_BQ];
+  float As[2][TF_BK][TF_LD];  // bank rows
+  float Bs[2][TF_BK][TF_LD];  // queries
+  float cand_s[TF_BQ][KN_CAP];
+  int cand_n[TF_BQ][KN_CAP];  // row within the chunk
+  long thr_i[TF_BQ];
   float ls_s[4][KN_MAXK];
   int ls_n[4][KN_MAXK];  // row within the chunk
-  float thr_s[KN_BQ];
-  int cnt[KN_BQ];
+  float thr_s[TF_BQ];
+  int cnt[TF_BQ];
 };
 
 // wave `wave` merges the buffers of its 32 queries (wave * 32 ...) into their lists.  The list of the next query is on its way
@@ -97,7 +92,7 @@ __device__ __forceinline__ void knn_merge_buffers(const KnnArgs& g, KnnLds& L, i
   auto fetch = [&](int i) {
     const int ql = wave * 32 + i;
     if (L.cnt[ql] == 0) return;  // the same for every lane; a query past B never has a survivor
-    const size_t off = ((size_t)split * g.B + (q0 + ql)) * g.K;
+    const size_t off = ((size_t)split * g.sw.B + (q0 + ql)) * g.K;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const int p = lane + 64 * t;
@@ -117,7 +112,7 @@ __device__ __forceinline__ void knn_merge_buffers(const KnnArgs& g, KnnLds& L, i
     if (i + 1 < 32) fetch(i + 1);
     const int n = L.cnt[ql] < KN_CAP ? L.cnt[ql] : KN_CAP;  // the same for every lane
     if (n == 0) continue;
-    const size_t off = ((size_t)split * g.B + (q0 + ql)) * g.K;
+    const size_t off = ((size_t)split * g.sw.B + (q0 + ql)) * g.K;
     float* ps = g.part_s + off;
     long* pi = g.part_i + off;
     // within one call every list entry is a row of this chunk: orders are compared on the 32-bit row, not the 64-bit index
@@ -137,15 +132,15 @@ __device__ __forceinline__ void knn_merge_buffers(const KnnArgs& g, KnnLds& L, i
       const float xs = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cs), c));
       const int xn = __builtin_amdgcn_readlane(cn, c);
 #pragma unroll
-      for (int t = 0; t < 4; ++t) ahead[t] += kn_before32(xs, xn, es[t], el[t]) ? 1 : 0;
-      crank += kn_before32(xs, xn, cs, cn) ? 1 : 0;
+      for (int t = 0; t < 4; ++t) ahead[t] += before(xs, xn, es[t], el[t]) ? 1 : 0;
+      crank += before(xs, xn, cs, cn) ? 1 : 0;
     }
     int cpos = g.K;
     if (lane < n) {
       int lo = 0, hi = g.K;  // the number of list elements before the survivor
       while (lo < hi) {
         const int mid = (lo + hi) >> 1;
-        if (kn_before32(L.ls_s[wave][mid], L.ls_n[wave][mid], cs, cn)) lo = mid + 1;
+        if (before(L.ls_s[wave][mid], L.ls_n[wave][mid], cs, cn)) lo = mid + 1;
         else hi = mid;
       }
       cpos = lo + crank;
@@ -172,79 +167,44 @@ __device__ __forceinline__ void knn_merge_buffers(const KnnArgs& g, KnnLds& L, i
 __global__ __launch_bounds__(256, 2) void knn_topk_kernel(const KnnArgs g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char knn_lds_raw[];
   KnnLds& L = *reinterpret_cast<KnnLds*>(knn_lds_raw);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1, j = lane & 31, half = lane >> 5;
-  const int split = blockIdx.x, q0 = blockIdx.y * KN_BQ;
-  const int nq = g.B - q0 < KN_BQ ? g.B - q0 : KN_BQ;
+  const SweepCtx c = sweep_begin(g.sw);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = c.half;
+  const int split = blockIdx.x, q0 = c.q0;
 
   // this workgroup's lists start empty
   {
-    float* ps = g.part_s + ((size_t)split * g.B + q0) * g.K;
-    long* pi = g.part_i + ((size_t)split * g.B + q0) * g.K;
-    for (int e = tid; e < nq * g.K; e += 256) ps[e] = -INFINITY, pi[e] = -1;
-    if (tid < KN_BQ) L.thr_s[tid] = -INFINITY, L.thr_i[tid] = -1, L.cnt[tid] = 0;
+    float* ps = g.part_s + ((size_t)split * g.sw.B + q0) * g.K;
+    long* pi = g.part_i + ((size_t)split * g.sw.B + q0) * g.K;
+    for (int e = tid; e < c.nq * g.K; e += 256) ps[e] = -INFINITY, pi[e] = -1;
+    if (tid < TF_BQ) L.thr_s[tid] = -INFINITY, L.thr_i[tid] = -1, L.cnt[tid] = 0;
   }
   __syncthreads();
 
-  const int kq = tid & (KN_KQ - 1);
-  const float* bp[KN_IT];
-  int lr[KN_IT];
-#pragma unroll
-  for (int it = 0; it < KN_IT; ++it) {
-    const int r = tid / KN_KQ + (256 / KN_KQ) * it;
-    lr[it] = r;
-    bp[it] = r < nq ? g.Q + (size_t)(q0 + r) * g.ldq + 4 * kq : nullptr;
-  }
-  const int tile_lo = split * g.tiles_per_split;
-  const int tile_hi = tile_lo + g.tiles_per_split < g.tiles ? tile_lo + g.tiles_per_split : g.tiles;
-
-  for (int tile = tile_lo; tile < tile_hi; ++tile) {
-    const int n0 = tile * KN_BM;
-    const float* ap[KN_IT];
-#pragma unroll
-    for (int it = 0; it < KN_IT; ++it) ap[it] = n0 + lr[it] < g.N ? g.X + (size_t)(n0 + lr[it]) * g.ldx + 4 * kq : nullptr;
+  for (int tile = c.tile_lo; tile < c.tile_hi; ++tile) {
     f32x16 acc[2][2];
-    tile_f32_product(ap, bp, lr, kq, g.D, L.As, L.Bs, wm, wn, j, half, acc);
+    sweep_tile(g.sw, c, tile, L.As, L.Bs, acc);
+    const int n0 = tile * TF_BM + c.wm * 64;  // the first bank row of this wave's part of the tile
 
-    // lane = query wn * 64 + v * 32 + j, register = bank row wm * 64 + u * 32 + acc_row(r, half) of the tile
-    if (g.sims_out) {
-#pragma unroll
-      for (int v = 0; v < 2; ++v) {
-        const int ql = wn * 64 + v * 32 + j;
-        if (ql >= nq) continue;
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int n = n0 + wm * 64 + u * 32 + acc_row(r, half);
-            if (n < g.N) g.sims_out[(size_t)(q0 + ql) * g.lds + n] = acc[u][v][r];
-          }
-      }
-    }
+    if (g.sims_out)
+      sweep_visit(g.sw, c, tile, acc, [&](int, int, int, int ql, int row, float s) { g.sims_out[(size_t)(q0 + ql) * g.lds + n0 + row] = s; });
 
     // bit (u * 2 + v) * 16 + r: the value is inside the chunk and the batch and has not been decided yet
     unsigned long long pend = 0;
-#pragma unroll
-    for (int v = 0; v < 2; ++v)
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if (wn * 64 + v * 32 + j < nq && n0 + wm * 64 + u * 32 + acc_row(r, half) < g.N) pend |= 1ull << ((u * 2 + v) * 16 + r);
-    const bool last = tile + 1 == tile_hi;
+    sweep_visit(g.sw, c, tile, acc, [&](int u, int v, int r, int, int, float) { pend |= 1ull << ((u * 2 + v) * 16 + r); });
+    const bool last = tile + 1 == c.tile_hi;
     for (;;) {
-      // what is behind its query's threshold is decided for good: the threshold only rises
+      // what is behind its query's threshold is decided for good: the threshold only rises.  Every value is compared, inside
+      // the chunk or not (`pend` knows): the thresholds are read again on every turn, so this loop is not a sweep_visit
       unsigned long long pass = 0;
 #pragma unroll
       for (int v = 0; v < 2; ++v) {
-        const int ql = wn * 64 + v * 32 + j;
-        const float ts = L.thr_s[ql];
-        const long ti = L.thr_i[ql] - g.index_base - n0 - wm * 64;  // in rows of this wave's part of the tile
+        const float ts = L.thr_s[c.query(v)];
+        const long ti = L.thr_i[c.query(v)] - g.index_base - n0;  // in rows of this wave's part of the tile
 #pragma unroll
         for (int u = 0; u < 2; ++u)
 #pragma unroll
           for (int r = 0; r < 16; ++r)
-            if (kn_before(acc[u][v][r], u * 32 + acc_row(r, half), ts, ti)) pass |= 1ull << ((u * 2 + v) * 16 + r);
+            if (before<long>(acc[u][v][r], u * 32 + acc_row(r, half), ts, ti)) pass |= 1ull << ((u * 2 + v) * 16 + r);
       }
       pend &= pass;
       // the survivors, one at a time (rare once the lists are full): the register is picked by a select chain
@@ -252,18 +212,18 @@ __global__ __launch_bounds__(256, 2) void knn_topk_kernel(const KnnArgs g) {
 #pragma unroll 1
       for (unsigned long long todo = pend; todo; todo &= todo - 1) {
         const int bit = __builtin_ctzll(todo);
-        const int ql = wn * 64 + ((bit >> 4) & 1) * 32 + j;
+        const int ql = c.query((bit >> 4) & 1);
         if (L.cnt[ql] >= KN_CAP) {  // full already: wait for the merge
           full = true;
           continue;
         }
         float s = 0.f;
 #pragma unroll
-        for (int c = 0; c < 64; ++c) s = bit == c ? acc[c >> 5][(c >> 4) & 1][c & 15] : s;
+        for (int e = 0; e < 64; ++e) s = bit == e ? acc[e >> 5][(e >> 4) & 1][e & 15] : s;
         const int slot = atomicAdd(&L.cnt[ql], 1);
         if (slot < KN_CAP) {
           L.cand_s[ql][slot] = s;
-          L.cand_n[ql][slot] = n0 + wm * 64 + (bit >> 5) * 32 + acc_row(bit & 15, half);
+          L.cand_n[ql][slot] = n0 + (bit >> 5) * 32 + acc_row(bit & 15, half);
           pend &= ~(1ull << bit);
         } else {
           full = true;  // stays pending: the merge below makes room and raises the threshold
@@ -306,14 +266,14 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(float* dst_s, long* dst_
       int lo = 0, hi = K;
       while (lo < hi) {
         const int mid = (lo + hi) >> 1;
-        if (kn_before(bs[mid], bi[mid], xs, xi)) lo = mid + 1;
+        if (before(bs[mid], bi[mid], xs, xi)) lo = mid + 1;
         else hi = mid;
       }
       px = t + lo;
       lo = 0, hi = K;
       while (lo < hi) {
         const int mid = (lo + hi) >> 1;
-        if (!kn_before(ys, yi, as[mid], ai[mid])) lo = mid + 1;
+        if (!before(ys, yi, as[mid], ai[mid])) lo = mid + 1;
         else hi = mid;
       }
       py = t + lo;
@@ -343,15 +303,7 @@ struct KnnVoteArgs {
   float inv_T;
 };
 
-__device__ __forceinline__ int kn_wave_sum_int(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// class order: score descending, lower class index first among equals
-__device__ __forceinline__ bool kv_before(float as, int ac, float bs, int bc) { return as > bs || (as == bs && ac < bc); }
-
+// class order: before() on (score, class index) -- score descending, lower class index first among equals
 __global__ __launch_bounds__(64) void knn_vote_kernel(const KnnVoteArgs g) {
   __shared__ int lab_s[KN_MAXK];
   __shared__ float w_s[KN_MAXK];
@@ -408,11 +360,11 @@ __global__ __launch_bounds__(64) void knn_vote_kernel(const KnnVoteArgs g) {
     int ahead = 0, below = 0;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-      ahead += (act[t] && kv_before(score[t], lab[t], st, tgt)) ? 1 : 0;
+      ahead += (act[t] && before(score[t], lab[t], st, tgt)) ? 1 : 0;
       below += (act[t] && lab[t] < tgt) ? 1 : 0;
     }
-    ahead = kn_wave_sum_int(ahead);
-    below = kn_wave_sum_int(below);
+    ahead = wave_sum_int(ahead);
+    below = wave_sum_int(below);
     // at score 0 every class without a neighbour and with a lower index is ranked before the target as well
     const int rank = tgt < 0 ? C : ahead + (st == 0.f ? tgt - below : 0);
     if (lane == 0) {
@@ -434,12 +386,12 @@ __global__ __launch_bounds__(64) void knn_vote_kernel(const KnnVoteArgs g) {
         int mc = INT_MAX;  // INT_MAX: nothing found
 #pragma unroll
         for (int t = 0; t < 4; ++t)
-          if (act[t] && kv_before(pv, pc, score[t], lab[t]) && (mc == INT_MAX || kv_before(score[t], lab[t], mv, mc))) mv = score[t], mc = lab[t];
+          if (act[t] && before(pv, pc, score[t], lab[t]) && (mc == INT_MAX || before(score[t], lab[t], mv, mc))) mv = score[t], mc = lab[t];
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
           const float xv = __shfl_xor(mv, o, 64);
           const int xc = __shfl_xor(mc, o, 64);
-          if (xc != INT_MAX && (mc == INT_MAX || kv_before(xv, xc, mv, mc))) mv = xv, mc = xc;
+          if (xc != INT_MAX && (mc == INT_MAX || before(xv, xc, mv, mc))) mv = xv, mc = xc;
         }
         if (mc == INT_MAX || mv == 0.f) {  // an unseen class may come first
           for (; unseen < C; ++unseen) {
@@ -448,7 +400,7 @@ __global__ __launch_bounds__(64) void knn_vote_kernel(const KnnVoteArgs g) {
             for (int t = 0; t < 4; ++t) seen = seen || (act[t] && lab[t] == unseen);
             if (!__any(seen ? 1 : 0)) break;
           }
-          if (unseen < C && (mc == INT_MAX || !kv_before(mv, mc, 0.f, unseen))) mv = 0.f, mc = unseen++;
+          if (unseen < C && (mc == INT_MAX || !before(mv, mc, 0.f, unseen))) mv = 0.f, mc = unseen++;
         }
         if (lane == 0) g.pred_out[((size_t)b * g.nk + m) * 5 + q] = mc == INT_MAX ? -1 : mc;
         pv = mc == INT_MAX ? -INFINITY : mv, pc = mc;
@@ -462,26 +414,10 @@ __global__ __launch_bounds__(64) void knn_vote_kernel(const KnnVoteArgs g) {
 
 using namespace vtp;
 
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// the split count of a call: the forced one, or enough workgroups to fill the chip twice as long as a split keeps 8 tiles
-static int knn_splits(int B, int N, int splits) {
-  if (splits > 0) return splits;
-  const int rb = cdiv(B, KN_BQ), tiles = cdiv(N, KN_BM);
-  int s = cdiv(KN_AUTO_BLOCKS, rb);
-  if (s > KN_AUTO_SPLITS) s = KN_AUTO_SPLITS;
-  if (s > tiles / KN_AUTO_TILES) s = tiles / KN_AUTO_TILES;
-  return s < 1 ? 1 : s;
-}
-
 extern "C" int vtp_knn_workspace_bytes(int B, int K, int splits) {
-  VTP_REQUIRE(B >= 1 && K >= 1 && K <= KN_MAXK && splits >= 0 && splits <= KN_MAX_SPLITS,
+  VTP_REQUIRE(B >= 1 && K >= 1 && K <= KN_MAXK && splits >= 0 && splits <= SWEEP_MAX_SPLITS,
               "vtp_knn_workspace_bytes: need B >= 1, 1 <= K <= 256, 0 <= splits <= 1024 (B=%d K=%d splits=%d)", B, K, splits);
-  int s = splits;
-  if (s == 0) {  // the most the heuristic takes for this B, whatever N
-    s = cdiv(KN_AUTO_BLOCKS, cdiv(B, KN_BQ));
-    if (s > KN_AUTO_SPLITS) s = KN_AUTO_SPLITS;
-  }
+  const int s = sweep_max_splits(B, splits);
   const long bytes = (long)s * B * K * 12;
   VTP_REQUIRE(bytes <= INT_MAX, "vtp_knn_workspace_bytes: the workspace of B=%d K=%d splits=%d exceeds 2 GiB: pass fewer queries per call", B, K, s);
   return (int)bytes;
@@ -490,34 +426,28 @@ extern "C" int vtp_knn_workspace_bytes(int B, int K, int splits) {
 extern "C" int vtp_knn_topk(const float* Q, int ldq, const float* X, int ldx, long index_base, int B, int N, int D, int K, float* sims,
                             long* idx, void* workspace, long workspace_bytes, int splits, float* sims_out, int lds, void* stream) {
   VTP_REQUIRE(Q && X && sims && idx && workspace, "vtp_knn_topk: null pointer (Q, X, sims, idx, workspace)");
-  VTP_REQUIRE(B >= 1 && N >= 1 && D >= 8 && D % 8 == 0, "vtp_knn_topk: need B, N >= 1 and D a positive multiple of 8 (B=%d N=%d D=%d)", B, N, D);
   VTP_REQUIRE(K >= 1 && K <= KN_MAXK, "vtp_knn_topk: need 1 <= K <= 256 (K=%d)", K);
-  VTP_REQUIRE(ldq >= D && ldx >= D && ldq % 4 == 0 && ldx % 4 == 0,
-              "vtp_knn_topk: leading dimensions must cover the rows, ldq and ldx multiples of 4 (ldq=%d ldx=%d)", ldq, ldx);
-  VTP_REQUIRE(aligned16(Q) && aligned16(X) && aligned16(workspace), "vtp_knn_topk: Q, X and workspace must be 16-byte aligned");
+  KnnArgs g;
+  dim3 grid;
+  if (sweep_prepare("vtp_knn_topk", Q, ldq, X, ldx, B, N, D, splits, KN_MIN_TILES, g.sw, grid) != VTP_OK) return VTP_ERR_ARG;
+  VTP_REQUIRE(aligned16(workspace), "vtp_knn_topk: workspace must be 16-byte aligned");
   VTP_REQUIRE(index_base >= 0 && index_base <= LONG_MAX - N, "vtp_knn_topk: index_base must be non-negative (index_base=%ld)", index_base);
-  VTP_REQUIRE(splits >= 0 && splits <= KN_MAX_SPLITS, "vtp_knn_topk: 0 <= splits <= 1024 (splits=%d)", splits);
   VTP_REQUIRE(!sims_out || lds >= N, "vtp_knn_topk: sims_out needs lds >= N (lds=%d)", lds);
-  const long rb = ((long)B + KN_BQ - 1) / KN_BQ;
-  VTP_REQUIRE(rb <= 65535, "vtp_knn_topk: B too large (B=%d)", B);
-  const int s = knn_splits(B, N, splits);
+  const int s = grid.x;
   const long need = (long)s * B * K * 12;
   VTP_REQUIRE(workspace_bytes >= need, "vtp_knn_topk: workspace of %ld bytes, %ld needed (vtp_knn_workspace_bytes)", workspace_bytes, need);
-  const int tiles = cdiv(N, KN_BM);
-  KnnArgs g;
-  g.Q = Q, g.X = X;
   g.part_i = (long*)workspace;  // the 8-byte entries first: both parts stay aligned
   g.part_s = (float*)((long*)workspace + (size_t)s * B * K);
   g.sims_out = sims_out;
   g.index_base = index_base;
-  g.ldq = ldq, g.ldx = ldx, g.lds = lds, g.B = B, g.N = N, g.D = D, g.K = K, g.tiles = tiles, g.tiles_per_split = cdiv(tiles, s);
+  g.lds = lds, g.K = K;
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute((const void*)knn_topk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(KnnLds));
     attr = true;
   }
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(knn_topk_kernel, dim3(s, (unsigned)rb), dim3(256), sizeof(KnnLds), st, g);
+  hipLaunchKernelGGL(knn_topk_kernel, grid, dim3(256), sizeof(KnnLds), st, g);
   const int rc = check_launch("knn_topk");
   if (rc != VTP_OK) return rc;
   int per = 1;  // split lists per group of the first merge stage: about sqrt(splits)

@@ -147,7 +147,6 @@ __global__ __launch_bounds__(64) void lpips_finalize_f32_kernel(const double* __
 
 using namespace vtp;
 
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 static const long INT_LIMIT = 2147483647L;
 
 extern "C" int vtp_lpips_scale_nhwc_f32(const float* x, float* y, int B, int H, int W, int Cout, const float* shift, const float* scale,

@@ -11,9 +11,9 @@
 //   contraction changes no bit).  d2 is symmetric bit for bit and two identical rows give exactly 0.  The clamp is a select, not
 //   fmaxf: a NaN stays a NaN, compares false everywhere and is never selected and never a hit; inputs are finite by contract.
 //
-// Tile loop: the one of knn_topk_kernel (knn.hip), shared with it through tile_f32.h (tile_f32_product).  Grid = bank splits x row
-//   blocks of 128 queries; 256 threads.  A workgroup walks its slice of the chunk in tiles of
-//   128 bank rows: 128 x 128 tile, four waves in 2 x 2, each 2 x 2 MFMA tiles of 32 x 32 on v_mfma_f32_32x32x2_f32, K slabs of 16
+// Tile loop: the bank sweep of tile_f32.h -- one walk (sweep_begin / sweep_tile / sweep_visit) that knn.hip and retrieval.hip run
+//   as well, around the one tile product (tile_f32_product) that is also the main loop of vtp_gemm_nt_f32.  Grid = bank splits x
+//   row blocks of 128 queries; 256 threads.  A workgroup walks its slice of the chunk in tiles of 128 bank rows: 128 x 128 tile, four waves in 2 x 2, each 2 x 2 MFMA tiles of 32 x 32 on v_mfma_f32_32x32x2_f32, K slabs of 16
 //   staged through LDS transposed ([k][row]), two buffers, the loads of slab t + 1 in flight under the MFMAs of slab t.  The bank
 //   rows are the A operand and the queries the B operand, so a query sits on a lane and its candidates are accumulator registers.
 //   The tile's 128 bank norms (and radii) go through LDS, two buffers by tile parity; a lane's two query norms stay in registers.
@@ -40,28 +40,27 @@
 
 namespace vtp {
 
-constexpr int PR_BM = TF_BM, PR_BQ = TF_BQ, PR_BK = TF_BK, PR_KQ = TF_KQ, PR_IT = TF_IT, PR_LD = TF_LD;  // the tile loop: tile_f32.h
 constexpr int PR_K = 8;                              // list length (PR_MAX_K)
-constexpr int PR_MAX_SPLITS = 1024, PR_AUTO_SPLITS = 256, PR_AUTO_BLOCKS = 512;
 constexpr int PR_NB = 64;  // rows per workgroup of pr_sqnorm_kernel, queries per workgroup of pr_fold_kernel
 
 struct PrArgs {
-  const float *Q, *X, *qn, *xn, *r2;
+  SweepArgs sw;
+  const float *qn, *xn, *r2;
   float* part;  // [splits][B][8]
   float* d2_out;
   int* hits;
   long excl;  // index_base - query_base (global bank row - global query row of an excluded pair); LONG_MIN: no exclusion
-  int ldq, ldx, ldo, B, N, D, tiles, tiles_per_split;
+  int ldo;
 };
 
 struct PrLds {
-  float As[2][PR_BK][PR_LD];  // bank rows
-  float Bs[2][PR_BK][PR_LD];  // queries
-  float xn[2][PR_BM];         // by tile parity
-  float r2[2][PR_BM];
+  float As[2][TF_BK][TF_LD];  // bank rows
+  float Bs[2][TF_BK][TF_LD];  // queries
+  float xn[2][TF_BM];         // by tile parity
+  float r2[2][TF_BM];
   union {
-    float lists[4][PR_K][PR_BQ];  // [wm * 2 + half][entry][query]
-    int cnt[4][PR_BQ];
+    float lists[4][PR_K][TF_BQ];  // [wm * 2 + half][entry][query]
+    int cnt[4][TF_BQ];
   };
 };
 
@@ -80,94 +79,63 @@ __device__ __forceinline__ void pr_insert(float (&l)[PR_K], float x) {
 
 template <bool COVER>
 __device__ __forceinline__ void pr_body(const PrArgs& g, PrLds& L) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1, j = lane & 31, half = lane >> 5;
-  const int split = blockIdx.x, q0 = blockIdx.y * PR_BQ;
-  const int nq = g.B - q0 < PR_BQ ? g.B - q0 : PR_BQ;
-
-  const int kq = tid & (PR_KQ - 1);
-  const float* bp[PR_IT];
-  int lr[PR_IT];
-#pragma unroll
-  for (int it = 0; it < PR_IT; ++it) {
-    const int r = tid / PR_KQ + (256 / PR_KQ) * it;
-    lr[it] = r;
-    bp[it] = r < nq ? g.Q + (size_t)(q0 + r) * g.ldq + 4 * kq : nullptr;
-  }
-  // this lane's two queries wn * 64 + v * 32 + j: norm, and the state of the epilogue
+  const SweepCtx c = sweep_begin(g.sw);
+  const int tid = threadIdx.x, split = blockIdx.x;
+  // this lane's two queries c.query(v): norm, and the state of the epilogue
   float qn[2], lst[2][PR_K];
   int cnt[2] = {0, 0};
 #pragma unroll
   for (int v = 0; v < 2; ++v) {
-    const int ql = wn * 64 + v * 32 + j;
-    qn[v] = ql < nq ? g.qn[q0 + ql] : 0.f;
+    const int ql = c.query(v);
+    qn[v] = ql < c.nq ? g.qn[c.q0 + ql] : 0.f;
 #pragma unroll
     for (int i = 0; i < PR_K; ++i) lst[v][i] = INFINITY;
   }
-  const int tile_lo = split * g.tiles_per_split;
-  const int tile_hi = tile_lo + g.tiles_per_split < g.tiles ? tile_lo + g.tiles_per_split : g.tiles;
 
-  for (int tile = tile_lo; tile < tile_hi; ++tile) {
-    const int n0 = tile * PR_BM, par = tile & 1;
-    const float* ap[PR_IT];
-#pragma unroll
-    for (int it = 0; it < PR_IT; ++it) ap[it] = n0 + lr[it] < g.N ? g.X + (size_t)(n0 + lr[it]) * g.ldx + 4 * kq : nullptr;
-    // the norms and radii of the tile's bank rows: read behind the barriers of tile_f32_product; the other parity may still be in use
+  for (int tile = c.tile_lo; tile < c.tile_hi; ++tile) {
+    const int n0 = tile * TF_BM, par = tile & 1;
+    // the norms and radii of the tile's bank rows: read behind the barriers of the tile product; the other parity may still be in use
     // by a wave that is in the epilogue of the tile before
-    if (tid < PR_BM) {
-      const bool in = n0 + tid < g.N;
+    if (tid < TF_BM) {
+      const bool in = n0 + tid < g.sw.N;
       L.xn[par][tid] = in ? g.xn[n0 + tid] : 0.f;
       if (COVER) L.r2[par][tid] = in ? g.r2[n0 + tid] : 0.f;
     }
     f32x16 acc[2][2];
-    tile_f32_product(ap, bp, lr, kq, g.D, L.As, L.Bs, wm, wn, j, half, acc);
+    sweep_tile(g.sw, c, tile, L.As, L.Bs, acc);
 
-    // lane = query wn * 64 + v * 32 + j, register = bank row wm * 64 + u * 32 + acc_row(r, half) of the tile
-    const int rows_left = g.N - n0 - wm * 64;  // rows of this wave's part of the tile inside the chunk
+    const int w0 = c.wm * 64;  // the first row of this wave's part of the tile
+    // the excluded pair of each query, in rows of this wave's part of the tile (-1: none here)
+    int ex[2] = {-1, -1};
+    if (!COVER && g.excl != LONG_MIN) {
 #pragma unroll
-    for (int v = 0; v < 2; ++v) {
-      const int ql = wn * 64 + v * 32 + j;
-      if (ql >= nq) continue;
-      // the excluded pair of this query, in rows of this wave's part of the tile (-1: none here)
-      int ex = -1;
-      if (!COVER && g.excl != LONG_MIN) {
-        const long e = (long)(q0 + ql) - g.excl - n0 - wm * 64;
-        ex = (e >= 0 && e < 64) ? (int)e : -1;
+      for (int v = 0; v < 2; ++v) {
+        const long e = (long)(c.q0 + c.query(v)) - g.excl - n0 - w0;
+        ex[v] = (e >= 0 && e < 64) ? (int)e : -1;
       }
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = u * 32 + acc_row(r, half);
-          if (row >= rows_left) continue;
-          float d = fmaf(-2.f, acc[u][v][r], qn[v] + L.xn[par][wm * 64 + row]);
-          d = d < 0.f ? 0.f : d;
-          if (COVER) {
-            cnt[v] += d <= L.r2[par][wm * 64 + row] ? 1 : 0;
-          } else {
-            if (g.d2_out) g.d2_out[(size_t)(q0 + ql) * g.ldo + n0 + wm * 64 + row] = d;
-            if (row != ex) pr_insert(lst[v], d);
-          }
-        }
     }
+    sweep_visit(g.sw, c, tile, acc, [&](int, int v, int, int ql, int row, float s) {
+      float d = fmaf(-2.f, s, qn[v] + L.xn[par][w0 + row]);
+      d = d < 0.f ? 0.f : d;
+      if (COVER) {
+        cnt[v] += d <= L.r2[par][w0 + row] ? 1 : 0;
+      } else {
+        if (g.d2_out) g.d2_out[(size_t)(c.q0 + ql) * g.ldo + n0 + w0 + row] = d;
+        if (row != ex[v]) pr_insert(lst[v], d);
+      }
+    });
   }
 
   // the four lane-sets of a query (wm x half) meet in LDS: `lists` / `cnt` are touched nowhere else
   if (COVER) {
-#pragma unroll
-    for (int v = 0; v < 2; ++v) L.cnt[wm * 2 + half][wn * 64 + v * 32 + j] = cnt[v];
-    __syncthreads();
-    if (tid < nq) {
-      const int c = L.cnt[0][tid] + L.cnt[1][tid] + L.cnt[2][tid] + L.cnt[3][tid];
-      if (c) atomicAdd(g.hits + q0 + tid, c);
-    }
+    sweep_add_counts(c, cnt, L.cnt, g.hits);
   } else {
 #pragma unroll
     for (int v = 0; v < 2; ++v)
 #pragma unroll
-      for (int i = 0; i < PR_K; ++i) L.lists[wm * 2 + half][i][wn * 64 + v * 32 + j] = lst[v][i];
+      for (int i = 0; i < PR_K; ++i) L.lists[c.wm * 2 + c.half][i][c.query(v)] = lst[v][i];
     __syncthreads();
-    if (tid < nq) {
+    if (tid < c.nq) {
       float m[PR_K];
 #pragma unroll
       for (int i = 0; i < PR_K; ++i) m[i] = L.lists[0][i][tid];
@@ -175,7 +143,7 @@ __device__ __forceinline__ void pr_body(const PrArgs& g, PrLds& L) {
       for (int s = 1; s < 4; ++s)
 #pragma unroll
         for (int i = 0; i < PR_K; ++i) pr_insert(m, L.lists[s][i][tid]);
-      f32x4* out = (f32x4*)(g.part + ((size_t)split * g.B + q0 + tid) * PR_K);
+      f32x4* out = (f32x4*)(g.part + ((size_t)split * g.sw.B + c.q0 + tid) * PR_K);
       out[0] = f32x4{m[0], m[1], m[2], m[3]};
       out[1] = f32x4{m[4], m[5], m[6], m[7]};
     }
@@ -249,28 +217,10 @@ __global__ __launch_bounds__(256) void pr_sqnorm_kernel(const float* X, int ldx,
 
 using namespace vtp;
 
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// the split count of a call: the forced one, or enough workgroups to fill the chip twice (two fit a CU).  Unlike vtp_knn_topk no
-// minimum of tiles per split is kept: a split costs one 16 KiB merge in LDS and a 32-byte list per query beyond its tiles, and at
-// a bank of 10 000 rows (79 tiles) a minimum of 8 tiles left two thirds of the chip idle.  Splits that would get no tile are dropped.
-static int pr_splits(int B, int N, int splits) {
-  if (splits > 0) return splits;
-  const int rb = cdiv(B, PR_BQ), tiles = cdiv(N, PR_BM);
-  int s = cdiv(PR_AUTO_BLOCKS, rb);
-  if (s > PR_AUTO_SPLITS) s = PR_AUTO_SPLITS;
-  if (s > tiles) s = tiles;
-  return cdiv(tiles, cdiv(tiles, s));
-}
-
 extern "C" int vtp_pr_workspace_bytes(int B, int splits) {
-  VTP_REQUIRE(B >= 1 && splits >= 0 && splits <= PR_MAX_SPLITS, "vtp_pr_workspace_bytes: need B >= 1, 0 <= splits <= 1024 (B=%d splits=%d)", B,
+  VTP_REQUIRE(B >= 1 && splits >= 0 && splits <= SWEEP_MAX_SPLITS, "vtp_pr_workspace_bytes: need B >= 1, 0 <= splits <= 1024 (B=%d splits=%d)", B,
               splits);
-  int s = splits;
-  if (s == 0) {  // the most the heuristic takes for this B, whatever N
-    s = cdiv(PR_AUTO_BLOCKS, cdiv(B, PR_BQ));
-    if (s > PR_AUTO_SPLITS) s = PR_AUTO_SPLITS;
-  }
+  const int s = sweep_max_splits(B, splits);
   const long bytes = (long)s * B * PR_K * 4;
   VTP_REQUIRE(bytes <= INT_MAX, "vtp_pr_workspace_bytes: the workspace of B=%d splits=%d exceeds 2 GiB: pass fewer queries per call", B, s);
   return (int)bytes;
@@ -278,45 +228,33 @@ extern "C" int vtp_pr_workspace_bytes(int B, int splits) {
 
 extern "C" int vtp_pr_sqnorm(const float* X, int ldx, int N, int D, float* out, void* stream) {
   VTP_REQUIRE(X && out, "vtp_pr_sqnorm: null pointer (X, out)");
-  VTP_REQUIRE(N >= 1 && D >= 8 && D % 8 == 0, "vtp_pr_sqnorm: need N >= 1 and D a positive multiple of 8 (N=%d D=%d)", N, D);
-  VTP_REQUIRE(ldx >= D && ldx % 4 == 0, "vtp_pr_sqnorm: the leading dimension must cover the rows, ldx a multiple of 4 (ldx=%d)", ldx);
-  VTP_REQUIRE(aligned16(X), "vtp_pr_sqnorm: X must be 16-byte aligned");
+  VTP_REQUIRE(N >= 1, "vtp_pr_sqnorm: need N >= 1 (N=%d)", N);
+  if (sweep_check_rows("vtp_pr_sqnorm", "X", "ldx", X, ldx, D) != VTP_OK) return VTP_ERR_ARG;
   hipLaunchKernelGGL(pr_sqnorm_kernel, dim3(cdiv(N, PR_NB)), dim3(256), 0, (hipStream_t)stream, X, ldx, N, D, out);
   return check_launch("pr_sqnorm");
-}
-
-// the checks the two tile kernels share; `fn` is the entry point's name
-static int pr_check_tiles(const char* fn, const float* Q, int ldq, const float* X, int ldx, int B, int N, int D, int splits) {
-  VTP_REQUIRE(B >= 1 && N >= 1 && D >= 8 && D % 8 == 0, "%s: need B, N >= 1 and D a positive multiple of 8 (B=%d N=%d D=%d)", fn, B, N, D);
-  VTP_REQUIRE(ldq >= D && ldx >= D && ldq % 4 == 0 && ldx % 4 == 0,
-              "%s: leading dimensions must cover the rows, ldq and ldx multiples of 4 (ldq=%d ldx=%d)", fn, ldq, ldx);
-  VTP_REQUIRE(aligned16(Q) && aligned16(X), "%s: Q and X must be 16-byte aligned", fn);
-  VTP_REQUIRE(splits >= 0 && splits <= PR_MAX_SPLITS, "%s: 0 <= splits <= 1024 (splits=%d)", fn, splits);
-  VTP_REQUIRE(((long)B + PR_BQ - 1) / PR_BQ <= 65535, "%s: B too large (B=%d)", fn, B);
-  return VTP_OK;
 }
 
 extern "C" int vtp_pr_knn_dist(const float* Q, int ldq, const float* qn, const float* X, int ldx, const float* xn, long query_base,
                                long index_base, int B, int N, int D, float* dist, void* workspace, long workspace_bytes, int splits,
                                float* d2_out, int ldo, void* stream) {
   VTP_REQUIRE(Q && qn && X && xn && dist && workspace, "vtp_pr_knn_dist: null pointer (Q, qn, X, xn, dist, workspace)");
-  if (pr_check_tiles("vtp_pr_knn_dist", Q, ldq, X, ldx, B, N, D, splits) != VTP_OK) return VTP_ERR_ARG;
+  PrArgs g;
+  dim3 grid;
+  if (sweep_prepare("vtp_pr_knn_dist", Q, ldq, X, ldx, B, N, D, splits, 1, g.sw, grid) != VTP_OK) return VTP_ERR_ARG;
   VTP_REQUIRE(aligned16(dist) && aligned16(workspace), "vtp_pr_knn_dist: dist and workspace must be 16-byte aligned");
   VTP_REQUIRE(query_base >= -1 && query_base <= LONG_MAX - B, "vtp_pr_knn_dist: query_base must be -1 (no exclusion) or a row index (query_base=%ld)",
               query_base);
   VTP_REQUIRE(index_base >= 0 && index_base <= LONG_MAX - N, "vtp_pr_knn_dist: index_base must be non-negative (index_base=%ld)", index_base);
   VTP_REQUIRE(!d2_out || ldo >= N, "vtp_pr_knn_dist: d2_out needs ldo >= N (ldo=%d)", ldo);
-  const int s = pr_splits(B, N, splits);
+  const int s = grid.x;
   const long need = (long)s * B * PR_K * 4;
   VTP_REQUIRE(workspace_bytes >= need, "vtp_pr_knn_dist: workspace of %ld bytes, %ld needed (vtp_pr_workspace_bytes)", workspace_bytes, need);
-  const int tiles = cdiv(N, PR_BM);
-  PrArgs g;
-  g.Q = Q, g.X = X, g.qn = qn, g.xn = xn, g.r2 = nullptr;
+  g.qn = qn, g.xn = xn, g.r2 = nullptr;
   g.part = (float*)workspace, g.d2_out = d2_out, g.hits = nullptr;
   g.excl = query_base < 0 ? LONG_MIN : index_base - query_base;
-  g.ldq = ldq, g.ldx = ldx, g.ldo = ldo, g.B = B, g.N = N, g.D = D, g.tiles = tiles, g.tiles_per_split = cdiv(tiles, s);
+  g.ldo = ldo;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(pr_knn_kernel, dim3(s, cdiv(B, PR_BQ)), dim3(256), 0, st, g);
+  hipLaunchKernelGGL(pr_knn_kernel, grid, dim3(256), 0, st, g);
   const int rc = check_launch("pr_knn");
   if (rc != VTP_OK) return rc;
   hipLaunchKernelGGL(pr_fold_kernel, dim3(cdiv(B, PR_NB)), dim3(PR_NB), 0, st, dist, (const float*)g.part, B, s);
@@ -326,14 +264,13 @@ extern "C" int vtp_pr_knn_dist(const float* Q, int ldq, const float* qn, const f
 extern "C" int vtp_pr_cover(const float* Q, int ldq, const float* qn, const float* X, int ldx, const float* xn, const float* r2, int B,
                             int N, int D, int* hits, int splits, void* stream) {
   VTP_REQUIRE(Q && qn && X && xn && r2 && hits, "vtp_pr_cover: null pointer (Q, qn, X, xn, r2, hits)");
-  if (pr_check_tiles("vtp_pr_cover", Q, ldq, X, ldx, B, N, D, splits) != VTP_OK) return VTP_ERR_ARG;
-  const int s = pr_splits(B, N, splits);
-  const int tiles = cdiv(N, PR_BM);
   PrArgs g;
-  g.Q = Q, g.X = X, g.qn = qn, g.xn = xn, g.r2 = r2;
+  dim3 grid;
+  if (sweep_prepare("vtp_pr_cover", Q, ldq, X, ldx, B, N, D, splits, 1, g.sw, grid) != VTP_OK) return VTP_ERR_ARG;
+  g.qn = qn, g.xn = xn, g.r2 = r2;
   g.part = nullptr, g.d2_out = nullptr, g.hits = hits;
   g.excl = LONG_MIN;
-  g.ldq = ldq, g.ldx = ldx, g.ldo = 0, g.B = B, g.N = N, g.D = D, g.tiles = tiles, g.tiles_per_split = cdiv(tiles, s);
-  hipLaunchKernelGGL(pr_cover_kernel, dim3(s, cdiv(B, PR_BQ)), dim3(256), 0, (hipStream_t)stream, g);
+  g.ldo = 0;
+  hipLaunchKernelGGL(pr_cover_kernel, grid, dim3(256), 0, (hipStream_t)stream, g);
   return check_launch("pr_cover");
 }

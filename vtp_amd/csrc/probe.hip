@@ -100,7 +100,7 @@ __global__ __launch_bounds__(256) void probe_ce_kernel(const float* __restrict__
   for (int o = 32; o > 0; o >>= 1) {
     const float om = __shfl_xor(m, o, 64);
     const int oi = __shfl_xor(mi, o, 64);
-    if (oi != INT_MAX && (mi == INT_MAX || om > m || (om == m && oi < mi))) m = om, mi = oi;
+    if (oi != INT_MAX && (mi == INT_MAX || before(om, oi, m, mi))) m = om, mi = oi;
   }
   if (lane == 0) red_v[w] = m, red_i[w] = mi;
   __syncthreads();
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(256) void probe_ce_kernel(const float* __restrict__
   for (int i = 1; i < 4; ++i) {
     const float om = red_v[i];
     const int oi = red_i[i];
-    if (oi != INT_MAX && (mi == INT_MAX || om > m || (om == m && oi < mi))) m = om, mi = oi;
+    if (oi != INT_MAX && (mi == INT_MAX || before(om, oi, m, mi))) m = om, mi = oi;
   }
   float s = 0.f;
   for (int c = tid; c < C; c += 256) s += expf(z[c] - m);
@@ -198,8 +198,6 @@ __global__ __launch_bounds__(256) void probe_sgd_kernel(float* __restrict__ W, f
 }  // namespace vtp
 
 using namespace vtp;
-
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 extern "C" int vtp_probe_logits(const float* X, int ldx, const float* W, const float* bias, float* logits, int ldl, int B, int N,
                                 int K, void* stream) {

@@ -23,10 +23,11 @@
 //   the bits of the tile).  Columns past D up to the tile's slab of 16 are zeros, as in the tile.  The thread of the first pair of a
 //   query within the round folds the round's pairs of that query into the query's running best, which lives in the output: one
 //   owner per query, no atomics.  An index outside [0, n_total) is ignored.
-// retr_rank_kernel.  The tile loop of knn_topk_kernel and pr_cover_kernel (tile_f32.h): grid = chunk splits x row blocks of 128
-//   queries, 256 threads, 128 x 128 tiles on v_mfma_f32_32x32x2_f32; a query sits on a lane and its candidates are accumulator
-//   registers.  The epilogue compares each of the lane's 64 values with the (s*, j*) of its query and counts per lane; the four
-//   lane-sets of a query (wm x half) are summed in LDS and one integer atomicAdd per query and workgroup reaches memory: exact and
+// retr_rank_kernel.  The bank sweep of tile_f32.h (the walk and the tile product that knn_topk_kernel and the precision / recall
+//   kernels run as well; the product is the main loop of vtp_gemm_nt_f32 itself): grid = chunk splits x row blocks of 128 queries,
+//   256 threads, 128 x 128 tiles on v_mfma_f32_32x32x2_f32; a query sits on a lane and its candidates are accumulator registers.
+//   The epilogue compares each of the lane's 64 values with the (s*, j*) of its query and counts per lane; sweep_add_counts sums
+//   the four lane-sets of a query (wm x half) in LDS and one integer atomicAdd per query and workgroup reaches memory: exact and
 //   order-free, so the result is identical whatever the chunking, the splits, B or the grid.
 // LDS: retr_rank 33 KiB of operand slabs + 2 KiB of counts, two workgroups per CU; retr_best 2 x 64 x 65 x 4 B = 33 KiB.
 #include "common.h"
@@ -39,14 +40,8 @@
 
 namespace vtp {
 
-constexpr int RT_BM = TF_BM, RT_BQ = TF_BQ, RT_BK = TF_BK, RT_KQ = TF_KQ, RT_IT = TF_IT, RT_LD = TF_LD;  // the tile loop: tile_f32.h
-constexpr int RT_MAX_SPLITS = 1024, RT_AUTO_SPLITS = 256, RT_AUTO_BLOCKS = 512;
 constexpr int RT_NB = 64;     // pairs per round of retr_best_kernel
 constexpr int RT_MAXNK = 8;   // recall levels per vtp_retr_count call
-
-// (similarity descending, index ascending): a strictly before b.  The empty best (-inf, -1) is before nothing and every finite
-// similarity is before it.
-__device__ __forceinline__ bool rt_before(float as, long ai, float bs, long bi) { return as > bs || (as == bs && ai < bi); }
 
 // ---------------------------------------------------------------------------------------------------------------- best ground truth
 __global__ __launch_bounds__(256) void retr_best_kernel(const float* Q, int ldq, const float* X, int ldx, long n_total, const int* gt_ptr,
@@ -73,7 +68,7 @@ __global__ __launch_bounds__(256) void retr_best_kernel(const float* Q, int ldq,
   // (the clamps and the range checks below keep every access inside the arrays whatever gt_ptr holds)
   const int pbeg = gt_ptr[b_lo] > 0 ? gt_ptr[b_lo] : 0;
   const int pend = gt_ptr[b_hi] < nnz ? gt_ptr[b_hi] : nnz;  // b_hi <= B: gt_ptr has B + 1 entries
-  const int dpad = (D + RT_BK - 1) / RT_BK * RT_BK;          // the tile walks whole slabs of 16 columns
+  const int dpad = (D + TF_BK - 1) / TF_BK * TF_BK;          // the tile walks whole slabs of 16 columns
   __syncthreads();
 
   for (int p0 = pbeg; p0 < pend; p0 += RT_NB) {
@@ -124,7 +119,7 @@ __global__ __launch_bounds__(256) void retr_best_kernel(const float* Q, int ldq,
       float s = best_s[b];
       long j = best_j[b];
       for (int t = tid; t < RT_NB && pb[t] == b; ++t)
-        if (pj[t] >= 0 && rt_before(ps[t], pj[t], s, j)) s = ps[t], j = pj[t];
+        if (pj[t] >= 0 && before(ps[t], pj[t], s, j)) s = ps[t], j = pj[t];
       best_s[b] = s, best_j[b] = j;
     }
     __syncthreads();
@@ -133,85 +128,47 @@ __global__ __launch_bounds__(256) void retr_best_kernel(const float* Q, int ldq,
 
 // ---------------------------------------------------------------------------------------------------------------- rank
 struct RetrArgs {
-  const float *Q, *X, *best_s;
+  SweepArgs sw;
+  const float* best_s;
   const long* best_j;
   int* beats;
   float* sims_out;
   long index_base;
-  int ldq, ldx, lds, B, N, D, tiles, tiles_per_split;
+  int lds;
 };
 
 struct RetrLds {
-  float As[2][RT_BK][RT_LD];  // gallery rows
-  float Bs[2][RT_BK][RT_LD];  // queries
-  int cnt[4][RT_BQ];          // [wm * 2 + half][query]
+  float As[2][TF_BK][TF_LD];  // gallery rows
+  float Bs[2][TF_BK][TF_LD];  // queries
+  int cnt[4][TF_BQ];          // [wm * 2 + half][query]
 };
 
 __global__ __launch_bounds__(256, 2) void retr_rank_kernel(const RetrArgs g) {
   __shared__ __attribute__((aligned(16))) RetrLds L;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1, j = lane & 31, half = lane >> 5;
-  const int split = blockIdx.x, q0 = blockIdx.y * RT_BQ;
-  const int nq = g.B - q0 < RT_BQ ? g.B - q0 : RT_BQ;
-
-  const int kq = tid & (RT_KQ - 1);
-  const float* bp[RT_IT];
-  int lr[RT_IT];
-#pragma unroll
-  for (int it = 0; it < RT_IT; ++it) {
-    const int r = tid / RT_KQ + (256 / RT_KQ) * it;
-    lr[it] = r;
-    bp[it] = r < nq ? g.Q + (size_t)(q0 + r) * g.ldq + 4 * kq : nullptr;
-  }
-  // this lane's two queries wn * 64 + v * 32 + j: the best ground-truth row, and the count
+  const SweepCtx c = sweep_begin(g.sw);
+  // this lane's two queries c.query(v): the best ground-truth row in rows of the chunk (negative: none), and the count
   float bs[2];
   long bj[2];
   int cnt[2] = {0, 0};
 #pragma unroll
   for (int v = 0; v < 2; ++v) {
-    const int ql = wn * 64 + v * 32 + j;
-    bs[v] = ql < nq ? g.best_s[q0 + ql] : -INFINITY;
-    bj[v] = ql < nq ? g.best_j[q0 + ql] : -1;
+    const int ql = c.query(v);
+    bs[v] = ql < c.nq ? g.best_s[c.q0 + ql] : -INFINITY;
+    bj[v] = ql < c.nq ? g.best_j[c.q0 + ql] : -1;
   }
-  const int tile_lo = split * g.tiles_per_split;
-  const int tile_hi = tile_lo + g.tiles_per_split < g.tiles ? tile_lo + g.tiles_per_split : g.tiles;
 
-  for (int tile = tile_lo; tile < tile_hi; ++tile) {
-    const int n0 = tile * RT_BM;
-    const float* ap[RT_IT];
-#pragma unroll
-    for (int it = 0; it < RT_IT; ++it) ap[it] = n0 + lr[it] < g.N ? g.X + (size_t)(n0 + lr[it]) * g.ldx + 4 * kq : nullptr;
+  for (int tile = c.tile_lo; tile < c.tile_hi; ++tile) {
     f32x16 acc[2][2];
-    tile_f32_product(ap, bp, lr, kq, g.D, L.As, L.Bs, wm, wn, j, half, acc);
-
-    // lane = query wn * 64 + v * 32 + j, register = gallery row wm * 64 + u * 32 + acc_row(r, half) of the tile
-    const int rows_left = g.N - n0 - wm * 64;  // rows of this wave's part of the tile inside the chunk
-#pragma unroll
-    for (int v = 0; v < 2; ++v) {
-      const int ql = wn * 64 + v * 32 + j;
-      if (ql >= nq) continue;
-      const bool all = bj[v] < 0;                                  // no ground truth: every row of the chunk counts
-      const long ti = bj[v] - g.index_base - n0 - wm * 64;         // j* in rows of this wave's part of the tile
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = u * 32 + acc_row(r, half);
-          if (row >= rows_left) continue;
-          if (g.sims_out) g.sims_out[(size_t)(q0 + ql) * g.lds + n0 + wm * 64 + row] = acc[u][v][r];
-          cnt[v] += (all || rt_before(acc[u][v][r], row, bs[v], ti)) ? 1 : 0;
-        }
-    }
+    sweep_tile(g.sw, c, tile, L.As, L.Bs, acc);
+    const int n0 = tile * TF_BM + c.wm * 64;  // the first gallery row of this wave's part of the tile
+    const bool all[2] = {bj[0] < 0, bj[1] < 0};                                // no ground truth: every row of the chunk counts
+    const long ti[2] = {bj[0] - g.index_base - n0, bj[1] - g.index_base - n0};  // j* in rows of this wave's part of the tile
+    sweep_visit(g.sw, c, tile, acc, [&](int, int v, int, int ql, int row, float s) {
+      if (g.sims_out) g.sims_out[(size_t)(c.q0 + ql) * g.lds + n0 + row] = s;
+      cnt[v] += (all[v] || before<long>(s, row, bs[v], ti[v])) ? 1 : 0;
+    });
   }
-
-  // the four lane-sets of a query (wm x half) meet in LDS: `cnt` is touched nowhere else
-#pragma unroll
-  for (int v = 0; v < 2; ++v) L.cnt[wm * 2 + half][wn * 64 + v * 32 + j] = cnt[v];
-  __syncthreads();
-  if (tid < nq) {
-    const int c = L.cnt[0][tid] + L.cnt[1][tid] + L.cnt[2][tid] + L.cnt[3][tid];
-    if (c) atomicAdd(g.beats + q0 + tid, c);
-  }
+  sweep_add_counts(c, cnt, L.cnt, g.beats);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- counters
@@ -244,29 +201,15 @@ __global__ __launch_bounds__(256) void retr_count_kernel(const int* beats, int B
 
 using namespace vtp;
 
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// the split count of a call: the one of vtp_pr_cover -- the forced one, or enough workgroups to fill the chip twice (two fit a CU);
-// a split costs one 2 KiB sum in LDS and an atomic per query beyond its tiles.  Splits that would get no tile are dropped.
-static int retr_splits(int B, int N, int splits) {
-  if (splits > 0) return splits;
-  const int rb = cdiv(B, RT_BQ), tiles = cdiv(N, RT_BM);
-  int s = cdiv(RT_AUTO_BLOCKS, rb);
-  if (s > RT_AUTO_SPLITS) s = RT_AUTO_SPLITS;
-  if (s > tiles) s = tiles;
-  return cdiv(tiles, cdiv(tiles, s));
-}
-
 extern "C" int vtp_retr_best(const float* Q, int ldq, const float* X, int ldx, long n_total, const int* gt_ptr, const long* gt_idx, int nnz,
                              int B, int D, float* best_s, long* best_j, void* stream) {
   VTP_REQUIRE(Q && X && gt_ptr && best_s && best_j, "vtp_retr_best: null pointer (Q, X, gt_ptr, best_s, best_j)");
   VTP_REQUIRE(gt_idx || nnz == 0, "vtp_retr_best: null pointer (gt_idx) with nnz != 0");
   VTP_REQUIRE(nnz >= 0 && nnz <= INT_MAX - RT_NB, "vtp_retr_best: need 0 <= nnz <= 2^31 - 65 (nnz=%d)", nnz);
-  VTP_REQUIRE(B >= 1 && D >= 8 && D % 8 == 0, "vtp_retr_best: need B >= 1 and D a positive multiple of 8 (B=%d D=%d)", B, D);
+  VTP_REQUIRE(B >= 1, "vtp_retr_best: need B >= 1 (B=%d)", B);
   VTP_REQUIRE(n_total >= 1 && n_total <= INT_MAX, "vtp_retr_best: need 1 <= n_total <= 2^31 - 1: a rank is an int32 (n_total=%ld)", n_total);
-  VTP_REQUIRE(ldq >= D && ldx >= D && ldq % 4 == 0 && ldx % 4 == 0,
-              "vtp_retr_best: leading dimensions must cover the rows, ldq and ldx multiples of 4 (ldq=%d ldx=%d)", ldq, ldx);
-  VTP_REQUIRE(aligned16(Q) && aligned16(X), "vtp_retr_best: Q and X must be 16-byte aligned");
+  if (sweep_check_rows("vtp_retr_best", "Q", "ldq", Q, ldq, D) != VTP_OK || sweep_check_rows("vtp_retr_best", "X", "ldx", X, ldx, D) != VTP_OK)
+    return VTP_ERR_ARG;
   hipLaunchKernelGGL(retr_best_kernel, dim3(nnz / RT_NB + 1), dim3(256), 0, (hipStream_t)stream, Q, ldq, X, ldx, n_total, gt_ptr, gt_idx, nnz,
                      B, D, best_s, best_j);
   return check_launch("retr_best");
@@ -275,23 +218,15 @@ extern "C" int vtp_retr_best(const float* Q, int ldq, const float* X, int ldx, l
 extern "C" int vtp_retr_rank(const float* Q, int ldq, const float* X, int ldx, long index_base, int B, int N, int D, const float* best_s,
                              const long* best_j, int* beats, int splits, float* sims_out, int lds, void* stream) {
   VTP_REQUIRE(Q && X && best_s && best_j && beats, "vtp_retr_rank: null pointer (Q, X, best_s, best_j, beats)");
-  VTP_REQUIRE(B >= 1 && N >= 1 && D >= 8 && D % 8 == 0, "vtp_retr_rank: need B, N >= 1 and D a positive multiple of 8 (B=%d N=%d D=%d)", B, N, D);
-  VTP_REQUIRE(ldq >= D && ldx >= D && ldq % 4 == 0 && ldx % 4 == 0,
-              "vtp_retr_rank: leading dimensions must cover the rows, ldq and ldx multiples of 4 (ldq=%d ldx=%d)", ldq, ldx);
-  VTP_REQUIRE(aligned16(Q) && aligned16(X), "vtp_retr_rank: Q and X must be 16-byte aligned");
+  RetrArgs g;
+  dim3 grid;
+  if (sweep_prepare("vtp_retr_rank", Q, ldq, X, ldx, B, N, D, splits, 1, g.sw, grid) != VTP_OK) return VTP_ERR_ARG;
   VTP_REQUIRE(index_base >= 0 && index_base <= (long)INT_MAX - N,
               "vtp_retr_rank: index_base must be non-negative and index_base + N at most 2^31 - 1 (index_base=%ld)", index_base);
-  VTP_REQUIRE(splits >= 0 && splits <= RT_MAX_SPLITS, "vtp_retr_rank: 0 <= splits <= 1024 (splits=%d)", splits);
   VTP_REQUIRE(!sims_out || lds >= N, "vtp_retr_rank: sims_out needs lds >= N (lds=%d)", lds);
-  const long rb = ((long)B + RT_BQ - 1) / RT_BQ;
-  VTP_REQUIRE(rb <= 65535, "vtp_retr_rank: B too large (B=%d)", B);
-  const int s = retr_splits(B, N, splits);
-  const int tiles = cdiv(N, RT_BM);
-  RetrArgs g;
-  g.Q = Q, g.X = X, g.best_s = best_s, g.best_j = best_j, g.beats = beats, g.sims_out = sims_out;
-  g.index_base = index_base;
-  g.ldq = ldq, g.ldx = ldx, g.lds = lds, g.B = B, g.N = N, g.D = D, g.tiles = tiles, g.tiles_per_split = cdiv(tiles, s);
-  hipLaunchKernelGGL(retr_rank_kernel, dim3(s, (unsigned)rb), dim3(256), 0, (hipStream_t)stream, g);
+  g.best_s = best_s, g.best_j = best_j, g.beats = beats, g.sims_out = sims_out;
+  g.index_base = index_base, g.lds = lds;
+  hipLaunchKernelGGL(retr_rank_kernel, grid, dim3(256), 0, (hipStream_t)stream, g);
   return check_launch("retr_rank");
 }
 

@@ -106,15 +106,6 @@ __device__ __forceinline__ f32x16 zs_tile(const float* __restrict__ wp, const fl
   return acc;
 }
 
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// the order of torch.topk with the lower index first among equals: a before b
-__device__ __forceinline__ bool zs_before(float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai < bi); }
-
 __global__ __launch_bounds__(ZS_WAVES * 64) void zs_topk_kernel(const float* __restrict__ F, int ldf, const float* __restrict__ Wt,
                                                      int ldw, const long* __restrict__ targets, float scale, int B, int C, int K, int CH,
                                                      unsigned long long* __restrict__ counts, int* __restrict__ per_class,
@@ -184,7 +175,7 @@ __global__ __launch_bounds__(ZS_WAVES * 64) void zs_topk_kernel(const float* __r
         const float ztv = zt_s[row];
         int cnt = 0;
 #pragma unroll
-        for (int i = 0; i < ZS_PER_LANE; ++i) cnt += (lane + 64 * i < cw && zs_before(v[i], c0 + lane + 64 * i, ztv, t)) ? 1 : 0;
+        for (int i = 0; i < ZS_PER_LANE; ++i) cnt += (lane + 64 * i < cw && before(v[i], c0 + lane + 64 * i, ztv, t)) ? 1 : 0;
         cnt = wave_sum_int(cnt);
         if (lane == 0) rank_s[row] += cnt;
       }
@@ -205,14 +196,14 @@ __global__ __launch_bounds__(ZS_WAVES * 64) void zs_topk_kernel(const float* __r
 #pragma unroll
           for (int i = 0; i < ZS_PER_LANE; ++i) {
             const int gi = c0 + lane + 64 * i;
-            if (lane + 64 * i < cw && zs_before(pv, pi, v[i], gi) && (mi == INT_MAX || zs_before(v[i], gi, mv, mi))) mv = v[i], mi = gi;
+            if (lane + 64 * i < cw && before(pv, pi, v[i], gi) && (mi == INT_MAX || before(v[i], gi, mv, mi))) mv = v[i], mi = gi;
           }
-          if (oi >= 0 && zs_before(pv, pi, ov, oi) && (mi == INT_MAX || zs_before(ov, oi, mv, mi))) mv = ov, mi = oi;
+          if (oi >= 0 && before(pv, pi, ov, oi) && (mi == INT_MAX || before(ov, oi, mv, mi))) mv = ov, mi = oi;
 #pragma unroll
           for (int o = 32; o > 0; o >>= 1) {
             const float xv = __shfl_xor(mv, o, 64);
             const int xi = __shfl_xor(mi, o, 64);
-            if (xi != INT_MAX && (mi == INT_MAX || zs_before(xv, xi, mv, mi))) mv = xv, mi = xi;
+            if (xi != INT_MAX && (mi == INT_MAX || before(xv, xi, mv, mi))) mv = xv, mi = xi;
           }
           nv[q] = mv, ni[q] = mi == INT_MAX ? -1 : mi;  // fewer than five comparable values (NaN logits): -1
           pv = mi == INT_MAX ? -INFINITY : mv, pi = mi;  // (-inf, INT_MAX): nothing comes after it
@@ -251,8 +242,6 @@ __global__ __launch_bounds__(ZS_WAVES * 64) void zs_topk_kernel(const float* __r
 }  // namespace vtp
 
 using namespace vtp;
-
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 extern "C" int vtp_zs_class_mean(const float* feat, int ldf, float* Wt, int ldw, int C, int T, int D, float eps, void* stream) {
   VTP_REQUIRE(feat && Wt, "vtp_zs_class_mean: null pointer");
