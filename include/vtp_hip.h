@@ -814,6 +814,37 @@ int vtp_is_rows(const float* logits, int ldl, int B, int C, double* p, int ldp, 
 int vtp_is_accum(const double* p, int ldp, const double* h, long row_base, long split_size, int B, int C, double* state, int n_slots,
                  void* stream);
 
+/* ---- Kernel Inception Distance (mmd.hip): the pair sums of the unbiased MMD^2 of two feature sets under the polynomial kernel
+ * k(x, y) = (gamma x.y + coef0)^degree (Binkowski et al. 2018), restated from the paper's definition; neither torch-fidelity nor the
+ * authors' TF code is a reference of this project, so parity with those programs is unpinned.  No atomics, no host synchronisation.
+ *   s(a, b) = the fmaf chain over k = 0 .. D-1 ascending, the bits of vtp_gemm_nt_f32 with the plain epilogue; then in fp64, every
+ *   operation rounded on its own: t = (double)s * gamma + coef0, k = t multiplied by t a further degree - 1 times, left to right.
+ *
+ * vtp_mmd_poly_part: part f64 [P, tiles, B], tiles = ceil(N / 128): part[p][t][b] = the sum of k(q_b, x_n) over the rows n of tile t
+ * of problem p's bank.  Q f32 [., D] (row stride ldq) holds the queries, X f32 [., D] (row stride ldx) the bank rows.
+ *   qi / xi (may be NULL: identity, Q is [B, D] / X is [N, D]): DEVICE int32 [P, B] / [P, N]: query b of problem p is row qi[p][b] of
+ *   Q [q_rows, D], bank row n is row xi[p][n] of X [x_rows, D]; an index outside its matrix is read as a row of zeros.  q_rows /
+ *   x_rows are read only with a list.
+ *   Left out (skipped, not added as zero): the pair with query_base + b == index_base + n when query_base >= 0 (positions in the
+ *   lists, not gathered rows; query_base = -1: nothing is excluded), rows past N, queries past B.
+ *   kparams: HOST double[2] = {gamma, coef0}, read before the launch.  degree: 1 .. 8.
+ *   The order of every sum is fixed (written once in mmd.hip) and depends on a row's position in its tile alone; index_base must be
+ *   a multiple of 128, so a tile covers the same absolute rows whatever the chunking of the bank.
+ *   Limits: D a positive multiple of 8, ldq and ldx multiples of 4 and >= D, Q and X 16-byte aligned, B <= 65535 * 128, P <= 65535,
+ *   part_bytes >= vtp_mmd_workspace_bytes(B, N, P) = P * tiles * B * 8.
+ * vtp_mmd_workspace_bytes returns the bytes of part, or -1 (bad argument, or more than 2 GiB: pass fewer rows per call).
+ * vtp_mmd_fold: rowsum f64 [P, B] (in/out: zero it before the first chunk; chunks in ascending order): rowsum[p][b] += part[p][t][b]
+ *   for t = 0 .. tiles - 1 ascending, one owner thread per element.
+ * vtp_mmd_total: total f64 [P]: total[p] = the sum of rowsum[p][0 .. B) by the tree that pairs neighbours level by level (an odd last
+ *   element moves up unchanged): its shape depends on B alone.  B <= 2097152.
+ * Row sums and totals repeat bit for bit whatever the chunk size, the queries per call or the card. */
+int vtp_mmd_workspace_bytes(int B, int N, int P);
+int vtp_mmd_poly_part(const float* Q, int ldq, int q_rows, const int* qi, const float* X, int ldx, int x_rows, const int* xi,
+                      long query_base, long index_base, int B, int N, int D, int P, const double* kparams, int degree, double* part,
+                      long part_bytes, void* stream);
+int vtp_mmd_fold(const double* part, double* rowsum, int B, int tiles, int P, void* stream);
+int vtp_mmd_total(const double* rowsum, int B, int P, double* total, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

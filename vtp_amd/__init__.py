@@ -2,7 +2,7 @@
 
 Public surface mirrors the reference (`from vtp.models.vtp_hf import VTPConfig, VTPModel`):
     from vtp_amd import VTPConfig, VTPModel, VTPTrainer, LinearProbe, ZeroShot, Knn, ReconEval, MultiCrop, Preprocess, FID,
-    InceptionFeatures, FrechetStats, frechet_distance, PrecisionRecall, InceptionScore, GenEval, Retrieval
+    InceptionFeatures, FrechetStats, frechet_distance, PrecisionRecall, InceptionScore, GenEval, Retrieval, KID
 Everything below the Python API is hand-written HIP in libvtp_hip.so (C ABI: include/vtp_hip.h)."""
 from .config import VTPConfig  # noqa: F401
 
@@ -59,4 +59,7 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name == "Retrieval":
         from .retrieval import Retrieval
         return Retrieval
+    if name == "KID":
+        from .kid import KID
+        return KID
     raise AttributeError(name)

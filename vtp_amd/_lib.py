@@ -183,6 +183,12 @@ SIGNATURES = {
     # Inception Score (inception_score.hip)
     "vtp_is_rows": [_P, _I, _I, _I, _P, _I, _P, _P],  # logits ldl B C p ldp h stream
     "vtp_is_accum": [_P, _I, _P, _L, _L, _I, _I, _P, _I, _P],  # p ldp h row_base split_size B C state n_slots stream
+    # Kernel Inception Distance (mmd.hip)
+    "vtp_mmd_workspace_bytes": [_I, _I, _I],  # B N P -> bytes, or -1
+    # Q ldq q_rows qi X ldx x_rows xi query_base index_base B N D P kparams degree part part_bytes stream
+    "vtp_mmd_poly_part": [_P, _I, _I, _P, _P, _I, _I, _P, _L, _L, _I, _I, _I, _I, _P, _I, _P, _L, _P],
+    "vtp_mmd_fold": [_P, _P, _I, _I, _I, _P],  # part rowsum B tiles P stream
+    "vtp_mmd_total": [_P, _I, _I, _P, _P],  # rowsum B P total stream
 }
 
 _lib = None

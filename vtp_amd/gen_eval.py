@@ -13,6 +13,8 @@ layout follows the published graph names (InceptionFeatures.forward_taps).
     for u8 in generated_batches:
         ge.add_generated(u8)                                       # uint8 [B, H, W, 3] on the device
     ge.results()                                                   # {"fid", "sfid", "is", "is_std", "precision", "recall"}
+GenEval(..., kid=True) (or kid=dict(subsets=..., subset_size=...)) adds "kid" / "kid_std", the Kernel Inception Distance of
+vtp_amd.KID on the same pool rows (tests/mmd_ref.py).
 
 add_generated / add_real run InceptionFeatures.forward_taps once on FID's preprocessing of the byte images; the pool row feeds a
 FrechetStats (FID), the InceptionScore and the PrecisionRecall bank, the flattened spatial tap a second FrechetStats (sFID, its
@@ -29,12 +31,15 @@ import torch
 
 from .fid import FEATURE_DIM, FID, FrechetStats, InceptionFeatures, frechet_distance
 from .inception_score import InceptionScore
+from .kid import KID
 from .precision_recall import PrecisionRecall
 
 
-def result_keys(fc: bool, reference: bool, reference_spatial: bool, real_rows: int, precision_recall: bool = True) -> Tuple[str, ...]:
+def result_keys(fc: bool, reference: bool, reference_spatial: bool, real_rows: int, precision_recall: bool = True, kid: bool = False,
+                kid_subsets: bool = True) -> Tuple[str, ...]:
     """the keys of GenEval.results(): fc -- a classifier was given; reference / reference_spatial -- set_reference was called with
-    (mu, sigma) / also with (mu_s, sigma_s); real_rows -- rows added through add_real on this rank's group"""
+    (mu, sigma) / also with (mu_s, sigma_s); real_rows -- rows added through add_real on this rank's group; kid -- a KID was asked
+    for, kid_subsets -- with the subset protocol (the full-set estimator has no "kid_std")"""
     keys = []
     if reference or real_rows >= 2:
         keys.append("fid")
@@ -44,21 +49,29 @@ def result_keys(fc: bool, reference: bool, reference_spatial: bool, real_rows: i
         keys += ["is", "is_std"]
     if precision_recall and real_rows >= 1:
         keys += ["precision", "recall"]
+    if kid and real_rows >= 1:
+        keys += ["kid", "kid_std"] if kid_subsets else ["kid"]
     return tuple(keys)
 
 
 class GenEval:
     """inception: an InceptionFeatures on the device.  fc: (weight [C, 2048], bias [C]) of the classifier, or None (no Inception
     Score).  k: the neighbourhood size of precision / recall (None: no banks are kept).  split_size: rows per split of the
-    Inception Score.  group: a process group whose ranks each add their own images."""
+    Inception Score.  group: a process group whose ranks each add their own images.  kid: a dict of vtp_amd.KID arguments (True:
+    its defaults; None: no KID); with k set it reads the banks of precision / recall, so the pool rows are kept once."""
 
-    def __init__(self, inception: InceptionFeatures, fc=None, k: Optional[int] = 3, split_size: Optional[int] = 5000, group=None):
+    def __init__(self, inception: InceptionFeatures, fc=None, k: Optional[int] = 3, split_size: Optional[int] = 5000, group=None,
+                 kid=None):
         self.inception, self.group = inception, group
         self._fid = FID(inception, group)  # its preprocessing per variant; ref = the real images, rec = the generated ones
         self.device = self._fid.device
         self._spatial: Optional[Dict[str, FrechetStats]] = None  # made by the first batch, which fixes D = 7 h w
         self.isc = None if fc is None else InceptionScore(fc[0], fc[1], split_size=split_size, device=self.device, group=group)
         self.pr = None if k is None else PrecisionRecall(k=k, group=group, device=self.device)
+        self.kid = None
+        if kid is not None and kid is not False:
+            kw = {} if kid is True else dict(kid)
+            self.kid = KID(banks=self.pr, **kw) if self.pr is not None else KID(group=group, device=self.device, **kw)
         self._ref = self._ref_s = None
         self._real_rows = 0
 
@@ -100,6 +113,8 @@ class GenEval:
         self._spatial["real"].update(spatial)
         if self.pr is not None:
             self.pr.add_real_features(pool)
+        elif self.kid is not None:
+            self.kid.add_real_features(pool)
         self._real_rows += int(pool.shape[0])
 
     def add_generated(self, u8: torch.Tensor) -> None:
@@ -111,6 +126,8 @@ class GenEval:
             self.isc.update(pool)
         if self.pr is not None:
             self.pr.add_fake_features(pool)
+        elif self.kid is not None:
+            self.kid.add_fake_features(pool)
 
     def _real_rows_of_group(self) -> int:
         if self.group is None:
@@ -126,7 +143,7 @@ class GenEval:
         if self.generated.n < 1:
             raise RuntimeError("results(): add_generated first")
         keys = result_keys(self.isc is not None, self._ref is not None, self._ref_s is not None, self._real_rows_of_group(),
-                           self.pr is not None)
+                           self.pr is not None, self.kid is not None, self.kid is not None and self.kid.subsets > 0)
         out: Dict[str, float] = {}
         if "fid" in keys:
             mu, sigma = self._ref if self._ref is not None else self.real.mean_cov()
@@ -139,6 +156,8 @@ class GenEval:
             out["is"], out["is_std"] = r["is"], r["is_std"]
         if "precision" in keys:
             out.update(self.pr.result())
+        if "kid" in keys:
+            out.update(self.kid.result())
         return out
 
     def reset(self) -> None:
@@ -150,4 +169,6 @@ class GenEval:
             self.isc.reset()
         if self.pr is not None:
             self.pr.reset()
+        if self.kid is not None:
+            self.kid.reset()
         self._real_rows = 0

@@ -968,6 +968,70 @@ def pr_cover(q, qn, x, xn, r2, hits, splits=0):
                "vtp_pr_cover")
 
 
+MMD_TILE = 128  # bank rows per tile of mmd_poly_part: index_base is a multiple of it
+MMD_MAX_DEGREE = 8
+
+
+def mmd_workspace_bytes(B, N, P=1):
+    """bytes of the part buffer of mmd_poly_part for B queries, N bank rows and P problems: P * ceil(N / 128) * B * 8; ValueError for
+    arguments the kernel refuses or a buffer above 2 GiB"""
+    n = _lib_().vtp_mmd_workspace_bytes(B, N, P)
+    if n < 0:
+        raise ValueError(_lib_().vtp_last_error().decode(errors="replace"))
+    return n
+
+
+def mmd_poly_part(q, x, part, gamma, coef0=1.0, degree=3, query_base=-1, index_base=0, qi=None, xi=None):
+    """part f64 [P, tiles, B] (tiles = ceil(N / 128)): per problem, bank tile and query the sum of (gamma q.x + coef0)^degree over the
+    tile's rows, the products with the bits of gemm_nt_f32 and everything after in fp64, in the fixed order of csrc/mmd.hip.  q f32
+    [., D] / x f32 [., D] may be column slices of wider matrices.  qi int32 [P, B] / xi int32 [P, N] on the device (None: identity, q is
+    [B, D] / x is [N, D]) pick the rows of q / x that a problem's queries / bank rows are.  query_base >= 0: the pair with query_base
+    + b == index_base + n (positions in the lists) is skipped; -1: no exclusion.  index_base: a multiple of 128."""
+    import ctypes
+    _pr_rows(q=q, x=x)
+    if q.shape[1] != x.shape[1]:
+        raise ValueError(f"q and x must be [., D] and [., D], got {tuple(q.shape)} and {tuple(x.shape)}")
+    D = q.shape[1]
+    _need(part, "part", torch.float64, dims=3)
+    P = part.shape[0]
+    if qi is not None:
+        _need(qi, "qi", torch.int32, dims=2)
+    if xi is not None:
+        _need(xi, "xi", torch.int32, dims=2)
+    B = q.shape[0] if qi is None else qi.shape[1]
+    N = x.shape[0] if xi is None else xi.shape[1]
+    for name, t in (("qi", qi), ("xi", xi)):
+        if t is not None and t.shape[0] != P:
+            raise ValueError(f"{name} must hold one list per problem ({P}, the first dimension of part), got {tuple(t.shape)}")
+    tiles = (N + MMD_TILE - 1) // MMD_TILE
+    if tuple(part.shape) != (P, tiles, B):
+        raise ValueError(f"part must be [P, {tiles}, {B}], got {tuple(part.shape)}")
+    _need_gpu(q=q, x=x, part=part, qi=qi, xi=xi)
+    kparams = (ctypes.c_double * 2)(float(gamma), float(coef0))
+    _lib.check(_lib_().vtp_mmd_poly_part(_p(q), q.stride(0), q.shape[0], _p(qi), _p(x), x.stride(0), x.shape[0], _p(xi), int(query_base),
+                                         int(index_base), B, N, D, P, ctypes.cast(kparams, ctypes.c_void_p), int(degree), _p(part),
+                                         part.numel() * 8, _s()), "vtp_mmd_poly_part")
+
+
+def mmd_fold(part, rowsum):
+    """rowsum f64 [P, B] += part f64 [P, tiles, B] summed over the tiles in ascending order, one owner thread per element"""
+    _need(part, "part", torch.float64, dims=3)
+    P, tiles, B = part.shape
+    _need(rowsum, "rowsum", torch.float64, (P, B))
+    _need_gpu(part=part, rowsum=rowsum)
+    _lib.check(_lib_().vtp_mmd_fold(_p(part), _p(rowsum), B, tiles, P, _s()), "vtp_mmd_fold")
+
+
+def mmd_total(rowsum, total):
+    """total f64 [P] = the sum of each row of rowsum f64 [P, B] by the tree that pairs neighbours level by level: its shape depends
+    on B alone"""
+    _need(rowsum, "rowsum", torch.float64, dims=2)
+    P, B = rowsum.shape
+    _need(total, "total", torch.float64, (P,))
+    _need_gpu(rowsum=rowsum, total=total)
+    _lib.check(_lib_().vtp_mmd_total(_p(rowsum), B, P, _p(total), _s()), "vtp_mmd_total")
+
+
 RETR_MAX_KS = 8  # recall levels per retr_count call
 
 

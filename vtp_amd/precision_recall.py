@@ -133,6 +133,11 @@ class PrecisionRecall:
             out[s] = torch.cat([p[:n] for p, n in zip(self._all_gather(shard), sizes)])
         return out
 
+    def gathered(self) -> Dict[str, torch.Tensor]:
+        """{"real", "fake"}: both banks of the whole group, rank-major, f32 [N, D] on the device (this rank's rows without a group):
+        what result() evaluates, for an evaluation that shares these banks (vtp_amd.KID)"""
+        return self._gathered()
+
     # ------------------------------------------------------------------------------------------------ evaluation
     def _workspace(self, B: int) -> torch.Tensor:
         need = ops.pr_workspace_bytes(B)
