@@ -344,7 +344,7 @@ def test_gen_eval_reports_kid_on_the_rows_it_feeds(monkeypatch):
     args = dict(subsets=3, subset_size=30, seed=2)
     want = feed(KID(**args), i, False).result()
     shared = make(k=3, kid=args)
-    assert shared.kid._banks is shared.pr  # one copy of the rows
+    assert all(shared.kid.rows(s).data_ptr() == shared.pr.rows(s).data_ptr() for s in ("real", "fake"))  # one copy of the rows
     out = shared.results("eig")
     assert set(out) == {"fid", "sfid", "precision", "recall", "kid", "kid_std"}
     assert {k: out[k] for k in ("kid", "kid_std")} == want

@@ -287,7 +287,7 @@ def test_through_the_class():
         knn.update_features(qs, targets.to(DEV))
     knn.add_bank_features(xs[100:1901], labels[100:1901].to(DEV))
     knn.add_bank_features(xs[1901:], labels[1901:].to(DEV))
-    assert knn.size == N and knn.bank.shape == (N, D) and knn._bank.shape[0] == 4096
+    assert knn.size == N and knn.bank.shape == (N, D) and knn.capacity == 4096
     ref = Knn(None, num_classes=C, ks=ks, temperature=T)
     ref.add_bank_features(F.normalize(xs, dim=1), labels.to(DEV))
     # a priori: a computed norm is within gamma_{D+2} of the true one and the division rounds once more, so normalising a normalised

@@ -32,7 +32,8 @@ from typing import Dict, Optional
 import torch
 
 from . import ops
-from .precision_recall import SETS, PrecisionRecall
+from .banks import BankSet, Group, eval_device, spans
+from .precision_recall import SETS, PrecisionRecall, bank_rows, gathered_rows
 
 PASSES = (("real", "real"), ("fake", "fake"), ("real", "fake"))  # (queries, bank) of the three sweeps: Sxx, Syy, Sxy
 
@@ -66,41 +67,40 @@ class KID:
             raise ValueError(f"banks must be a PrecisionRecall, got {type(banks)}")
         if banks is not None and (group is not None or capacity is not None):
             raise ValueError("group and capacity belong to the PrecisionRecall whose banks are shared")
-        if not torch.cuda.is_available():
-            raise RuntimeError("vtp_amd.KID runs on the MI355X kernels only (no CPU fallback)")
+        self.device = eval_device("KID", None, banks.device if banks is not None else device)
         self.subsets, self.subset_size, self.degree = int(subsets), int(subset_size), int(degree)
         self.gamma, self.coef0, self.seed = gamma, float(coef0), int(seed)
         self.chunk_rows = (int(chunk_rows) + ops.MMD_TILE - 1) // ops.MMD_TILE * ops.MMD_TILE
         self.query_rows = int(query_rows)
         self._shared = banks is not None
-        self._banks = banks if self._shared else PrecisionRecall(k=1, group=group, device=device, capacity=capacity)
-        self.device = self._banks.device
+        self._group = Group(banks.group if self._shared else group)
+        self.banks = banks.banks if self._shared else BankSet(SETS, self.device, capacity)  # rows as given
         self._rowsums: Dict[str, torch.Tensor] = {}
         self._tables = (None, None)  # (the arguments of the last draws, their tables on the device)
 
     # ------------------------------------------------------------------------------------------------ banks
-    def _own(self) -> PrecisionRecall:
+    def _add(self, which: str, feats: torch.Tensor) -> None:
         if self._shared:
             raise RuntimeError("this KID reads the banks of a PrecisionRecall: add the rows there")
         self._rowsums = {}
-        return self._banks
+        self.banks.append(which, feats, f"{which} features")
 
     def add_real_features(self, feats: torch.Tensor) -> None:
         """appends the rows of feats [n, D] to the real bank: device only"""
-        self._own().add_real_features(feats)
+        self._add("real", feats)
 
     def add_fake_features(self, feats: torch.Tensor) -> None:
         """appends the rows of feats [n, D] to the bank of generated samples: device only"""
-        self._own().add_fake_features(feats)
+        self._add("fake", feats)
 
     def rows(self, which: str) -> torch.Tensor:
         """this rank's rows of a bank, f32 [size, D] (a view)"""
-        return self._banks.rows(which)
+        return bank_rows(self.banks, which)
 
     def reset(self) -> None:
         """empties both banks (shared banks are their owner's to empty) and forgets the last result"""
         if not self._shared:
-            self._banks.reset()
+            self.banks.clear()
         self._rowsums = {}
 
     # ------------------------------------------------------------------------------------------------ evaluation
@@ -136,10 +136,8 @@ class KID:
         for i, (qs, xs) in enumerate(PASSES):
             q, bank = x[qs], x[xs]
             rowsum = torch.zeros(1, q.shape[0], device=self.device, dtype=torch.float64)
-            for b0 in range(0, q.shape[0], self.query_rows):
-                b1 = min(q.shape[0], b0 + self.query_rows)
-                for n0 in range(0, bank.shape[0], self.chunk_rows):
-                    n1 = min(bank.shape[0], n0 + self.chunk_rows)
+            for b0, b1 in spans(q.shape[0], self.query_rows):
+                for n0, n1 in spans(bank.shape[0], self.chunk_rows):
                     tiles = (n1 - n0 + ops.MMD_TILE - 1) // ops.MMD_TILE
                     part = ws[:tiles * (b1 - b0)].view(1, tiles, b1 - b0)
                     ops.mmd_poly_part(q[b0:b1], bank[n0:n1], part, gamma, self.coef0, self.degree, query_base=b0 if qs == xs else -1,
@@ -152,7 +150,7 @@ class KID:
     def result(self) -> Dict[str, float]:
         """{"kid": the mean of the subsets' MMD^2_u, "kid_std": their population standard deviation}, or with subsets = 0 {"kid": the
         MMD^2_u of the whole sets}; recomputed from the banks, one copy to the host"""
-        x = self._banks.gathered()
+        x = gathered_rows(self.banks, self._group)
         nr, nf = x["real"].shape[0], x["fake"].shape[0]
         if self.subsets:
             m = self.subset_size

@@ -26,6 +26,7 @@ from typing import Callable, Dict, Optional, Sequence, Tuple
 import torch
 
 from . import ops
+from .banks import Bank, Group, Workspace, eval_device, feature_rows, spans
 from .zeroshot import percent
 
 
@@ -45,6 +46,16 @@ def check_ks(ks: Sequence[int]) -> Tuple[int, ...]:
     return ks
 
 
+def neighbour_lists(q: torch.Tensor, x: torch.Tensor, k: int, ws: Workspace, query_rows: int, chunk_rows: int, splits: int,
+                    sims: torch.Tensor, idx: torch.Tensor) -> None:
+    """merges the bank rows x [N, D] into the neighbour lists sims f32 [B, k] / idx int64 [B, k] of the queries q [B, D], which
+    start out (-inf, -1): passes of query_rows queries over chunks of chunk_rows bank rows"""
+    for b0, b1 in spans(q.shape[0], query_rows):
+        buf = ws.at_least(ops.knn_workspace_bytes(b1 - b0, k, splits))
+        for n0, n1 in spans(x.shape[0], chunk_rows):
+            ops.knn_topk(q[b0:b1], x[n0:n1], n0, k, sims[b0:b1], idx[b0:b1], buf, splits)
+
+
 class Knn:
     """model: a vtp_amd.VTPModel, or None when features are given (add_bank_features / update_features).  feature_fn(model, images)
     -> [B, D] replaces the class token after the final norm.  capacity: bank rows to allocate up front (the buffer doubles when it
@@ -61,29 +72,16 @@ class Knn:
             raise ValueError(f"temperature must be positive, got {temperature}")
         if chunk_rows < 1 or query_rows < 1 or (capacity is not None and capacity < 1):
             raise ValueError("chunk_rows, query_rows and capacity must be positive")
-        if not torch.cuda.is_available():
-            raise RuntimeError("vtp_amd.Knn runs on the MI355X kernels only (no CPU fallback)")
+        self.device = eval_device("Knn", model, device)
         self.model, self.group = model, group
         self.num_classes, self.temperature = int(num_classes), float(temperature)
         self.feature_fn = feature_fn or cls_feature
         self.chunk_rows, self.query_rows = int(chunk_rows), int(query_rows)
-        if device is None:
-            device = next(model.parameters()).device if model is not None else torch.device("cuda", torch.cuda.current_device())
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("vtp_amd.Knn runs on the MI355X kernels only: the model / device must be cuda (no CPU fallback)")
-        self.world = 1
-        if group is not None:
-            import torch.distributed as dist
-            self._dist = dist
-            self.world = dist.get_world_size(group)
-        self._capacity0 = capacity
-        self._bank: Optional[torch.Tensor] = None    # f32 [capacity, D], normalised rows
-        self._labels: Optional[torch.Tensor] = None  # i32 [capacity]
-        self.size = 0                                # bank rows in use
-        self._frozen = False                         # an update has seen the bank
+        self._group = Group(group)
+        self._bank = Bank(self.device, capacity, {"labels": torch.int32})  # the normalised rows and their labels
+        self._frozen = False  # an update has seen the bank
         self._counts = torch.zeros(len(self.ks), 3, device=self.device, dtype=torch.int64)  # per k: top-1 hits, top-5 hits, rows
-        self._ws: Optional[torch.Tensor] = None
+        self._ws = Workspace(self.device)
 
     # ------------------------------------------------------------------------------------------------ features
     def _features(self, images: torch.Tensor) -> torch.Tensor:
@@ -93,18 +91,6 @@ class Knn:
             raise ValueError("images must live on the MI355X (got a CPU tensor): there is no CPU path")
         with torch.no_grad():
             return self.feature_fn(self.model, images)
-
-    def _rows(self, feats: torch.Tensor, what: str) -> torch.Tensor:
-        if not isinstance(feats, torch.Tensor) or not feats.is_cuda:
-            raise ValueError(f"{what} must live on the MI355X (got a CPU tensor): there is no CPU path")
-        if feats.dim() != 2 or feats.shape[0] < 1 or feats.shape[1] % 8:
-            raise ValueError(f"{what} must be [n, D] with n >= 1 and D a multiple of 8, got {tuple(feats.shape)}")
-        if self._bank is not None and feats.shape[1] != self._bank.shape[1]:
-            raise ValueError(f"{what} must be [n, {self._bank.shape[1]}] like the bank, got {tuple(feats.shape)}")
-        f = feats.detach().to(torch.float32)
-        if f.stride(1) != 1 or f.stride(0) % 4 or f.data_ptr() % 16:
-            f = f.contiguous()
-        return f
 
     def _ints(self, t: torch.Tensor, n: int, what: str) -> torch.Tensor:
         if not isinstance(t, torch.Tensor) or not t.is_cuda:
@@ -121,35 +107,28 @@ class Knn:
         """appends the normalised rows of feats [n, D] and their labels [n] to the bank: device only"""
         if self._frozen:
             raise RuntimeError("the bank has been evaluated against: reset() before adding to it")
-        f = self._rows(feats, "bank features")
+        f = feature_rows(feats, "bank features", self._bank.width, align=True)
         n, D = f.shape
         y = self._ints(labels, n, "bank labels").to(torch.int32)
-        if self._bank is None or self.size + n > self._bank.shape[0]:
-            cap = self._bank.shape[0] if self._bank is not None else max(self._capacity0 or 0, 1)
-            while cap < self.size + n:
-                cap *= 2
-            bank = torch.empty(cap, D, device=self.device, dtype=torch.float32)
-            lab = torch.empty(cap, device=self.device, dtype=torch.int32)
-            if self.size:
-                bank[:self.size].copy_(self._bank[:self.size])
-                lab[:self.size].copy_(self._labels[:self.size])
-            self._bank, self._labels = bank, lab
-        ops.zs_class_mean(f, self._bank[self.size:self.size + n], n, 1, D, 1e-12)  # F.normalize of every row (T = 1)
-        self._labels[self.size:self.size + n].copy_(y)
-        self.size += n
+        rows, lab = self._bank.reserve(n, D)
+        ops.zs_class_mean(f, rows, n, 1, D, 1e-12)  # F.normalize of every row (T = 1)
+        lab.copy_(y)
+
+    size = property(lambda self: self._bank.size, doc="bank rows in use")
+    capacity = property(lambda self: self._bank.capacity, doc="bank rows allocated")
 
     @property
     def bank(self) -> torch.Tensor:
         """the normalised bank rows in use, f32 [size, D] (a view)"""
-        if self._bank is None:
+        if not self.size:
             raise RuntimeError("the bank is empty: add_bank / add_bank_features first")
-        return self._bank[:self.size]
+        return self._bank.rows
 
     @property
     def bank_labels(self) -> torch.Tensor:
-        if self._labels is None:
+        if not self.size:
             raise RuntimeError("the bank is empty: add_bank / add_bank_features first")
-        return self._labels[:self.size]
+        return self._bank.column("labels")
 
     # ------------------------------------------------------------------------------------------------ evaluation
     def update(self, images: torch.Tensor, targets: torch.Tensor) -> None:
@@ -165,7 +144,7 @@ class Knn:
         K, nk = self.ks[-1], len(self.ks)
         if self.size < K:
             raise RuntimeError(f"the bank holds {self.size} rows, fewer than max(ks) = {K}")
-        f = self._rows(feats, "query features")
+        f = feature_rows(feats, "query features", self._bank.width, align=True)
         B, D = f.shape
         y = self._ints(targets, B, "targets").to(torch.int64).contiguous()
         for name, t, shape, dt in (("sims_out", sims_out, (B, K), torch.float32), ("idx_out", idx_out, (B, K), torch.int64),
@@ -179,24 +158,12 @@ class Knn:
         idx = idx_out if idx_out is not None else torch.empty(B, K, device=self.device, dtype=torch.int64)
         sims.fill_(float("-inf"))  # (-inf, -1): an empty entry
         idx.fill_(-1)
-        for b0 in range(0, B, self.query_rows):
-            b1 = min(B, b0 + self.query_rows)
-            need = ops.knn_workspace_bytes(b1 - b0, K, splits)
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = torch.empty(need, device=self.device, dtype=torch.uint8)
-            for n0 in range(0, self.size, self.chunk_rows):
-                n1 = min(self.size, n0 + self.chunk_rows)
-                ops.knn_topk(q[b0:b1], self._bank[n0:n1], n0, K, sims[b0:b1], idx[b0:b1], self._ws, splits)
-        ops.knn_vote(sims, idx, self._labels[:self.size], y, self.ks, 1.0 / self.temperature, self.num_classes, self._counts, rank_out,
-                     pred_out)
+        neighbour_lists(q, self._bank.rows, K, self._ws, self.query_rows, self.chunk_rows, splits, sims, idx)
+        ops.knn_vote(sims, idx, self.bank_labels, y, self.ks, 1.0 / self.temperature, self.num_classes, self._counts, rank_out, pred_out)
 
     def counts(self) -> Dict[int, Tuple[int, int, int]]:
         """{k: (top-1 hits, top-5 hits, rows seen)}, summed over the process group with one all-reduce; one copy to the host"""
-        c = self._counts
-        if self.world > 1:
-            c = c.clone()
-            self._dist.all_reduce(c, group=self.group)
-        c = c.cpu()
+        c = self._group.summed(self._counts).cpu()
         return {k: (int(c[m, 0]), int(c[m, 1]), int(c[m, 2])) for m, k in enumerate(self.ks)}
 
     def accuracy(self) -> Dict[int, Tuple[float, float]]:

@@ -27,8 +27,26 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import ops
+from .banks import BankSet, Group, Workspace, eval_device, spans
 
 SETS = ("real", "fake")
+
+
+def bank_rows(banks: BankSet, which: str) -> torch.Tensor:
+    """this rank's rows of the real or the generated bank, f32 [size, D] (a view)"""
+    if not banks[which].size:
+        raise RuntimeError(f"the {which} bank is empty: add_{which}_features first")
+    return banks[which].rows
+
+
+def gathered_rows(banks: BankSet, group: Group) -> Dict[str, torch.Tensor]:
+    """{"real", "fake"}: both banks of the whole group, rank-major (this rank's rows without a group, where an empty bank raises)"""
+    if group.world == 1:
+        return {s: bank_rows(banks, s) for s in SETS}
+    rows, _, totals = banks.gathered(group)
+    if not any(totals.values()):
+        raise RuntimeError("both banks are empty on every rank: add_real_features / add_fake_features first")
+    return rows
 
 
 class PrecisionRecall:
@@ -42,51 +60,24 @@ class PrecisionRecall:
             raise ValueError(f"k must be 1 .. {ops.PR_MAX_K}, got {k}")
         if chunk_rows < 1 or query_rows < 1 or (capacity is not None and capacity < 1):
             raise ValueError("chunk_rows, query_rows and capacity must be positive")
-        if not torch.cuda.is_available():
-            raise RuntimeError("vtp_amd.PrecisionRecall runs on the MI355X kernels only (no CPU fallback)")
+        self.device = eval_device("PrecisionRecall", None, device)
         self.k, self.group = int(k), group
         self.chunk_rows, self.query_rows = int(chunk_rows), int(query_rows)
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if self.device.type != "cuda":
-            raise RuntimeError("vtp_amd.PrecisionRecall runs on the MI355X kernels only: the device must be cuda (no CPU fallback)")
-        self.world = 1
-        if group is not None:
-            import torch.distributed as dist
-            self._dist = dist
-            self.world = dist.get_world_size(group)
-        self._capacity0 = capacity
-        self._ws: Optional[torch.Tensor] = None
+        self._group = Group(group)
+        self.banks = BankSet(SETS, self.device, capacity)  # rows as given
+        self._ws = Workspace(self.device)
         self.reset()
 
     def reset(self) -> None:
         """empties both banks and forgets the last result"""
-        self._bank: Dict[str, Optional[torch.Tensor]] = {s: None for s in SETS}  # f32 [capacity, D], rows as given
-        self._size = {s: 0 for s in SETS}
+        self.banks.clear()
         self._radii: Dict[str, torch.Tensor] = {}
         self._hits: Dict[str, torch.Tensor] = {}
         self._covered: Optional[torch.Tensor] = None  # int64 [2] on the device: covered fake rows, covered real rows
 
     # ------------------------------------------------------------------------------------------------ banks
     def _add(self, which: str, feats: torch.Tensor) -> None:
-        if not isinstance(feats, torch.Tensor) or not feats.is_cuda:
-            raise ValueError(f"{which} features must live on the MI355X (got a CPU tensor): there is no CPU path")
-        if feats.dim() != 2 or feats.shape[0] < 1 or feats.shape[1] < 8 or feats.shape[1] % 8:
-            raise ValueError(f"{which} features must be [n, D] with n >= 1 and D a multiple of 8, got {tuple(feats.shape)}")
-        n, D = feats.shape
-        for s in SETS:
-            if self._bank[s] is not None and self._bank[s].shape[1] != D:
-                raise ValueError(f"{which} features must be [n, {self._bank[s].shape[1]}] like the {s} bank, got {tuple(feats.shape)}")
-        bank, size = self._bank[which], self._size[which]
-        if bank is None or size + n > bank.shape[0]:
-            cap = bank.shape[0] if bank is not None else max(self._capacity0 or 0, 1)
-            while cap < size + n:
-                cap *= 2
-            grown = torch.empty(cap, D, device=self.device, dtype=torch.float32)
-            if size:
-                grown[:size].copy_(bank[:size])
-            self._bank[which] = bank = grown
-        bank[size:size + n].copy_(feats.detach())
-        self._size[which] = size + n
+        self.banks.append(which, feats, f"{which} features")
         self._radii, self._hits, self._covered = {}, {}, None
 
     def add_real_features(self, feats: torch.Tensor) -> None:
@@ -99,76 +90,34 @@ class PrecisionRecall:
 
     def rows(self, which: str) -> torch.Tensor:
         """this rank's rows of a bank, f32 [size, D] (a view)"""
-        if self._bank[which] is None:
-            raise RuntimeError(f"the {which} bank is empty: add_{which}_features first")
-        return self._bank[which][:self._size[which]]
-
-    def _all_gather(self, t: torch.Tensor) -> list:
-        """t of every rank, in rank order (the gloo backend gathers host tensors only: staged through the host there)"""
-        host = self._dist.get_backend(self.group) == "gloo"
-        src = t.cpu() if host else t
-        parts = [torch.empty_like(src) for _ in range(self.world)]
-        self._dist.all_gather(parts, src, group=self.group)
-        return [p.to(self.device) for p in parts] if host else parts
-
-    def _gathered(self) -> Dict[str, torch.Tensor]:
-        """both banks of the whole group, rank-major: the row counts are exchanged, the shards padded to the largest and gathered"""
-        if self.world == 1:
-            return {s: self.rows(s) for s in SETS}
-        D = next((b.shape[1] for b in self._bank.values() if b is not None), 0)
-        mine = torch.tensor([self._size["real"], self._size["fake"], D], device=self.device, dtype=torch.int64)
-        every = torch.stack(self._all_gather(mine)).cpu()
-        widths = {int(d) for d in every[:, 2] if int(d)}
-        if len(widths) > 1:
-            raise ValueError(f"the ranks hold features of different widths: {sorted(widths)}")
-        if not widths:
-            raise RuntimeError("both banks are empty on every rank: add_real_features / add_fake_features first")
-        D = widths.pop()
-        out = {}
-        for c, s in enumerate(SETS):
-            sizes = [int(n) for n in every[:, c]]
-            shard = torch.zeros(max(max(sizes), 1), D, device=self.device, dtype=torch.float32)
-            if self._size[s]:
-                shard[:self._size[s]].copy_(self.rows(s))
-            out[s] = torch.cat([p[:n] for p, n in zip(self._all_gather(shard), sizes)])
-        return out
+        return bank_rows(self.banks, which)
 
     def gathered(self) -> Dict[str, torch.Tensor]:
         """{"real", "fake"}: both banks of the whole group, rank-major, f32 [N, D] on the device (this rank's rows without a group):
         what result() evaluates, for an evaluation that shares these banks (vtp_amd.KID)"""
-        return self._gathered()
+        return gathered_rows(self.banks, self._group)
 
     # ------------------------------------------------------------------------------------------------ evaluation
-    def _workspace(self, B: int) -> torch.Tensor:
-        need = ops.pr_workspace_bytes(B)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, device=self.device, dtype=torch.uint8)
-        return self._ws
-
     def _radii_of(self, x: torch.Tensor, xn: torch.Tensor) -> torch.Tensor:
         """the squared distance of every row of x to its k-th nearest other row"""
         n = x.shape[0]
         dist = torch.full((n, ops.PR_MAX_K), float("inf"), device=self.device, dtype=torch.float32)
-        for b0 in range(0, n, self.query_rows):
-            b1 = min(n, b0 + self.query_rows)
-            ws = self._workspace(b1 - b0)
-            for n0 in range(0, n, self.chunk_rows):
-                n1 = min(n, n0 + self.chunk_rows)
+        for b0, b1 in spans(n, self.query_rows):
+            ws = self._ws.at_least(ops.pr_workspace_bytes(b1 - b0))
+            for n0, n1 in spans(n, self.chunk_rows):
                 ops.pr_knn_dist(x[b0:b1], xn[b0:b1], x[n0:n1], xn[n0:n1], dist[b0:b1], ws, query_base=b0, index_base=n0)
         return dist[:, self.k - 1].contiguous()
 
     def _hits_of(self, q: torch.Tensor, qn: torch.Tensor, x: torch.Tensor, xn: torch.Tensor, r2: torch.Tensor) -> torch.Tensor:
         """per row of q the number of rows of x whose ball holds it"""
         hits = torch.zeros(q.shape[0], device=self.device, dtype=torch.int32)
-        for b0 in range(0, q.shape[0], self.query_rows):
-            b1 = min(q.shape[0], b0 + self.query_rows)
-            for n0 in range(0, x.shape[0], self.chunk_rows):
-                n1 = min(x.shape[0], n0 + self.chunk_rows)
+        for b0, b1 in spans(q.shape[0], self.query_rows):
+            for n0, n1 in spans(x.shape[0], self.chunk_rows):
                 ops.pr_cover(q[b0:b1], qn[b0:b1], x[n0:n1], xn[n0:n1], r2[n0:n1], hits[b0:b1])
         return hits
 
     def _compute(self) -> None:
-        x = self._gathered()
+        x = self.gathered()
         for s in SETS:
             if x[s].shape[0] < self.k + 1:
                 raise RuntimeError(f"the {s} set holds {x[s].shape[0]} rows, fewer than k + 1 = {self.k + 1}: its radii would be infinite")

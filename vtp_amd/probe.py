@@ -15,6 +15,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import ops
+from .banks import Group, eval_device
 
 DEFAULT_LEARNING_RATES = (1e-5, 2e-5, 5e-5, 1e-4, 2e-4, 5e-4, 1e-3, 2e-3, 5e-3, 1e-2, 2e-2, 5e-2, 0.1)  # the tool's sweep (:61-64)
 Head = Tuple[str, int, bool, float]  # (key, use_n_blocks, use_avgpool, lr)
@@ -78,8 +79,7 @@ class LinearProbe:
 
     def __init__(self, model, heads: Sequence[Head], num_classes: int, momentum: float = 0.9, max_iter: Optional[int] = None,
                  group=None, *, embed_dim: Optional[int] = None, device=None):
-        if not torch.cuda.is_available():
-            raise RuntimeError("vtp_amd.LinearProbe runs on the MI355X kernels only (no CPU fallback)")
+        self.device = eval_device("LinearProbe", model, device)
         self.model = model
         self.D = int(embed_dim if embed_dim is not None else model.config.vision_embed_dim)
         if self.D % 4:
@@ -87,16 +87,8 @@ class LinearProbe:
         if max_iter is not None and max_iter < 1:
             raise ValueError("max_iter must be >= 1 (or None for constant learning rates)")
         self.C, self.momentum, self.max_iter, self.group = int(num_classes), float(momentum), max_iter, group
-        if device is None:
-            device = next(model.parameters()).device if model is not None else torch.device("cuda", torch.cuda.current_device())
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("vtp_amd.LinearProbe runs on the MI355X kernels only: the model / device must be cuda (no CPU fallback)")
-        self.world, self.rank = 1, 0
-        if group is not None:
-            import torch.distributed as dist
-            self._dist = dist
-            self.world, self.rank = dist.get_world_size(group), dist.get_rank(group)
+        self._group = Group(group)
+        self.world, self.rank = self._group.world, self._group.rank
         heads = list(heads)
         kept = resolve_heads(heads)
         if not kept:
@@ -173,13 +165,14 @@ class LinearProbe:
 
     def _all_gather_rows(self, out: torch.Tensor, inp: torch.Tensor):
         """rows of every rank in rank order: RCCL all-gather, or all_reduce on backends without it (VTPTrainer._all_gather_rows)"""
-        if self._dist.get_backend(self.group) == "nccl":
-            self._dist.all_gather_into_tensor(out, inp, group=self.group)
+        dist = self._group.dist
+        if dist.get_backend(self.group) == "nccl":
+            dist.all_gather_into_tensor(out, inp, group=self.group)
         else:
             B = inp.shape[0]
             out.zero_()
             out[self.rank * B:(self.rank + 1) * B].copy_(inp)
-            self._dist.all_reduce(out, group=self.group)
+            dist.all_reduce(out, group=self.group)
 
     # ------------------------------------------------------------------------------------------------ training
     def learning_rates(self, step: Optional[int] = None) -> Dict[str, float]:
@@ -214,7 +207,7 @@ class LinearProbe:
             ops.probe_sgd(g.weight, g.bias, g.m_weight, g.m_bias, dlogits, x_all[:, g.col0:g.col0 + g.K], g.lr, B * self.world, g.H,
                           self.C, g.K, self.momentum)
         if self.world > 1:
-            self._dist.all_reduce(losses, group=self.group)
+            self._group.dist.all_reduce(losses, group=self.group)
         self.steps += 1
         return losses
 
@@ -238,9 +231,7 @@ class LinearProbe:
     def counts(self) -> Tuple[torch.Tensor, int]:
         """(correct per head as a CPU int64 tensor, rows seen), summed over the process group with one all-reduce"""
         c = torch.cat([self._correct.to(torch.int64), torch.tensor([self._total], device=self.device, dtype=torch.int64)])
-        if self.world > 1:
-            self._dist.all_reduce(c, group=self.group)
-        c = c.cpu()
+        c = self._group.summed(c).cpu()
         return c[:-1], int(c[-1])
 
     def accuracies(self) -> Dict[str, float]:

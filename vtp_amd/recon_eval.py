@@ -23,6 +23,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import ops
+from .banks import Group, eval_device
 from .tokenizer import NORMALIZE_IMAGENET
 
 ACC_SLOTS = 8  # the accumulator block of vtp_recon_finalize (include/vtp_hip.h)
@@ -82,19 +83,9 @@ class ReconEval:
     None; with one, every update feeds it the byte images and results() has 'fid'."""
 
     def __init__(self, model, lpips=None, group=None, device=None, fid=None):
-        if not torch.cuda.is_available():
-            raise RuntimeError("vtp_amd.ReconEval runs on the MI355X kernels only (no CPU fallback)")
+        self.device = eval_device("ReconEval", model, device)
         self.model, self.lpips, self.group, self.fid = model, lpips, group, fid
-        if device is None:
-            device = next(model.parameters()).device if model is not None else torch.device("cuda", torch.cuda.current_device())
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("vtp_amd.ReconEval runs on the MI355X kernels only: the model / device must be cuda (no CPU fallback)")
-        self.world = 1
-        if group is not None:
-            import torch.distributed as dist
-            self._dist = dist
-            self.world = dist.get_world_size(group)
+        self._group = Group(group)
         mean, std = NORMALIZE_IMAGENET["mean"], NORMALIZE_IMAGENET["std"]
         self.sub = [-m / s for m, s in zip(mean, std)]  # transform_rev (:265-268)
         self.div = [1 / s for s in std]
@@ -152,11 +143,7 @@ class ReconEval:
 
     def accumulators(self) -> torch.Tensor:
         """the accumulator block, summed over the process group with one all-reduce; one copy to the host (CPU f64 [8])"""
-        t = self._acc
-        if self.world > 1:
-            t = t.clone()
-            self._dist.all_reduce(t, group=self.group)
-        return t.cpu()
+        return self._group.summed(self._acc).cpu()
 
     def results(self) -> dict:
         res = aggregate(self.accumulators().tolist(), self.lpips is not None)

@@ -37,6 +37,8 @@ from typing import Callable, Dict, Optional, Sequence, Tuple
 import torch
 
 from . import ops
+from .banks import BankSet, Group, Workspace, eval_device, feature_rows, spans
+from .knn import neighbour_lists
 from .zeroshot import percent
 
 SIDES = ("image", "text")
@@ -73,30 +75,18 @@ class Retrieval:
         self.ks = check_ks(ks)
         if chunk_rows < 1 or query_rows < 1 or (capacity is not None and capacity < 1):
             raise ValueError("chunk_rows, query_rows and capacity must be positive")
-        if not torch.cuda.is_available():
-            raise RuntimeError("vtp_amd.Retrieval runs on the MI355X kernels only (no CPU fallback)")
+        self.device = eval_device("Retrieval", model, device)
         self.model, self.group = model, group
         self.feature_fn = {"image": image_feature_fn or clip_image_feature, "text": text_feature_fn or clip_text_feature}
         self.chunk_rows, self.query_rows = int(chunk_rows), int(query_rows)
-        if device is None:
-            device = next(model.parameters()).device if model is not None else torch.device("cuda", torch.cuda.current_device())
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("vtp_amd.Retrieval runs on the MI355X kernels only: the model / device must be cuda (no CPU fallback)")
-        self.world = 1
-        if group is not None:
-            import torch.distributed as dist
-            self._dist = dist
-            self.world = dist.get_world_size(group)
-        self._capacity0 = capacity
-        self._ws: Optional[torch.Tensor] = None
+        self._group = Group(group)
+        self.banks = BankSet(SIDES, self.device, capacity, {"ids": torch.int64})  # rows as given, and the image id of every row
+        self._ws = Workspace(self.device)
         self.reset()
 
     def reset(self) -> None:
         """empties both banks and forgets the last result"""
-        self._bank: Dict[str, Optional[torch.Tensor]] = {s: None for s in SIDES}  # f32 [capacity, D], rows as given
-        self._ids: Dict[str, Optional[torch.Tensor]] = {s: None for s in SIDES}   # int64 [capacity]: the image id of every row
-        self._size = {s: 0 for s in SIDES}
+        self.banks.clear()
         self._forget()
 
     def _forget(self) -> None:
@@ -122,29 +112,12 @@ class Retrieval:
             raise ValueError(f"the image ids of the {side} rows must be {n} integers, got {image_ids.dtype} {tuple(image_ids.shape)}")
 
     def _add(self, side: str, feats: torch.Tensor, image_ids: torch.Tensor) -> None:
-        if not isinstance(feats, torch.Tensor) or not feats.is_cuda:
-            raise ValueError(f"{side} features must live on the MI355X (got a CPU tensor): there is no CPU path")
-        if feats.dim() != 2 or feats.shape[0] < 1 or feats.shape[1] < 8 or feats.shape[1] % 8:
-            raise ValueError(f"{side} features must be [n, D] with n >= 1 and D a multiple of 8, got {tuple(feats.shape)}")
-        n, D = feats.shape
-        for s in SIDES:
-            if self._bank[s] is not None and self._bank[s].shape[1] != D:
-                raise ValueError(f"{side} features must be [n, {self._bank[s].shape[1]}] like the {s} bank, got {tuple(feats.shape)}")
-        self._check_ids(side, image_ids, n)
-        bank, size = self._bank[side], self._size[side]
-        if bank is None or size + n > bank.shape[0]:
-            cap = bank.shape[0] if bank is not None else max(self._capacity0 or 0, 1)
-            while cap < size + n:
-                cap *= 2
-            grown = torch.empty(cap, D, device=self.device, dtype=torch.float32)
-            ids = torch.empty(cap, device=self.device, dtype=torch.int64)
-            if size:
-                grown[:size].copy_(bank[:size])
-                ids[:size].copy_(self._ids[side][:size])
-            self._bank[side], self._ids[side] = grown, ids
-        self._bank[side][size:size + n].copy_(feats.detach())  # the cast to f32
-        self._ids[side][size:size + n].copy_(image_ids.detach())
-        self._size[side] = size + n
+        f = feature_rows(feats, f"{side} features")
+        self.banks.check_width(f.shape, f"{side} features")
+        self._check_ids(side, image_ids, f.shape[0])
+        rows, ids = self.banks[side].reserve(*f.shape)
+        rows.copy_(f)
+        ids.copy_(image_ids.detach())
         self._forget()
 
     def add_images(self, images: torch.Tensor, image_ids: torch.Tensor) -> None:
@@ -164,50 +137,23 @@ class Retrieval:
 
     def rows(self, side: str) -> torch.Tensor:
         """this rank's rows of a bank ("image" / "text"), f32 [size, D] (a view)"""
-        if self._bank[side] is None:
+        if not self.banks[side].size:
             raise RuntimeError(f"the {side} bank is empty: add_{side}s / add_{side}_features first")
-        return self._bank[side][:self._size[side]]
+        return self.banks[side].rows
 
     def ids(self, side: str) -> torch.Tensor:
         """the image ids of this rank's rows of a bank, int64 [size] (a view)"""
         self.rows(side)
-        return self._ids[side][:self._size[side]]
-
-    def _all_gather(self, t: torch.Tensor) -> list:
-        """t of every rank, in rank order (the gloo backend gathers host tensors only: staged through the host there)"""
-        host = self._dist.get_backend(self.group) == "gloo"
-        src = t.cpu() if host else t
-        parts = [torch.empty_like(src) for _ in range(self.world)]
-        self._dist.all_gather(parts, src, group=self.group)
-        return [p.to(self.device) for p in parts] if host else parts
+        return self.banks[side].column("ids")
 
     def _gathered(self) -> Tuple[Dict[str, torch.Tensor], Dict[str, torch.Tensor]]:
-        """both banks and both id vectors of the whole group, rank-major: the row counts are exchanged, the shards padded to the
-        largest and gathered"""
-        if self.world == 1:
-            return {s: self.rows(s) for s in SIDES}, {s: self.ids(s) for s in SIDES}
-        D = next((b.shape[1] for b in self._bank.values() if b is not None), 0)
-        mine = torch.tensor([self._size["image"], self._size["text"], D], device=self.device, dtype=torch.int64)
-        every = torch.stack(self._all_gather(mine)).cpu()
-        widths = {int(d) for d in every[:, 2] if int(d)}
-        if len(widths) > 1:
-            raise ValueError(f"the ranks hold features of different widths: {sorted(widths)}")
-        if not widths:
-            raise RuntimeError("both banks are empty on every rank: add_images / add_texts first")
-        D = widths.pop()
-        feats, ids = {}, {}
-        for c, s in enumerate(SIDES):
-            sizes = [int(n) for n in every[:, c]]
-            if not sum(sizes):
-                raise RuntimeError(f"the {s} bank is empty on every rank: add_{s}s / add_{s}_features first")
-            shard = torch.zeros(max(sizes), D, device=self.device, dtype=torch.float32)
-            shard_ids = torch.zeros(max(sizes), device=self.device, dtype=torch.int64)
-            if self._size[s]:
-                shard[:self._size[s]].copy_(self.rows(s))
-                shard_ids[:self._size[s]].copy_(self.ids(s))
-            feats[s] = torch.cat([p[:n] for p, n in zip(self._all_gather(shard), sizes)])
-            ids[s] = torch.cat([p[:n] for p, n in zip(self._all_gather(shard_ids), sizes)])
-        return feats, ids
+        """both banks and both id vectors of the whole group, rank-major (BankSet.gathered); a bank without rows raises"""
+        rows, columns, totals = self.banks.gathered(self._group)
+        where = " on every rank" if self._group.world > 1 else ""
+        for s in SIDES:
+            if not totals[s]:
+                raise RuntimeError(f"the {s} bank is empty{where}: add_{s}s / add_{s}_features first")
+        return rows, {s: columns[s]["ids"] for s in SIDES}
 
     # ------------------------------------------------------------------------------------------------ evaluation
     def ground_truth(self, query_ids: torch.Tensor, gallery_ids: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -237,11 +183,9 @@ class Retrieval:
         rank = torch.empty(B, device=self.device, dtype=torch.int32)
         counts = torch.zeros(len(self.ks) + 1, device=self.device, dtype=torch.int64)
         beats = torch.empty(min(B, self.query_rows), device=self.device, dtype=torch.int32)
-        for b0 in range(0, B, self.query_rows):
-            b1 = min(B, b0 + self.query_rows)
+        for b0, b1 in spans(B, self.query_rows):
             pass_beats = beats[:b1 - b0].zero_()
-            for n0 in range(0, N, self.chunk_rows):
-                n1 = min(N, n0 + self.chunk_rows)
+            for n0, n1 in spans(N, self.chunk_rows):
                 ops.retr_rank(q[b0:b1], x[n0:n1], n0, best_s[b0:b1], best_j[b0:b1], pass_beats)
             ops.retr_count(pass_beats, self.ks, counts, rank, b0)
         return rank, counts
@@ -300,13 +244,5 @@ class Retrieval:
         k = int(k)
         sims = torch.full((B, k), float("-inf"), device=self.device, dtype=torch.float32)
         idx = torch.full((B, k), -1, device=self.device, dtype=torch.int64)
-        rows = min(self.query_rows, 1024)
-        for b0 in range(0, B, rows):
-            b1 = min(B, b0 + rows)
-            need = ops.knn_workspace_bytes(b1 - b0, k)
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = torch.empty(need, device=self.device, dtype=torch.uint8)
-            for n0 in range(0, N, self.chunk_rows):
-                n1 = min(N, n0 + self.chunk_rows)
-                ops.knn_topk(q[b0:b1], x[n0:n1], n0, k, sims[b0:b1], idx[b0:b1], self._ws)
+        neighbour_lists(q, x, k, self._ws, min(self.query_rows, 1024), self.chunk_rows, 0, sims, idx)
         return idx

@@ -20,6 +20,7 @@ from typing import Callable, Iterator, List, Optional, Sequence, Tuple
 import torch
 
 from . import ops
+from .banks import Group, aligned_f32, eval_device
 
 
 def caption_batches(classnames: Sequence[str], templates: Sequence[Callable[[str], str]],
@@ -48,19 +49,9 @@ class ZeroShot:
     each evaluate their own rows; counts() sums over it."""
 
     def __init__(self, model, group=None, scale: float = 100.0, device=None):
-        if not torch.cuda.is_available():
-            raise RuntimeError("vtp_amd.ZeroShot runs on the MI355X kernels only (no CPU fallback)")
+        self.device = eval_device("ZeroShot", model, device)
         self.model, self.group, self.scale = model, group, float(scale)
-        if device is None:
-            device = next(model.parameters()).device if model is not None else torch.device("cuda", torch.cuda.current_device())
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("vtp_amd.ZeroShot runs on the MI355X kernels only: the model / device must be cuda (no CPU fallback)")
-        self.world = 1
-        if group is not None:
-            import torch.distributed as dist
-            self._dist = dist
-            self.world = dist.get_world_size(group)
+        self._group = Group(group)
         self.Wt: Optional[torch.Tensor] = None  # f32 [C, D], one row per class
         self._counts = torch.zeros(3, device=self.device, dtype=torch.int64)  # top-1 hits, top-5 hits, rows
         self._per_class: Optional[torch.Tensor] = None  # i32 [2, C]: rows seen, top-1 hits
@@ -140,9 +131,7 @@ class ZeroShot:
         B = feats.shape[0]
         if targets.is_floating_point() or targets.shape != (B,):
             raise ValueError(f"targets must be {B} integer class indices, got {targets.dtype} {tuple(targets.shape)}")
-        f = feats.detach().to(torch.float32)
-        if f.stride(1) != 1 or f.stride(0) % 4 or f.data_ptr() % 16:
-            f = f.contiguous()
+        f = aligned_f32(feats)
         y = targets.detach().to(torch.int64).contiguous()
         for name, t, shape, dt in (("logits_out", logits_out, (B, C), torch.float32), ("rank_out", rank_out, (B,), torch.int32),
                                    ("pred_out", pred_out, (B, 5), torch.int32)):
@@ -152,15 +141,9 @@ class ZeroShot:
                 raise ValueError(f"{name} must be a {dt} tensor of shape {shape} on the MI355X, rows contiguous")
         ops.zs_topk(f, self.Wt, y, self.scale, B, C, D, self._counts, self._per_class, rank_out, pred_out, logits_out)
 
-    def _reduced(self, t: torch.Tensor) -> torch.Tensor:
-        if self.world > 1:
-            t = t.clone()
-            self._dist.all_reduce(t, group=self.group)
-        return t.cpu()
-
     def counts(self) -> Tuple[int, int, int]:
         """(top-1 hits, top-5 hits, rows seen), summed over the process group with one all-reduce; one copy to the host"""
-        c = self._reduced(self._counts)
+        c = self._group.summed(self._counts).cpu()
         return int(c[0]), int(c[1]), int(c[2])
 
     def accuracy(self) -> Tuple[float, float]:
@@ -172,7 +155,7 @@ class ZeroShot:
         """top-1 accuracy in percent per class (CPU f64 [C]; NaN for a class no target named)"""
         if self._per_class is None:
             raise RuntimeError("no classifier yet: build_classifier or set_classifier first")
-        pc = self._reduced(self._per_class).to(torch.float64)
+        pc = self._group.summed(self._per_class).cpu().to(torch.float64)
         return torch.where(pc[0] > 0, pc[1] / pc[0].clamp_min(1.0) * 100.0, torch.full_like(pc[0], float("nan")))
 
     def reset(self) -> None:
