@@ -23,6 +23,7 @@ import torch
 
 from . import ops
 from .ops import EPI_BF16, EPI_F32, EPI_F32_SLAB, EPI_GELU, EPI_SWIGLU
+from .wgrad import Problem, plan_block
 
 
 # =====================================================================================================================
@@ -165,7 +166,7 @@ class ParamStore:
         self._desc_dev = torch.tensor(rows, dtype=torch.int64, device=self.device)
         self._ndesc = len(rows)
         self._tiles = tiles
-        self._desc_tile0 = [r[7] for r in rows] + [tiles]
+        self._desc_tile0 = [r[-1] for r in rows] + [tiles]  # (a record's last slot: its first tile)
         self.prep()
 
     def prep(self):
@@ -226,6 +227,7 @@ class Workspace:
     def __init__(self, device):
         self.device = device
         self._bufs: Dict[tuple, torch.Tensor] = {}
+        self.wgrad_groups: Dict[tuple, object] = {}  # Stack.backward: the planned grouped weight-gradient launches over these buffers
 
     def get(self, name: str, shape, dtype, zero: bool = False) -> torch.Tensor:
         key = (name, tuple(shape), dtype)
@@ -333,62 +335,50 @@ def linear_bwd(ws: Workspace, tag: str, L, dy_b, x_b, M: int, d_in, *, need_dx: 
         gw = L.gw if gw is None else gw
         gb = L.gb if gb is None else gb
         wT = L.wT if wT is None else wT
+    c_remap = (-1, swiglu_h) if swiglu_h else (0, 0)
+
+    def wgrad(dst, accumulate: bool, colsum=None, in_gemm: bool = False):
+        """dst[N, K] (+)= dy[M, N]^T x[M, K] straight from the activation layouts (LDS transpose reads inside the GEMM), split-K into slabs;
+        colsum (f32 [N]) += the column sums of dy, by a column-sum launch beside the GEMM or (in_gemm) by the GEMM itself"""
+        if colsum is not None and not in_gemm:
+            ops.colsum_bf16(dy_b, dy_b.stride(0), colsum, M, N, swiglu_h=swiglu_h, in_remap=dy_remap)
+        kw = dict(M=N, N=K, K=M, lda=dy_b.stride(0), ldb=x_b.stride(0), ldc=K, a_remap=dy_remap, b_remap=x_remap, c_remap=c_remap,
+                  a_colsum=colsum if in_gemm else None)
+        St, n_el = ops.gemm_tn_splits(N, K, M), N * K  # tile-configuration aware (8-phase 256x256 kernel: tiles x splits = 256 CUs)
+        if St == 1:
+            ops.gemm_tn(dy_b, x_b, dst, resid=dst if accumulate else None, epi=EPI_F32, **kw)
+        else:
+            slab = ws.get("T.slab", (St * n_el,), F32)
+            ops.gemm_tn(dy_b, x_b, slab, ldc2=n_el // 4, epi=EPI_F32_SLAB, splits=St, **kw)
+            ops.reduce_slabs(slab, n_el, St, dst, n_el, accumulate=accumulate)
+
     if ls is not None:
         # y = gamma (.) (x W^T + b) (LayerScale, misc.py:24-25) and dy_b is the gradient of y: the branch output f is not stored
         # -- G = dy^T x and cs = colsum(dy) give dW = gamma (.) G, db = gamma (.) cs, dgamma = rowsum(W (.) G) + b (.) cs
         gamma, g_gamma = ls
         assert L is not None and not swiglu_h and dy_remap == (0, 0) and x_remap == (0, 0)
-        cs = ws.get("T.ls_cs", (N,), F32)
-        cs.zero_()
+        cs = ws.get("T.ls_cs", (N,), F32).zero_()
         G = ws.get("T.ls_G", (N * K,), F32)
-
-        def wgrad_ls():
-            kw = dict(M=N, N=K, K=M, lda=dy_b.stride(0), ldb=x_b.stride(0), ldc=K, a_colsum=cs)
-            St = ops.gemm_tn_splits(N, K, M)
-            if St == 1:
-                ops.gemm_tn(dy_b, x_b, G, epi=EPI_F32, **kw)
-            else:
-                slab = ws.get("T.slab", (St * N * K,), F32)
-                ops.gemm_tn(dy_b, x_b, slab, ldc2=N * K // 4, epi=EPI_F32_SLAB, splits=St, **kw)
-                ops.reduce_slabs(slab, N * K, St, G, N * K, accumulate=False)
-            ops.layerscale_wgrad(G, L.w32, L.bias, cs, gamma, gw, gb, g_gamma, N, K)
-
         OVERLAP.join()
-        wgrad_ls()
+        wgrad(G, False, cs, in_gemm=True)
+        ops.layerscale_wgrad(G, L.w32, L.bias, cs, gamma, gw, gb, g_gamma, N, K)
         if need_dx:
             ops.gemm_nt(dy_b, L.wTs, d_in, M=M, N=K, K=N, lda=dy_b.stride(0), ldb=N, ldc=d_in.stride(0), epi=EPI_BF16,
                         c_remap=dx_remap)
         return
     if bias_grad_done:  # the kernel that produced dy_b already accumulated its column sums into the bias gradient
         gb = None
-    c_remap = (-1, swiglu_h) if swiglu_h else (0, 0)
-
-    def wgrad():
-        # dW[N,K] = dy[M,N]^T x[M,K] straight from the activation layouts (LDS transpose reads inside the GEMM); db = colsum(dy) as a
-        # column-sum launch beside it
-        if gb is not None:
-            ops.colsum_bf16(dy_b, dy_b.stride(0), gb, M, N, swiglu_h=swiglu_h, in_remap=dy_remap)
-        kw = dict(M=N, N=K, K=M, lda=dy_b.stride(0), ldb=x_b.stride(0), ldc=K, a_remap=dy_remap, b_remap=x_remap, c_remap=c_remap)
-        St = ops.gemm_tn_splits(N, K, M)  # tile-configuration aware (8-phase 256x256 kernel: tiles x splits = 256 CUs)
-        if St == 1:
-            ops.gemm_tn(dy_b, x_b, gw, resid=gw, epi=EPI_F32, **kw)
-        else:
-            n_el = N * K
-            slab = ws.get("T.slab", (St * n_el,), F32)
-            ops.gemm_tn(dy_b, x_b, slab, ldc2=n_el // 4, epi=EPI_F32_SLAB, splits=St, **kw)
-            ops.reduce_slabs(slab, n_el, St, gw, n_el, accumulate=True)
-
     if defer is not None:  # grouped weight gradients: record the problem, the caller launches the block's group later
         assert dy_remap == (0, 0) and x_remap == (0, 0)
-        defer.append(dict(dy=dy_b, x=x_b, gw=gw, gb=gb, N=N, K=K, swiglu_h=swiglu_h))
+        defer.append(Problem(dy=dy_b, x=x_b, gw=gw, gb=gb, N=N, K=K, swiglu_h=swiglu_h, Ktok=M))
     elif OVERLAP.enabled and need_dx:
         OVERLAP.join()   # previous layer's dW branch is done with the shared T.* scratch (and with its inputs)
         OVERLAP.fork()   # the side stream sees dy_b / x_b complete
         with torch.cuda.stream(OVERLAP.side):
-            wgrad()
+            wgrad(gw, True, gb)
     else:
         OVERLAP.join()
-        wgrad()
+        wgrad(gw, True, gb)
     if need_dx and dgrad_swiglu is not None:
         # this linear is the w3 of a SwiGLU FFN: the dgrad GEMM's epilogue applies the activation backward with the saved x12 and
         # writes dx12 directly (d_in = the [M, 2K] pre-activation gradient); dh never exists in HBM
@@ -397,18 +387,6 @@ def linear_bwd(ws: Workspace, tag: str, L, dy_b, x_b, M: int, d_in, *, need_dx: 
     elif need_dx:
         ops.gemm_nt(dy_b, wT, d_in, M=M, N=K, K=N, lda=dy_b.stride(0), ldb=N, ldc=d_in.stride(0), epi=EPI_BF16,
                     a_remap=dy_remap, c_remap=dx_remap, m_rows=m_rows)
-
-
-class WgradGroups:
-    """several ops.WgradGroup launched back to back (the weight gradients of a block whose problems sum over different token counts,
-    where one launch cannot take them)"""
-
-    def __init__(self, parts):
-        self.parts = parts
-
-    def launch(self):
-        for g in self.parts:
-            g.launch()
 
 
 # =====================================================================================================================
@@ -523,7 +501,8 @@ class Stack:
         # gradients and runs this stack's backward ONCE before it reads them (VTPTrainer's step sets it; the autograd boundary, which
         # must accumulate like nn.Parameter.grad does, never does).  Saves the 256-KiB read of every output tile in the epilogue of the
         # step's dominant kernel: 38 -> 24 us per last-arriving workgroup (tools/wgrad_timeline.py)
-        self.wgrad_overwrite = False
+        self.wgrad_overwrite = False  # (nothing enforces the single backward while it is set: ADVICE; a pull request of its own)
+        self.wgrad_scratch: Dict[str, torch.Tensor] = {}  # partial sums / tickets shared by this stack's grouped launches
         # packed captions (TextEngine, causal + arg-max pooling): a RowPlan on the device.  Launch geometry stays that of the static
         # M = B * T; the kernels read the counts (ops: m_rows / k_rows / the varlen attention).  Set by the owner before forward() and left
         # in place for the matching backward(); None: padded rows.
@@ -794,9 +773,6 @@ class Stack:
             Mc = s.o_c.shape[0]
             d_o_c = ws.get(bt + "do", (Mc, D), BF)
             linear_bwd(ws, "proj", b.proj, dy_b, s.o_c, Mc, d_o_c, bias_grad_done=bias_done, defer=probs)
-            if probs is not None:
-                for pr in probs:  # what has been recorded so far (w3, w12, proj) sums over the compact rows
-                    pr["Ktok"] = Mc
             ops.expand_rows_bf16(d_o_c, s.row_map, d_o, M, Mc, D)
         else:
             linear_bwd(ws, "proj", b.proj, dy_b, s.o, M, d_o, bias_grad_done=bias_done,
@@ -1027,8 +1003,8 @@ class Stack:
         dy_colsum_done: the caller's norm backward already summed dy_b's columns into the last block's w3 bias gradient
         (self.blocks[-1].w3.gb as its dx_colsum).
         hold_last (grouped weight gradients only): block 0's group is neither launched nor announced here but left in self.held =
-        (0, group) -- the caller launches it and yields ("block", 0) -- and extra_last, a list of problem records {x, gw, gb, N, K,
-        swiglu_h} over the same token rows whose dy is this stack's input gradient (TrunkEngine: the patch-embed weight gradient),
+        (0, group) -- the caller launches it and yields ("block", 0) -- and extra_last, a list of wgrad.Problem records (dy and Ktok
+        unset) over the same token rows whose dy is this stack's input gradient (TrunkEngine: the patch-embed weight gradient),
         rides in that launch.
         Tail rows (the forward ran with a row plan: saved[-1].row_map is set): dy / dy_b have the Mc compact rows, and the last block's
         FFN half, its projection and their weight gradients (K = Mc token rows) run on them -- see _attn_bwd."""
@@ -1055,9 +1031,7 @@ class Stack:
         if vl is not None and not (grouped and tail_Mc is None and len(segs) == 1 and not extra_last):
             raise RuntimeError("Stack.backward: packed captions need the grouped weight gradients of one plain segment (varlen_ok)")
         par = (lambda i: f".{i & 1}") if grouped else (lambda i: "")
-        groups = ws.__dict__.setdefault("_wgrad_groups", {})
-        scratch = self.__dict__.setdefault("_wgrad_scratch", {})
-        pending = None  # (block index, ops.WgradGroup) whose launch is due
+        pending = None  # (block index, the block's planned launch: wgrad.plan_block) whose launch is due
 
         def launch_pending():
             """fork now (the side stream picks up behind the norm backward that closed the previous block); the launch itself is
@@ -1114,24 +1088,12 @@ class Stack:
                 OVERLAP.join()
                 yield ("block", i)
                 continue
-            extra = [dict(pr, dy=dy_b) for pr in extra_last] if (i == 0 and hold_last and extra_last) else []
+            extra = [pr._replace(dy=dy_b, Ktok=M) for pr in extra_last] if (i == 0 and hold_last and extra_last) else []
             gkey = (i, bool(self.wgrad_overwrite), len(extra), Mf, vl is not None)
-            grp = groups.get(gkey)
+            grp = ws.wgrad_groups.get(gkey)
             if grp is None:
-                # problems over different token counts (tail rows: proj / w12 / w3 over Mc rows beside qkv over all M) share the
-                # launch where the item-list kernel runs it, cut per problem; otherwise one group per token count, back to back
-                counts = sorted({pr.get("Ktok", M) for pr in probs + extra}, reverse=True)
-                if len(counts) > 1 and ops.wgrad_group_mixed_ok(counts):
-                    counts = [None]
-                parts = []
-                for kt in counts:
-                    g = ops.WgradGroup(M if kt is None else kt, k_rows=self.m_rows)
-                    for pr in probs + extra:
-                        if kt is None or pr.get("Ktok", M) == kt:
-                            g.add(pr["dy"], pr["x"], pr["gw"], pr["gb"], pr["N"], pr["K"], pr["swiglu_h"],
-                                  accumulate=not self.wgrad_overwrite, Ktok=pr.get("Ktok"))
-                    parts.append(g.finalize(self.store.device, scratch))
-                grp = groups[gkey] = parts[0] if len(parts) == 1 else WgradGroups(parts)
+                grp = ws.wgrad_groups[gkey] = plan_block(probs + extra, M=M, k_rows=self.m_rows, accumulate=not self.wgrad_overwrite,
+                                                         device=self.store.device, scratch=self.wgrad_scratch)
             if pending is not None:
                 yield ("block", pending[0])  # its weight gradients are complete (joined above)
             pending = (i, grp)
@@ -1522,9 +1484,8 @@ class TrunkEngine:
         g_cls, g_mask = st.g(self.prefix + "cls_token"), st.g(self.prefix + "mask_token")
         # the patch-embed weight (and bias) gradient as a fifth problem of block 0's grouped launch: dy = the stack's input gradient
         # (cls and masked rows zeroed by token_rows_bwd below, before the launch), x = the im2col rows in the token layout
-        extra = None
-        if not want_dimg and D % 8 == 0:
-            extra = [dict(x=c.patches, gw=self.pe.gw, gb=self.pe.gb, N=self.pe.N, K=self.pe.K, swiglu_h=0)]
+        extra = [Problem(dy=None, x=c.patches, gw=self.pe.gw, gb=self.pe.gb, N=self.pe.N, K=self.pe.K, swiglu_h=0,
+                         Ktok=None)] if not want_dimg and D % 8 == 0 else None  # (dy and Ktok: set where Stack.backward attaches it)
         dx0, dx0_b = yield from self.stack.backward(ws, dx, dx_b, c.stack_segs, 1, c.stack_saved,
                                                     dy_colsum_done=self.stack.w3_colsum_target(self.depth - 1) is not None,
                                                     hold_last=extra is not None, extra_last=extra)
