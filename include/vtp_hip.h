@@ -518,6 +518,43 @@ int vtp_probe_ce(const float* logits, int ldl, const long* labels, int B, int H,
 int vtp_probe_sgd(float* W, float* bias, float* mW, float* mb, const float* dlogits, int ldl, const float* X, int ldx, const float* lr,
                   int B, int H, int C, int K, float momentum, void* stream);
 
+/* ---- linear segmentation probe (segprobe.hip): a linear layer on frozen patch tokens, logits upsampled bilinearly to the label
+ * map, per-pixel cross-entropy, confusion counts for mIoU -- the protocol of the DINOv2 / iBOT papers restated (parity with their
+ * programs is unpinned).  Z f32 [M = B*h*w, H*C] (row stride ldz) are the low-resolution logits of vtp_probe_logits, token row
+ * (b, i, j) at b*h*w + i*w + j; labels u8 [B, Hl, Wl] with any Hl, Wl >= 1; 1 <= C <= 255.  A label equal to ignore_index is
+ * skipped; a label >= C that is not ignore_index is skipped too and counted as out of range.  Upsampling is ATen's
+ * upsample_bilinear2d(align_corners=False): per axis scale = (float)in / out, src = max(scale * (dst + 0.5f) - 0.5f, 0), i0 =
+ * (int)src, i1 = i0 + (i0 < in - 1), l1 = src - i0, l0 = 1 - l1; value = l0y (l0x v00 + l1x v01) + l1y (l0x v10 + l1x v11).
+ * Nothing of size [B, C, Hl, Wl] is stored and no float is accumulated with atomics: every result repeats bit for bit.
+ *
+ * vtp_seg_ce, per head h < H over the valid pixels p of the batch (n_valid of them):
+ *   loss[h]        = sum_p (lse(z_p) - z_p[y_p]) / n_valid, 0 without a valid pixel            (overwritten)
+ *   lse[h,b,y,x]   = log-sum-exp of the interpolated logits, f32 [H, B, Hl, Wl]                -- NULL: evaluation, not written
+ *   conf[h,t,c]   += #{p : y_p = t, argmax z_p = c}, lowest index on ties; int64 [H, C, C]     -- NULL: not counted
+ *   call_counts    = (n_valid, out of range) of this call, i32 [2]                             (overwritten)
+ *   totals        += the same two, int64 [2]                                                   -- NULL: not kept
+ * workspace: vtp_seg_ce_workspace_bytes(...) bytes, 4-byte aligned (one loss partial per workgroup and head, folded in workgroup
+ * order); that function returns the bytes, or -1 (bad argument or more than 2 GiB). */
+int vtp_seg_ce_workspace_bytes(int B, int h, int w, int Hl, int Wl, int H, int C);
+int vtp_seg_ce(const float* Z, int ldz, const unsigned char* labels, int B, int h, int w, int Hl, int Wl, int H, int C,
+               int ignore_index, float* lse, long* conf, float* loss, int* call_counts, long* totals, void* workspace,
+               long workspace_bytes, void* stream);
+/* G[(b,i,j), h*C + c] = (1 / n_valid) sum_p w_p(i,j) (exp(z_p[c] - lse_p) - [y_p = c]) over the valid pixels that have cell (i, j)
+ * among their four taps (row stride ldg); lse and call_counts as vtp_seg_ce left them.  A gather: one writer and one summation
+ * order (raster) per element; a cell without a pixel in its support gets exactly 0, and so does everything when n_valid is 0. */
+int vtp_seg_dlogits(const float* Z, int ldz, const unsigned char* labels, const float* lse, const int* call_counts, float* G, int ldg,
+                    int B, int h, int w, int Hl, int Wl, int H, int C, int ignore_index, void* stream);
+/* vtp_probe_sgd's step for M token rows: dW = G^T X and db = column sums of G are formed in slices of vtp_seg_sgd_slice() rows
+ * (a constant of the kernel, a multiple of 64), each a k-ordered fmaf chain written to the workspace; the slices are added in
+ * ascending order by one owner per element, which applies mW = fmaf(momentum, mW, dW); W = fmaf(-lr[n / C], mW, W) in the same
+ * pass (likewise mb / bias).  The result depends on the inputs and the slice constant alone.  X f32 [M, K] with row stride ldx:
+ * K % 4 == 0, ldx % 4 == 0, ldx >= K; X, W, mW and the workspace 16-byte aligned.  workspace: vtp_seg_sgd_workspace_bytes(M, N = H*C, K)
+ * bytes (returns -1 for a bad argument or more than 2 GiB: pass fewer heads per call). */
+int vtp_seg_sgd_slice(void);
+int vtp_seg_sgd_workspace_bytes(int M, int N, int K);
+int vtp_seg_sgd(float* W, float* bias, float* mW, float* mb, const float* G, int ldg, const float* X, int ldx, const float* lr, int M,
+                int H, int C, int K, float momentum, void* workspace, long workspace_bytes, void* stream);
+
 /* ---- zero-shot classification (zeroshot.hip; reference: tools/test_zero_shot_hf.py at precision 'fp32') ------------------
  * The tool's own arithmetic, fp32 in and out, products on the f32-input MFMA.  D % 4 == 0, leading dimensions % 4 == 0 and
  * >= D, feat / F / Wt 16-byte aligned.  The classifier is kept as Wt f32 [C, D] (one row per class); the tool's [D, C]

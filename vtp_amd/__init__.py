@@ -2,7 +2,7 @@
 
 Public surface mirrors the reference (`from vtp.models.vtp_hf import VTPConfig, VTPModel`):
     from vtp_amd import VTPConfig, VTPModel, VTPTrainer, LinearProbe, ZeroShot, Knn, ReconEval, MultiCrop, Preprocess, FID,
-    InceptionFeatures, FrechetStats, frechet_distance, PrecisionRecall, InceptionScore, GenEval, Retrieval, KID
+    InceptionFeatures, FrechetStats, frechet_distance, PrecisionRecall, InceptionScore, GenEval, Retrieval, KID, SegProbe
 Everything below the Python API is hand-written HIP in libvtp_hip.so (C ABI: include/vtp_hip.h)."""
 from .config import VTPConfig  # noqa: F401
 
@@ -29,6 +29,9 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name == "LinearProbe":
         from .probe import LinearProbe
         return LinearProbe
+    if name == "SegProbe":
+        from .segprobe import SegProbe
+        return SegProbe
     if name == "ZeroShot":
         from .zeroshot import ZeroShot
         return ZeroShot

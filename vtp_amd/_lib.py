@@ -131,6 +131,16 @@ SIGNATURES = {
     "vtp_probe_logits": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P],  # X ldx W bias logits ldl B N K stream
     "vtp_probe_ce": [_P, _I, _P, _I, _I, _I, _F, _P, _P, _P, _P],  # logits ldl labels B H C inv_rows loss correct dlogits stream
     "vtp_probe_sgd": [_P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _F, _P],  # W bias mW mb dlogits ldl X ldx lr B H C K momentum stream
+    # linear segmentation probe (segprobe.hip)
+    "vtp_seg_ce_workspace_bytes": [_I, _I, _I, _I, _I, _I, _I],  # B h w Hl Wl H C -> bytes, or -1
+    # Z ldz labels B h w Hl Wl H C ignore_index lse conf loss call_counts totals workspace workspace_bytes stream
+    "vtp_seg_ce": [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _L, _P],
+    # Z ldz labels lse call_counts G ldg B h w Hl Wl H C ignore_index stream
+    "vtp_seg_dlogits": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "vtp_seg_sgd_slice": [],
+    "vtp_seg_sgd_workspace_bytes": [_I, _I, _I],  # M N K -> bytes, or -1
+    # W bias mW mb G ldg X ldx lr M H C K momentum workspace workspace_bytes stream
+    "vtp_seg_sgd": [_P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _F, _P, _L, _P],
     "vtp_zs_class_mean": [_P, _I, _P, _I, _I, _I, _I, _F, _P],  # feat ldf Wt ldw C T D eps stream
     # F ldf Wt ldw targets scale B C D counts per_class rank pred logits ldl stream
     "vtp_zs_topk": [_P, _I, _P, _I, _P, _F, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P],

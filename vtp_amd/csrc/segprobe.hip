@@ -1,0 +1,445 @@
+// Linear segmentation probe (the DINOv2 / iBOT dense evaluation protocol, restated from the papers): a linear layer on frozen patch
+// tokens, its low-resolution logit map upsampled bilinearly to the label map, per-pixel cross-entropy, mIoU.  The low-resolution
+// logits Z[M = B h w, H C] come from vtp_probe_logits; nothing of size [B, C, Hl, Wl] is ever stored:
+//   vtp_seg_ce      : per pixel and head the interpolated logits from LDS-staged cells -> lse, argmax, loss partials, confusion counts
+//   vtp_seg_dlogits : G = d loss / d Z as a GATHER: one wave per (cell, head, 64 classes) walks the pixels of the cell's support
+//   vtp_seg_sgd     : dW = G^T X on the f32-input MFMA in fixed slices of the token rows, folded in slice order into the SGD step
+// ATen's upsample_bilinear2d (align_corners=False, no antialias) per axis is seg_tap below; every kernel takes the taps and weights
+// of a pixel from that one function, and the blend from seg_blend, so the forward and the gradient agree on every pixel.
+// No float atomics anywhere: every float has one writer and one summation order; the confusion counts are integer atomics.
+#include "common.h"
+#include "mfma_f32.h"
+#include "vtp_hip.h"
+
+#include <limits.h>
+
+namespace vtp {
+
+constexpr int SEG_THREADS = 256;
+constexpr int SEG_CELL_FLOATS = 10240;  // LDS floats for the staged cells of one head (40 KB)
+constexpr int SEG_HASH = 2048;          // slots of the workgroup's (target, prediction) table: twice the pixels of the largest tile
+constexpr int SEG_TILE = 32;            // label pixels per tile edge where the footprint allows it
+constexpr int SEG_SLICE = 512;          // token rows per weight-gradient slice: a constant, never derived from the device
+constexpr int SEG_MAX_EDGE = 32768;     // h, w, Hl, Wl: keeps the integer inverse map and B Hl Wl checks simple
+
+struct SegTap {
+  int i0, i1;
+  float l0, l1;
+};
+
+// taps and weights of output index dst on an axis resampled from `in` to `out` entries.  No contraction: the host plans the LDS
+// footprint with the same function and has to get the same integers.
+__host__ __device__ inline SegTap seg_tap(int dst, int in, int out) {
+#pragma clang fp contract(off)
+  const float scale = (float)in / (float)out;
+  float src = scale * ((float)dst + 0.5f) - 0.5f;
+  src = src < 0.f ? 0.f : src;
+  SegTap t;
+  t.i0 = (int)src;
+  if (t.i0 > in - 1) t.i0 = in - 1;  // cannot happen for dst < out; keeps every index inside the map whatever the rounding
+  t.i1 = t.i0 + (t.i0 < in - 1 ? 1 : 0);
+  t.l1 = src - (float)t.i0;
+  t.l0 = 1.f - t.l1;
+  return t;
+}
+
+// 7 roundings, the same in every kernel
+__device__ __forceinline__ float seg_blend(float v00, float v01, float v10, float v11, const SegTap& ty, const SegTap& tx) {
+#pragma clang fp contract(off)
+  return ty.l0 * (tx.l0 * v00 + tx.l1 * v01) + ty.l1 * (tx.l0 * v10 + tx.l1 * v11);
+}
+
+__device__ __forceinline__ bool seg_valid(int lab, int C, int ignore) { return lab != ignore && lab < C; }
+
+// ---------------------------------------------------------------------------------------------------------------- pixel pass
+// The tiling of the label map: tiles of th x tw pixels whose cell footprint (fy x fx cells of C | 1 floats) fits the LDS budget.
+struct SegPlan {
+  int th, tw, tiles_y, tiles_x;
+};
+
+static int seg_footprint(int tile, int in, int out) {
+  int worst = 1;
+  for (int p0 = 0; p0 < out; p0 += tile) {
+    const int p1 = (p0 + tile < out ? p0 + tile : out) - 1;
+    const int n = seg_tap(p1, in, out).i1 - seg_tap(p0, in, out).i0 + 1;
+    worst = n > worst ? n : worst;
+  }
+  return worst;
+}
+
+static SegPlan seg_plan(int h, int w, int Hl, int Wl, int C) {
+  SegPlan p;
+  p.th = p.tw = SEG_TILE;
+  const int Cs = C | 1;
+  for (;;) {
+    const int fy = seg_footprint(p.th, h, Hl), fx = seg_footprint(p.tw, w, Wl);
+    if ((long)fy * fx * Cs <= SEG_CELL_FLOATS || (p.th == 1 && p.tw == 1)) break;  // 1 x 1 pixel: at most 2 x 2 cells of 255 floats
+    if ((fy >= fx && p.th > 1) || p.tw == 1) p.th /= 2;
+    else p.tw /= 2;
+  }
+  p.tiles_y = cdiv(Hl, p.th);
+  p.tiles_x = cdiv(Wl, p.tw);
+  return p;
+}
+
+__device__ __forceinline__ int block_sum_int(int v, int* red) {
+  v = wave_sum_int(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return red[0] + red[1] + red[2] + red[3];
+}
+
+// grid (tiles, B).  part_loss f32 [H, nblocks] and part_cnt i32 [2, nblocks] (valid, out of range) get one entry per workgroup;
+// seg_ce_fold_kernel adds them in workgroup order.
+__global__ __launch_bounds__(SEG_THREADS) void seg_ce_kernel(const float* __restrict__ Z, int ldz, const uint8_t* __restrict__ labels,
+                                                            int h, int w, int Hl, int Wl, int H, int C, int ignore, int th, int tw,
+                                                            int tiles_x, float* __restrict__ lse, unsigned long long* __restrict__ conf,
+                                                            float* __restrict__ part_loss, int* __restrict__ part_cnt) {
+  __shared__ float cells[SEG_CELL_FLOATS];
+  __shared__ int hkey[SEG_HASH], hcnt[SEG_HASH];
+  __shared__ float red[4];
+  __shared__ int redi[4];
+  const int tid = threadIdx.x, b = blockIdx.y, B = gridDim.y, tile = blockIdx.x;
+  const int nblocks = gridDim.x * gridDim.y, blk = b * gridDim.x + tile;
+  const int y0 = (tile / tiles_x) * th, x0 = (tile % tiles_x) * tw;
+  const int y1 = min(y0 + th, Hl) - 1, x1 = min(x0 + tw, Wl) - 1;
+  const int fy0 = seg_tap(y0, h, Hl).i0, fx0 = seg_tap(x0, w, Wl).i0;
+  const int ncy = seg_tap(y1, h, Hl).i1 - fy0 + 1, ncx = seg_tap(x1, w, Wl).i1 - fx0 + 1;
+  const int Cs = C | 1;  // odd row length: the cells of neighbouring pixels land on different LDS banks
+  const int ncell = min(ncy * ncx, SEG_CELL_FLOATS / Cs);  // the host planned the tile so that the footprint fits
+  const int npix = th * tw;
+  const long plane = (long)Hl * Wl;
+  const uint8_t* lab_b = labels + b * plane;
+
+  int nv = 0, no = 0;
+  for (int p = tid; p < npix; p += SEG_THREADS) {
+    const int py = y0 + p / tw, px = x0 + p % tw;
+    if (py > y1 || px > x1) continue;
+    const int lab = lab_b[(long)py * Wl + px];
+    if (lab == ignore) continue;
+    if (lab < C) ++nv;
+    else ++no;
+  }
+  nv = block_sum_int(nv, redi);
+  no = block_sum_int(no, redi);
+  if (tid == 0) part_cnt[blk] = nv, part_cnt[nblocks + blk] = no;
+
+  for (int hh = 0; hh < H; ++hh) {
+    __syncthreads();
+    for (int i = tid; i < ncell * C; i += SEG_THREADS) {
+      const int cell = i / C, c = i - cell * C;
+      const long row = ((long)b * h + fy0 + cell / ncx) * w + fx0 + cell % ncx;
+      cells[cell * Cs + c] = Z[row * ldz + (long)hh * C + c];
+    }
+    if (conf)
+      for (int i = tid; i < SEG_HASH; i += SEG_THREADS) hkey[i] = -1, hcnt[i] = 0;
+    __syncthreads();
+    float loss = 0.f;
+    for (int p = tid; p < npix; p += SEG_THREADS) {
+      const int py = y0 + p / tw, px = x0 + p % tw;
+      if (py > y1 || px > x1) continue;
+      const int lab = lab_b[(long)py * Wl + px];
+      const bool ok = seg_valid(lab, C, ignore);
+      if (!ok && !lse) continue;
+      const SegTap ty = seg_tap(py, h, Hl), tx = seg_tap(px, w, Wl);
+      const float* c00 = cells + ((ty.i0 - fy0) * ncx + (tx.i0 - fx0)) * Cs;
+      const float* c01 = cells + ((ty.i0 - fy0) * ncx + (tx.i1 - fx0)) * Cs;
+      const float* c10 = cells + ((ty.i1 - fy0) * ncx + (tx.i0 - fx0)) * Cs;
+      const float* c11 = cells + ((ty.i1 - fy0) * ncx + (tx.i1 - fx0)) * Cs;
+      float m = -INFINITY;
+      int mi = 0;
+      for (int c = 0; c < C; ++c) {
+        const float v = seg_blend(c00[c], c01[c], c10[c], c11[c], ty, tx);
+        if (v > m) m = v, mi = c;  // strict >: the lowest index of the maximum stays
+      }
+      float s = 0.f;
+      for (int c = 0; c < C; ++c) s += expf(seg_blend(c00[c], c01[c], c10[c], c11[c], ty, tx) - m);
+      const float l = m + logf(s);
+      if (lse) lse[((long)hh * B + b) * plane + (long)py * Wl + px] = l;
+      if (!ok) continue;
+      loss += l - seg_blend(c00[lab], c01[lab], c10[lab], c11[lab], ty, tx);
+      if (conf) {  // integer counts in an LDS table first: one global atomic per (target, prediction) pair the tile holds
+        const int key = lab * C + mi;
+        unsigned slot = ((unsigned)key * 2654435761u) >> 21;
+        for (;;) {
+          const int prev = atomicCAS(&hkey[slot], -1, key);
+          if (prev == -1 || prev == key) break;
+          slot = (slot + 1) & (SEG_HASH - 1);  // at most npix <= SEG_HASH / 2 keys: a free slot exists
+        }
+        atomicAdd(&hcnt[slot], 1);
+      }
+    }
+    loss = block_sum<4>(loss, red);  // fixed order; its barriers also close the table
+    if (tid == 0) part_loss[(long)hh * nblocks + blk] = loss;
+    if (conf)
+      for (int i = tid; i < SEG_HASH; i += SEG_THREADS)
+        if (hkey[i] >= 0) atomicAdd(conf + (long)hh * C * C + hkey[i], (unsigned long long)hcnt[i]);
+  }
+}
+
+// one workgroup; one owner thread per sum, partials added in ascending workgroup order
+__global__ __launch_bounds__(SEG_THREADS) void seg_ce_fold_kernel(const float* __restrict__ part_loss, const int* __restrict__ part_cnt,
+                                                                 int nblocks, int H, float* __restrict__ loss, int* __restrict__ call_counts,
+                                                                 long* __restrict__ totals) {
+  __shared__ int cnt[2];
+  const int tid = threadIdx.x;
+  if (tid < 2) {
+    int s = 0;
+    for (int i = 0; i < nblocks; ++i) s += part_cnt[(long)tid * nblocks + i];
+    cnt[tid] = s;
+    call_counts[tid] = s;
+    if (totals) totals[tid] += s;
+  }
+  __syncthreads();
+  const int n = cnt[0];
+  for (int hh = tid; hh < H; hh += SEG_THREADS) {
+    float s = 0.f;
+    for (int i = 0; i < nblocks; ++i) s += part_loss[(long)hh * nblocks + i];
+    loss[hh] = n > 0 ? s / (float)n : 0.f;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- cell pass
+__device__ __forceinline__ float seg_pick(float a, float b, float c, int k) { return k == 0 ? a : (k == 1 ? b : c); }
+
+// One wave per (cell, head, chunk of 64 classes), lane = class.  A pixel that has the cell among its taps has its other taps in
+// the cell's 3 x 3 neighbourhood, whatever the scale: the nine logits of the lane's class sit in registers and the walk over the
+// candidate pixels (raster order, wave-uniform) reads only the label and lse of each pixel.
+__global__ __launch_bounds__(SEG_THREADS) void seg_dlogits_kernel(const float* __restrict__ Z, int ldz, const uint8_t* __restrict__ labels,
+                                                                 const float* __restrict__ lse, const int* __restrict__ call_counts,
+                                                                 float* __restrict__ G, int ldg, int B, int h, int w, int Hl, int Wl, int H,
+                                                                 int C, int ignore, int chunks, long tasks) {
+  const int lane = threadIdx.x & 63;
+  const long task = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (task >= tasks) return;
+  const int cc = (int)(task % chunks);
+  const long t2 = task / chunks;
+  const int hh = (int)(t2 % H);
+  const long cell = t2 / H;
+  const int hw = h * w, b = (int)(cell / hw), iy = (int)(cell % hw) / w, ix = (int)(cell % w);
+  const int c = cc * 64 + lane, cl = c < C ? c : C - 1;
+  float nb[3][3];
+#pragma unroll
+  for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+    for (int dx = 0; dx < 3; ++dx) {
+      const int yy = min(max(iy + dy - 1, 0), h - 1), xx = min(max(ix + dx - 1, 0), w - 1);  // a clamped neighbour is never a tap
+      nb[dy][dx] = Z[((long)b * hw + (long)yy * w + xx) * ldz + (long)hh * C + cl];
+    }
+  // candidate pixels from the inverse map in integers, two pixels wider than src in [i - 1, i + 1) asks for; membership and weight
+  // are the tap function's
+  const int ylo = (int)max(0L, (2L * iy - 1) * Hl / (2L * h) - 2), yhi = (int)min((long)Hl - 1, ((2L * iy + 3) * Hl + 2L * h - 1) / (2L * h) + 1);
+  const int xlo = (int)max(0L, (2L * ix - 1) * Wl / (2L * w) - 2), xhi = (int)min((long)Wl - 1, ((2L * ix + 3) * Wl + 2L * w - 1) / (2L * w) + 1);
+  const long plane = (long)Hl * Wl;
+  const uint8_t* lab_b = labels + b * plane;
+  const float* lse_b = lse + ((long)hh * B + b) * plane;
+  float acc = 0.f;
+  for (int py = ylo; py <= yhi; ++py) {
+    const SegTap ty = seg_tap(py, h, Hl);
+    if (ty.i0 != iy && ty.i1 != iy) continue;
+    const float wy = (ty.i0 == iy ? ty.l0 : 0.f) + (ty.i1 == iy ? ty.l1 : 0.f);
+    const int ka = ty.i0 - iy + 1, kb = ty.i1 - iy + 1;
+    float ra[3], rb[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) ra[j] = seg_pick(nb[0][j], nb[1][j], nb[2][j], ka), rb[j] = seg_pick(nb[0][j], nb[1][j], nb[2][j], kb);
+    for (int px = xlo; px <= xhi; ++px) {
+      const SegTap tx = seg_tap(px, w, Wl);
+      if (tx.i0 != ix && tx.i1 != ix) continue;
+      const int lab = lab_b[(long)py * Wl + px];
+      if (!seg_valid(lab, C, ignore)) continue;
+      const float wx = (tx.i0 == ix ? tx.l0 : 0.f) + (tx.i1 == ix ? tx.l1 : 0.f);
+      const int ja = tx.i0 - ix + 1, jb = tx.i1 - ix + 1;
+      const float z = seg_blend(seg_pick(ra[0], ra[1], ra[2], ja), seg_pick(ra[0], ra[1], ra[2], jb), seg_pick(rb[0], rb[1], rb[2], ja),
+                                seg_pick(rb[0], rb[1], rb[2], jb), ty, tx);
+      const float g = expf(z - lse_b[(long)py * Wl + px]) - (lab == c ? 1.f : 0.f);
+      acc = fmaf(wy * wx, g, acc);
+    }
+  }
+  const int nv = call_counts[0];
+  const float inv = nv > 0 ? 1.f / (float)nv : 0.f;
+  if (c < C) G[cell * ldg + (long)hh * C + c] = acc * inv;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- weight step
+// probe_sgd_kernel's tile (one wave = 64 rows n x 64 columns k, four 32x32 accumulators, k-ordered fmaf chains) over ONE slice of
+// SEG_SLICE token rows; the partial tile goes to wsW [S, N, K], the partial column sums of G to wsb [S, N].
+__global__ __launch_bounds__(SEG_THREADS) void seg_wgrad_kernel(const float* __restrict__ G, int ldg, const float* __restrict__ X, int ldx,
+                                                               int M, int N, int K, int k_tiles, int n_tiles, long tasks,
+                                                               float* __restrict__ wsW, float* __restrict__ wsb) {
+  const int lane = threadIdx.x & 63, r = lane & 31, half = lane >> 5;
+  const long task = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (task >= tasks) return;
+  const int kt = (int)(task % k_tiles);
+  const long t2 = task / k_tiles;
+  const int nt = (int)(t2 % n_tiles), s = (int)(t2 / n_tiles);
+  const int n0 = nt * 64, k0 = kt * 64, m0 = s * SEG_SLICE, m1 = min(M, m0 + SEG_SLICE);
+  const int na = n0 + r, nb = n0 + 32 + r, ka = k0 + r, kb = k0 + 32 + r;
+  const float* gpa = G + (na < N ? na : N - 1);
+  const float* gpb = G + (nb < N ? nb : N - 1);
+  const float* xpa = X + (ka < K ? ka : K - 1);
+  const float* xpb = X + (kb < K ? kb : K - 1);
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acc[0][0][i] = acc[0][1][i] = acc[1][0][i] = acc[1][1][i] = 0.f;
+  for (int b0 = m0; b0 < m1; b0 += 8) {  // four k steps of 2 rows in flight; rows past the slice end are zeros: exact no-ops at the chain's end
+    float a0[4], a1[4], x0[4], x1[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int b = b0 + 2 * u + half;
+      const long bc = b < m1 ? b : m1 - 1;
+      a0[u] = gpa[bc * ldg], a1[u] = gpb[bc * ldg], x0[u] = xpa[bc * ldx], x1[u] = xpb[bc * ldx];
+      a0[u] = (b < m1 && na < N) ? a0[u] : 0.f;
+      a1[u] = (b < m1 && nb < N) ? a1[u] : 0.f;
+      x0[u] = (b < m1 && ka < K) ? x0[u] : 0.f;
+      x1[u] = (b < m1 && kb < K) ? x1[u] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      acc[0][0] = mfma32(a0[u], x0[u], acc[0][0]);
+      acc[0][1] = mfma32(a0[u], x1[u], acc[0][1]);
+      acc[1][0] = mfma32(a1[u], x0[u], acc[1][0]);
+      acc[1][1] = mfma32(a1[u], x1[u], acc[1][1]);
+    }
+  }
+  float* out = wsW + (long)s * N * K;
+#pragma unroll
+  for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int n = n0 + 32 * ti + acc_row(i, half);
+      if (n >= N) continue;
+#pragma unroll
+      for (int tj = 0; tj < 2; ++tj) {
+        const int k = k0 + 32 * tj + r;
+        if (k < K) out[(long)n * K + k] = acc[ti][tj][i];
+      }
+    }
+  if (k0 == 0) {
+    const int n = n0 + lane;
+    if (n < N) {
+      float db = 0.f;
+      for (int b = m0; b < m1; ++b) db += G[(long)b * ldg + n];
+      wsb[(long)s * N + n] = db;
+    }
+  }
+}
+
+// one owner per four weights (or one bias): the S partials added in slice order, then the two fmaf lines of vtp_probe_sgd
+__global__ __launch_bounds__(SEG_THREADS) void seg_sgd_fold_kernel(float* __restrict__ W, float* __restrict__ bias, float* __restrict__ mW,
+                                                                  float* __restrict__ mb, const float* __restrict__ wsW,
+                                                                  const float* __restrict__ wsb, const float* __restrict__ lr, int S, int N,
+                                                                  int C, int K, float momentum) {
+  const long nk4 = (long)N * K / 4, i = (long)blockIdx.x * SEG_THREADS + threadIdx.x;
+  if (i < nk4) {
+    const f32x4* p = (const f32x4*)wsW + i;
+    f32x4 d = p[0];
+    for (int s = 1; s < S; ++s) d += p[(long)s * nk4];
+    const float nlr = -lr[(int)(i * 4 / K) / C];  // K % 4 == 0: the four weights share a row
+    f32x4 m = ((f32x4*)mW)[i], x = ((f32x4*)W)[i];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      m[e] = fmaf(momentum, m[e], d[e]);
+      x[e] = fmaf(nlr, m[e], x[e]);
+    }
+    ((f32x4*)mW)[i] = m;
+    ((f32x4*)W)[i] = x;
+  } else if (i - nk4 < N) {
+    const int n = (int)(i - nk4);
+    float d = wsb[n];
+    for (int s = 1; s < S; ++s) d += wsb[(long)s * N + n];
+    const float m = fmaf(momentum, mb[n], d);
+    mb[n] = m;
+    bias[n] = fmaf(-lr[n / C], m, bias[n]);
+  }
+}
+
+static bool seg_shape_ok(int B, int h, int w, int Hl, int Wl) {
+  return B >= 1 && B <= 65535 && h >= 1 && w >= 1 && h <= SEG_MAX_EDGE && w <= SEG_MAX_EDGE && Hl <= SEG_MAX_EDGE && Wl <= SEG_MAX_EDGE &&
+         (long)B * h * w <= INT_MAX && (long)B * Hl * Wl <= INT_MAX;
+}
+
+static long seg_ce_bytes(const SegPlan& p, int B, int H) { return ((long)H + 2) * p.tiles_y * p.tiles_x * B * 4; }
+static long seg_sgd_bytes(int M, int N, int K) { return (long)cdiv(M, SEG_SLICE) * N * ((long)K + 1) * 4; }
+
+}  // namespace vtp
+
+using namespace vtp;
+
+extern "C" int vtp_seg_ce_workspace_bytes(int B, int h, int w, int Hl, int Wl, int H, int C) {
+  VTP_REQUIRE(Hl >= 1 && Wl >= 1, "vtp_seg_ce_workspace_bytes: bad label size (Hl, Wl >= 1)");
+  VTP_REQUIRE(C >= 1 && C <= 255 && H >= 1, "vtp_seg_ce_workspace_bytes: bad shape (H >= 1, 1 <= C <= 255)");
+  VTP_REQUIRE(seg_shape_ok(B, h, w, Hl, Wl), "vtp_seg_ce_workspace_bytes: bad shape (B, h, w >= 1; edges <= 32768; B Hl Wl < 2^31)");
+  const long n = seg_ce_bytes(seg_plan(h, w, Hl, Wl, C), B, H);
+  VTP_REQUIRE(n <= INT_MAX, "vtp_seg_ce_workspace_bytes: more than 2 GiB (pass fewer heads per call)");
+  return (int)n;
+}
+
+extern "C" int vtp_seg_ce(const float* Z, int ldz, const unsigned char* labels, int B, int h, int w, int Hl, int Wl, int H, int C,
+                          int ignore_index, float* lse, long* conf, float* loss, int* call_counts, long* totals, void* workspace,
+                          long workspace_bytes, void* stream) {
+  VTP_REQUIRE(Z && labels && loss && call_counts && workspace, "vtp_seg_ce: null pointer");
+  VTP_REQUIRE(Hl >= 1 && Wl >= 1, "vtp_seg_ce: bad label size (Hl, Wl >= 1)");
+  VTP_REQUIRE(C >= 1 && C <= 255 && H >= 1 && (long)H * C * C <= INT_MAX, "vtp_seg_ce: bad shape (H >= 1, 1 <= C <= 255)");
+  VTP_REQUIRE(seg_shape_ok(B, h, w, Hl, Wl), "vtp_seg_ce: bad shape (B, h, w >= 1; edges <= 32768; B Hl Wl < 2^31)");
+  VTP_REQUIRE(ldz >= (long)H * C, "vtp_seg_ce: bad leading dimension (ldz >= H * C)");
+  const SegPlan p = seg_plan(h, w, Hl, Wl, C);
+  const long tiles = (long)p.tiles_y * p.tiles_x, nblocks = tiles * B;
+  VTP_REQUIRE(nblocks <= INT_MAX / 4, "vtp_seg_ce: too many tiles");
+  VTP_REQUIRE(workspace_bytes >= seg_ce_bytes(p, B, H) && ((uintptr_t)workspace & 3) == 0,
+              "vtp_seg_ce: workspace too small (vtp_seg_ce_workspace_bytes) or not 4-byte aligned");
+  float* part_loss = (float*)workspace;
+  int* part_cnt = (int*)(part_loss + (long)H * nblocks);
+  hipLaunchKernelGGL(seg_ce_kernel, dim3((unsigned)tiles, B), dim3(SEG_THREADS), 0, (hipStream_t)stream, Z, ldz, labels, h, w, Hl, Wl, H,
+                     C, ignore_index, p.th, p.tw, p.tiles_x, lse, (unsigned long long*)conf, part_loss, part_cnt);
+  hipLaunchKernelGGL(seg_ce_fold_kernel, dim3(1), dim3(SEG_THREADS), 0, (hipStream_t)stream, part_loss, part_cnt, (int)nblocks, H, loss,
+                     call_counts, totals);
+  return check_launch("seg_ce");
+}
+
+extern "C" int vtp_seg_dlogits(const float* Z, int ldz, const unsigned char* labels, const float* lse, const int* call_counts, float* G,
+                               int ldg, int B, int h, int w, int Hl, int Wl, int H, int C, int ignore_index, void* stream) {
+  VTP_REQUIRE(Z && labels && lse && call_counts && G, "vtp_seg_dlogits: null pointer");
+  VTP_REQUIRE(Hl >= 1 && Wl >= 1, "vtp_seg_dlogits: bad label size (Hl, Wl >= 1)");
+  VTP_REQUIRE(C >= 1 && C <= 255 && H >= 1 && (long)H * C <= INT_MAX, "vtp_seg_dlogits: bad shape (H >= 1, 1 <= C <= 255)");
+  VTP_REQUIRE(seg_shape_ok(B, h, w, Hl, Wl), "vtp_seg_dlogits: bad shape (B, h, w >= 1; edges <= 32768; B Hl Wl < 2^31)");
+  VTP_REQUIRE(ldz >= (long)H * C && ldg >= (long)H * C, "vtp_seg_dlogits: bad leading dimension (ldz, ldg >= H * C)");
+  const int chunks = cdiv(C, 64);
+  const long tasks = (long)B * h * w * H * chunks;
+  VTP_REQUIRE((tasks + 3) / 4 <= INT_MAX, "vtp_seg_dlogits: too many tiles");
+  hipLaunchKernelGGL(seg_dlogits_kernel, dim3(cdiv(tasks, 4)), dim3(SEG_THREADS), 0, (hipStream_t)stream, Z, ldz, labels, lse, call_counts,
+                     G, ldg, B, h, w, Hl, Wl, H, C, ignore_index, chunks, tasks);
+  return check_launch("seg_dlogits");
+}
+
+extern "C" int vtp_seg_sgd_slice(void) { return SEG_SLICE; }
+
+extern "C" int vtp_seg_sgd_workspace_bytes(int M, int N, int K) {
+  VTP_REQUIRE(M >= 1 && N >= 1 && K >= 4 && K % 4 == 0, "vtp_seg_sgd_workspace_bytes: bad shape (M, N >= 1, K %% 4 == 0)");
+  const long n = seg_sgd_bytes(M, N, K);
+  VTP_REQUIRE(n <= INT_MAX, "vtp_seg_sgd_workspace_bytes: more than 2 GiB (pass fewer heads per call)");
+  return (int)n;
+}
+
+extern "C" int vtp_seg_sgd(float* W, float* bias, float* mW, float* mb, const float* G, int ldg, const float* X, int ldx, const float* lr,
+                           int M, int H, int C, int K, float momentum, void* workspace, long workspace_bytes, void* stream) {
+  VTP_REQUIRE(W && bias && mW && mb && G && X && lr && workspace, "vtp_seg_sgd: null pointer");
+  VTP_REQUIRE(C >= 1 && C <= 255, "vtp_seg_sgd: bad shape (1 <= C <= 255)");
+  VTP_REQUIRE(M >= 1 && H >= 1 && (long)H * C <= INT_MAX && K >= 4 && K % 4 == 0, "vtp_seg_sgd: bad shape (M, H >= 1, K %% 4 == 0)");
+  VTP_REQUIRE(ldx >= K && ldx % 4 == 0 && ldg >= (long)H * C,
+              "vtp_seg_sgd: bad leading dimension (ldx >= K, ldx %% 4 == 0, ldg >= H * C)");
+  VTP_REQUIRE(aligned16(X) && aligned16(W) && aligned16(mW) && aligned16(workspace),
+              "vtp_seg_sgd: X, W, mW and workspace must be 16-byte aligned");
+  const int N = H * C, S = cdiv(M, SEG_SLICE);
+  VTP_REQUIRE(workspace_bytes >= seg_sgd_bytes(M, N, K), "vtp_seg_sgd: workspace too small (vtp_seg_sgd_workspace_bytes)");
+  const int k_tiles = cdiv(K, 64), n_tiles = cdiv(N, 64);
+  const long tasks = (long)k_tiles * n_tiles * S, nk4 = (long)N * K / 4;
+  VTP_REQUIRE((tasks + 3) / 4 <= INT_MAX && (nk4 + N) / SEG_THREADS < INT_MAX, "vtp_seg_sgd: too many tiles");
+  float* wsW = (float*)workspace;
+  float* wsb = wsW + (long)S * N * K;
+  hipLaunchKernelGGL(seg_wgrad_kernel, dim3(cdiv(tasks, 4)), dim3(SEG_THREADS), 0, (hipStream_t)stream, G, ldg, X, ldx, M, N, K, k_tiles,
+                     n_tiles, tasks, wsW, wsb);
+  hipLaunchKernelGGL(seg_sgd_fold_kernel, dim3(cdiv(nk4 + N, SEG_THREADS)), dim3(SEG_THREADS), 0, (hipStream_t)stream, W, bias, mW, mb, wsW,
+                     wsb, lr, S, N, C, K, momentum);
+  return check_launch("seg_sgd");
+}

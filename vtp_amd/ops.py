@@ -603,6 +603,78 @@ def probe_sgd(w, bias, mw, mb, dlogits, x, lr, B, H, C, K, momentum):
                                      B, H, C, K, momentum, _s()), "vtp_probe_sgd")
 
 
+def _seg_bytes(fn, *args):
+    n = fn(*args)
+    if n < 0:
+        raise ValueError(_lib_().vtp_last_error().decode(errors="replace"))
+    return n
+
+
+def seg_ce_workspace_bytes(B, h, w, Hl, Wl, H, C):
+    """bytes of workspace seg_ce needs; ValueError for arguments the kernel refuses or a workspace above 2 GiB"""
+    return _seg_bytes(_lib_().vtp_seg_ce_workspace_bytes, B, h, w, Hl, Wl, H, C)
+
+
+def seg_ce(z, labels, hw, H, C, ignore_index, loss, call_counts, workspace, lse=None, conf=None, totals=None):
+    """pixel pass of the segmentation probe: z f32 [B*h*w, >= H*C] low-resolution logits (probe_logits), labels u8 [B, Hl, Wl] ->
+    loss f32 [H] (mean over the valid pixels, overwritten), call_counts i32 [2] (valid, out of range; overwritten); optional lse
+    f32 [H, B, Hl, Wl] (training), conf int64 [H, C, C] (accumulated; row = target) and totals int64 [2] (accumulated)"""
+    h, w = hw
+    _need(labels, "labels", torch.uint8, dims=3)
+    B, Hl, Wl = labels.shape
+    _need(loss, "loss", torch.float32, (H,))
+    _need(call_counts, "call_counts", torch.int32, (2,))
+    if lse is not None:
+        _need(lse, "lse", torch.float32, (H, B, Hl, Wl))
+    if conf is not None:
+        _need(conf, "conf", torch.int64, (H, C, C))
+    if totals is not None:
+        _need(totals, "totals", torch.int64, (2,))
+    _need(workspace, "workspace", torch.uint8, dims=1)
+    _need_f32(z=z)
+    _need_gpu(labels=labels, loss=loss, call_counts=call_counts, lse=lse, conf=conf, totals=totals, workspace=workspace)
+    if z.dim() != 2 or z.shape[0] != B * h * w or z.stride(1) != 1:
+        raise ValueError(f"z must be [{B * h * w}, >= {H * C}] with unit column stride, got {tuple(z.shape)}")
+    _lib.check(_lib_().vtp_seg_ce(_p(z), z.stride(0), _p(labels), B, h, w, Hl, Wl, H, C, ignore_index, _p(lse), _p(conf), _p(loss),
+                                  _p(call_counts), _p(totals), _p(workspace), workspace.numel(), _s()), "vtp_seg_ce")
+
+
+def seg_dlogits(z, labels, hw, H, C, ignore_index, lse, call_counts, g):
+    """cell pass: g f32 [B*h*w, >= H*C] = d (mean pixel cross-entropy) / d z, gathered per cell from lse and call_counts of seg_ce"""
+    h, w = hw
+    _need(labels, "labels", torch.uint8, dims=3)
+    B, Hl, Wl = labels.shape
+    _need(lse, "lse", torch.float32, (H, B, Hl, Wl))
+    _need(call_counts, "call_counts", torch.int32, (2,))
+    _need_f32(z=z, g=g)
+    _need_gpu(labels=labels, lse=lse, call_counts=call_counts)
+    for name, t in (("z", z), ("g", g)):
+        if t.dim() != 2 or t.shape[0] != B * h * w or t.stride(1) != 1:
+            raise ValueError(f"{name} must be [{B * h * w}, >= {H * C}] with unit column stride, got {tuple(t.shape)}")
+    _lib.check(_lib_().vtp_seg_dlogits(_p(z), z.stride(0), _p(labels), _p(lse), _p(call_counts), _p(g), g.stride(0), B, h, w, Hl, Wl,
+                                       H, C, ignore_index, _s()), "vtp_seg_dlogits")
+
+
+def seg_sgd_slice():
+    """token rows per weight-gradient slice of seg_sgd: a constant of the kernel"""
+    return _lib_().vtp_seg_sgd_slice()
+
+
+def seg_sgd_workspace_bytes(M, N, K):
+    """bytes of workspace seg_sgd needs for M token rows and N = H * C outputs; ValueError for refused arguments or above 2 GiB"""
+    return _seg_bytes(_lib_().vtp_seg_sgd_workspace_bytes, M, N, K)
+
+
+def seg_sgd(w, bias, mw, mb, g, x, lr, M, H, C, K, momentum, workspace):
+    """probe_sgd for M token rows, sliced over the rows and folded in slice order: w [H*C, K], bias [H*C] and their momentum buffers
+    updated in place from g [M, >= H*C] and x [M, K] (a column slice); lr f32 [H] on the device"""
+    _need(workspace, "workspace", torch.uint8, dims=1)
+    _need_f32(w=w, bias=bias, mw=mw, mb=mb, g=g, x=x, lr=lr)
+    _need_gpu(workspace=workspace)
+    _lib.check(_lib_().vtp_seg_sgd(_p(w), _p(bias), _p(mw), _p(mb), _p(g), g.stride(0), _p(x), x.stride(0), _p(lr), M, H, C, K, momentum,
+                                   _p(workspace), workspace.numel(), _s()), "vtp_seg_sgd")
+
+
 def zs_class_mean(feat, wt, C, T, D, eps=1e-12):
     """wt[c] f32 [C, D] = F.normalize(mean over t of feat[c * T + t]) (feat f32 [C * T, D], template t of class c in row c * T + t);
     feat and wt may be row / column slices of wider matrices (row strides taken from the tensors)"""
