@@ -106,6 +106,11 @@ __global__ __launch_bounds__(256) void koleo_loss_kernel(const float* __restrict
 //   colsum[k] = sum_t E[t,k] u[t]        (over the samples, per prototype)   -> v[k] = 1 / (K colsum[k])
 //   rowsum[t] = sum_k E[t,k] v[k]        (over the prototypes, per sample)   -> u[t] = 1 / (B_total rowsum[t])
 // so Q is never materialised until the final pass.  Rows t >= n_rows (device count, optional) are padding.
+// Specified for the rows t < n_rows and for a range of logits * inv_temp over them below 87: `shift` is ONE maximum over all valid
+// rows, so a smaller e^(z - shift) flushes to zero (the head's logits are scaled cosines, a range of 2 * inv_temp <= 50).  What probs, u
+// and rowsum hold for the padding rows is unspecified (their exponentials may overflow: 0 * inf = NaN) and nothing reads it: the
+// cross entropy skips rows by their target index.  With n_rows = 0 (a step without masked patches) shift stays -inf and every row is
+// such a padding row; the call returns, count is clamped at 1 and no valid row exists to be wrong.
 __global__ __launch_bounds__(256) void sk_max_kernel(const bf16* __restrict__ logits, float inv_temp, float* __restrict__ mx_out,
                                                      int T, int K, const int* __restrict__ rows_dev) {
   __shared__ float red[4];

@@ -42,6 +42,10 @@ __global__ __launch_bounds__(256) void scatter_token_rows_kernel(const bf16* __r
 }
 
 // weight_norm(Linear(C -> K)): W_eff[k, :] = g[k] * v[k, :] / ||v[k, :]||.  One wave per prototype row (C <= 512).
+// Specified for rows whose fp32 sum of squares is a normal number (>= 2^-126, a row norm of about 1e-19): below that the sum flushes to
+// zero, rsqrtf gives inf and the row comes out as inf / NaN, as torch's fp32 weight_norm does.  Unspecified, not guarded: an
+// initialised or trained prototype row is some eighteen orders of magnitude away from it (tests/test_ssl_kernels_gpu.py runs a row of
+// norm 1e-16).
 __global__ __launch_bounds__(256) void weight_norm_prep_kernel(const float* __restrict__ v, const float* __restrict__ g,
                                                                bf16* __restrict__ weff, bf16* __restrict__ weffT,
                                                                float* __restrict__ inv_norm, int K, int C) {
