@@ -420,10 +420,13 @@ int vtp_sinkhorn_knopp(const void* logits, float inv_temp, void* probs, float* u
 /* ---- fp8 forward path (BASELINE config 5: VTP-L encode -> decode with fp8 MFMA; fp8.hip, gemm8p.hip) --------
  * e4m3 = the OCP fp8 format of gfx950, per-tensor scales:  q = e4m3(clamp(x * scale, -448, 448)).
  * vtp_quantize_e4m3: src bf16 (src_is_f32 = 0) or f32 [n] -> dst bytes [n]; scale from device memory (scale_dev) or the argument.
- * vtp_amax: amax[0] = max(amax[0], max |src|)  (calibration of the scales).   vtp_dequantize_e4m3: bytes -> f32 * inv_scale.
+ *   +-inf saturates to +-448; a NaN leaves as a NaN code (S.1111.111), here and in vtp_norm_fwd_e4m3.
+ * vtp_amax: amax[0] = max(amax[0], max |src|)  (calibration of the scales); a NaN in src leaves a NaN in amax[0].
+ * vtp_dequantize_e4m3: bytes -> f32 * inv_scale.
  * vtp_gemm_nt_fp8: C[M,N] = alpha * A8[M,K] B8[N,K]^T (+ bias, + residual | SwiGLU), epilogues VTP_EPI_BF16 / F32 / SWIGLU as
  *   in vtp_gemm_nt, alpha = 1 / (scale_A * scale_B); K, lda, ldb in fp8 elements, multiples of 16; rope_pos / rope_sin / rope_cos /
- *   rope_cols (or nulls / 0): apply_rope fused into the bf16 epilogue exactly as in vtp_gemm_qkv_rope. */
+ *   rope_cols (or nulls / 0): apply_rope fused into the bf16 epilogue exactly as in vtp_gemm_qkv_rope.  M x lda and N x ldb bytes
+ *   must stay below 4 GiB (32-bit staging offsets; there is no other kernel to fall back to). */
 /* norm_fwd with the quantisation fused: y8[M, D] = e4m3(bf16(norm(x)) * q_scale[0]) (q_scale in device memory) */
 int vtp_norm_fwd_e4m3(const float* x, const float* w, const float* b, void* y8, const float* q_scale, float* stats, int M, int D,
                       float eps, int kind, void* stream);

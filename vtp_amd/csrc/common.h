@@ -48,6 +48,23 @@ __device__ __forceinline__ int wave_sum_int(int v) {
   return v;
 }
 
+// max that keeps a NaN (fmaxf returns the other operand): the amax of data holding a NaN is a NaN
+__device__ __forceinline__ float max_nan(float m, float v) { return (v > m || v != v) ? v : m; }
+
+// four floats -> four e4m3 (OCP) codes, saturating at +-448 (+-inf included).  The clamp is a compare-and-select, so a NaN passes
+// it (fminf / fmaxf would turn it into -448), and its code is forced to S.1111.111 whatever the conversion made of it.
+__device__ __forceinline__ uint32_t pack4_e4m3(float a, float b, float c, float d) {
+  constexpr float E4M3_MAX = 448.f;
+  const float ca = a > E4M3_MAX ? E4M3_MAX : (a < -E4M3_MAX ? -E4M3_MAX : a);
+  const float cb = b > E4M3_MAX ? E4M3_MAX : (b < -E4M3_MAX ? -E4M3_MAX : b);
+  const float cc = c > E4M3_MAX ? E4M3_MAX : (c < -E4M3_MAX ? -E4M3_MAX : c);
+  const float cd = d > E4M3_MAX ? E4M3_MAX : (d < -E4M3_MAX ? -E4M3_MAX : d);
+  uint32_t w = __builtin_amdgcn_cvt_pk_fp8_f32(ca, cb, 0u, false);
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(cc, cd, w, true);
+  const uint32_t nan = (a != a ? 0x7Fu : 0u) | (b != b ? 0x7F00u : 0u) | (c != c ? 0x7F0000u : 0u) | (d != d ? 0x7F000000u : 0u);
+  return w | nan;
+}
+
 // The total order (value descending, index ascending) of every ranking here (torch.topk with the lower index first among equals):
 // a strictly before b.  An empty entry (-inf, -1) is before nothing and every finite value is before it; a NaN is before nothing
 // and nothing is before it.  I is the index type of the caller: int where the indices are 32-bit, long for global rows.

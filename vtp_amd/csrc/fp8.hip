@@ -6,17 +6,6 @@
 
 namespace vtp {
 
-constexpr float E4M3_MAX = 448.f;
-
-__device__ __forceinline__ uint32_t pack4_e4m3(float a, float b, float c, float d) {
-  a = fminf(fmaxf(a, -E4M3_MAX), E4M3_MAX);
-  b = fminf(fmaxf(b, -E4M3_MAX), E4M3_MAX);
-  c = fminf(fmaxf(c, -E4M3_MAX), E4M3_MAX);
-  d = fminf(fmaxf(d, -E4M3_MAX), E4M3_MAX);
-  uint32_t w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0u, false);
-  return __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
-}
-
 // 8 elements per thread: 16 B (bf16) or 32 B (f32) in, 8 B out
 template <bool F32IN>
 __global__ __launch_bounds__(256) void quantize_e4m3_kernel(const void* __restrict__ src, uint8_t* __restrict__ dst, long n8,
@@ -42,6 +31,7 @@ __global__ __launch_bounds__(256) void quantize_e4m3_kernel(const void* __restri
 }
 
 // amax[0] = max(amax[0], max |x|)   (non-negative floats order like their bit patterns: integer atomicMax)
+// A NaN in the data leaves a NaN in amax[0]: every fold keeps it (max_nan), and |NaN| as an integer is above every finite value and inf.
 template <bool F32IN>
 __global__ __launch_bounds__(256) void amax_kernel(const void* __restrict__ src, long n8, float* __restrict__ amax) {
   __shared__ float red[4];
@@ -50,18 +40,19 @@ __global__ __launch_bounds__(256) void amax_kernel(const void* __restrict__ src,
     if constexpr (F32IN) {
       const f32x4 a = *(const f32x4*)((const float*)src + 8 * i), b = *(const f32x4*)((const float*)src + 8 * i + 4);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) m = fmaxf(m, fmaxf(fabsf(a[e]), fabsf(b[e])));
+      for (int e = 0; e < 4; ++e) m = max_nan(max_nan(m, fabsf(a[e])), fabsf(b[e]));
     } else {
       const bf16x8 a = *(const bf16x8*)((const bf16*)src + 8 * i);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf(bf2f(a[e])));
+      for (int e = 0; e < 8; ++e) m = max_nan(m, fabsf(bf2f(a[e])));
     }
   }
-  m = wave_max(m);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = max_nan(m, __shfl_xor(m, o, 64));
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
   __syncthreads();
   if (threadIdx.x == 0) {
-    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    m = max_nan(max_nan(red[0], red[1]), max_nan(red[2], red[3]));
     atomicMax((unsigned int*)amax, __float_as_uint(m));
   }
 }

@@ -704,19 +704,22 @@ extern "C" int vtp_gemm_nt_fp8(const void* A8, int lda, const void* B8, int ldb,
                                const int* rope_pos, const void* rope_sin, const void* rope_cos, int rope_cols, void* stream) {
   VTP_REQUIRE(A8 && B8 && C, "vtp_gemm_nt_fp8: null operand");
   VTP_REQUIRE(!rope_pos || (epilogue == VTP_EPI_BF16 && rope_sin && rope_cos && rope_cols % 128 == 0 && rope_cols <= N && N % 8 == 0 &&
-                            ldc % 8 == 0), "vtp_gemm_nt_fp8: fused RoPE needs the bf16 epilogue, both tables and rope_cols %% 128 == 0");
+                            ldc % 8 == 0),
+              "vtp_gemm_nt_fp8: fused RoPE needs the bf16 epilogue, both tables, rope_cols %% 128 == 0, rope_cols <= N and N, ldc %% 8 == 0");
   VTP_REQUIRE(M > 0 && N > 0 && K > 0, "vtp_gemm_nt_fp8: bad shape M=%d N=%d K=%d", M, N, K);
   VTP_REQUIRE(K % 16 == 0 && lda % 16 == 0 && ldb % 16 == 0, "vtp_gemm_nt_fp8: K, lda, ldb must be multiples of 16 (16-B rows)");
   VTP_REQUIRE(N % 4 == 0 && ldc % 4 == 0, "vtp_gemm_nt_fp8: N and ldc must be multiples of 4");
   VTP_REQUIRE(((uintptr_t)A8 % 16 == 0) && ((uintptr_t)B8 % 16 == 0) && ((uintptr_t)C % 16 == 0), "vtp_gemm_nt_fp8: operands must be 16-B aligned");
-  VTP_REQUIRE(epilogue == VTP_EPI_BF16 || epilogue == VTP_EPI_F32 || epilogue == VTP_EPI_SWIGLU, "vtp_gemm_nt_fp8: forward epilogues only");
-  VTP_REQUIRE(epilogue != VTP_EPI_SWIGLU || (N % 16 == 0 && bias), "vtp_gemm_nt_fp8: SwiGLU epilogue needs interleaved N %% 16 == 0 and a bias");
   GemmArgs a{};
   a.A = (const bf16*)A8; a.B = (const bf16*)B8; a.C = C; a.C2 = C2; a.bias = bias; a.resid = resid;
   a.M = M; a.N = N; a.K = K / 2; a.lda = lda / 2; a.ldb = ldb / 2; a.ldc = ldc; a.ldc2 = ldc2;  // 2-byte units for the staging side
   a.alpha = alpha;
   a.xcd_swizzle = swz_flags();
   a.k_split = (a.K + 63) / 64 * 64;
+  // the 8-phase kernel is the only one for fp8 operands, and it stages with 32-bit byte offsets from the operand bases
+  VTP_REQUIRE(gemm8p_fits(a, false), "vtp_gemm_nt_fp8: M x lda and N x ldb bytes must stay below 4 GiB (32-bit staging offsets)");
+  VTP_REQUIRE(epilogue == VTP_EPI_BF16 || epilogue == VTP_EPI_F32 || epilogue == VTP_EPI_SWIGLU, "vtp_gemm_nt_fp8: forward epilogues only");
+  VTP_REQUIRE(epilogue != VTP_EPI_SWIGLU || (N % 16 == 0 && bias), "vtp_gemm_nt_fp8: SwiGLU epilogue needs interleaved N %% 16 == 0 and a bias");
   if (rope_pos) {  // apply_rope in the epilogue, as in vtp_gemm_qkv_rope
     a.xcd_swizzle |= 2;
     a.rope_pos = rope_pos; a.rope_sin = (const bf16*)rope_sin; a.rope_cos = (const bf16*)rope_cos; a.rope_cols = rope_cols;

@@ -78,11 +78,7 @@ __global__ __launch_bounds__(256) void norm_fwd_kernel(const float* __restrict__
       const bf16x4 ob = __builtin_convertvector(o, bf16x4);
       if (y8) {
         const float qs = *q_scale;
-        float q[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) q[e] = fminf(fmaxf(bf2f(ob[e]) * qs, -448.f), 448.f);
-        uint32_t wq = __builtin_amdgcn_cvt_pk_fp8_f32(q[0], q[1], 0u, false);
-        wq = __builtin_amdgcn_cvt_pk_fp8_f32(q[2], q[3], wq, true);
+        const uint32_t wq = pack4_e4m3(bf2f(ob[0]) * qs, bf2f(ob[1]) * qs, bf2f(ob[2]) * qs, bf2f(ob[3]) * qs);  // a NaN stays a NaN code
         *(uint32_t*)(y8 + (size_t)row * D + col) = wq;
       } else if constexpr (!std::is_same_v<OUT, float>) {
         *(bf16x4*)(yr + col) = ob;

@@ -897,6 +897,10 @@ class Stack:
     def fp8_finalize(self):
         """weights -> e4m3 with scale 448 / amax(W); activation scales 448 / calibrated amax (x 1 / margin)"""
         f, dev = self.fp8, self.store.device
+        bad = (~torch.isfinite(f["amax"])).nonzero().cpu().tolist()  # a NaN / inf that arose in the calibration pass (vtp_amax keeps it)
+        if bad:
+            raise ValueError(f"fp8 calibration: the amax of block {bad[0][0]}, operand {bad[0][1]} (0 qkv, 1 proj, 2 w12, 3 w3 input) is "
+                             f"not finite ({float(f['amax'][bad[0][0], bad[0][1]])}): the calibration batch produced a NaN or an overflow")
         amax = f["amax"].clamp_min(1e-12)
         f["act_scale"] = (ops.E4M3_MAX / amax).contiguous()        # device [depth, 4]: read by the quantise kernels
         act_inv = (amax / ops.E4M3_MAX).cpu().tolist()               # host: the GEMM alphas

@@ -324,8 +324,12 @@ class VTPModel(nn.Module):
         lat = self._latents_nograd(calibration_images)
         if self.pixel_decoder is not None:
             self._decode_nograd(lat)
-        for stack in self._fp8_stacks():
-            stack.fp8_finalize()
+        try:
+            for stack in self._fp8_stacks():
+                stack.fp8_finalize()
+        except ValueError:  # a calibrated amax that is not finite: nothing stays half set up (the bf16 path runs as before)
+            self.disable_fp8_forward()
+            raise
         self._fp8_on = True
         return self
 
