@@ -234,6 +234,33 @@ def test_weight_step_within_the_sliced_chain_bound(mi):
     print(f"SEG-SGD M={M} ({S} slices): within the bound for N in {sorted(NHC)} and K in (40, 132, 260)")
 
 
+@pytest.mark.parametrize("mi", range(5))
+def test_one_slice_has_the_bits_of_probe_sgd(mi):
+    """Within one slice vtp_seg_sgd is vtp_probe_sgd: the same G^T X wave tile over the same rows, one partial to fold, the same two
+    fmaf lines (csrc/wave_f32.h).  From non-zero momentum buffers, X a column slice of a wider matrix; N = 111 straddles the
+    64-row tile and the head boundary."""
+    _gpu()
+    from vtp_amd import ops
+    M = (1, 2, 7, 130, ops.seg_sgd_slice())[mi]
+    mom = 0.9
+    for H, C in ((1, 7), (3, 37)):
+        N = H * C
+        for K in (40, 132):
+            g = torch.Generator().manual_seed(2000 * mi + N + K)
+            Gm, X = 0.1 * torch.randn(M, N, generator=g), torch.randn(M, K, generator=g)
+            state = [0.05 * torch.randn(N, K, generator=g), 0.05 * torch.randn(N, generator=g),
+                     0.02 * torch.randn(N, K, generator=g), 0.02 * torch.randn(N, generator=g)]  # W, bias, mW, mb
+            lr = torch.tensor([0.1 * (hh + 1) for hh in range(H)], dtype=F32).to(DEV)
+            Gd, Xd = Gm.to(DEV), _sliced(X)
+            seg, probe = [t.to(DEV) for t in state], [t.to(DEV) for t in state]
+            ws = torch.empty(ops.seg_sgd_workspace_bytes(M, N, K), device=DEV, dtype=torch.uint8)
+            ops.seg_sgd(*seg, Gd, Xd, lr, M, H, C, K, mom, ws)
+            ops.probe_sgd(*probe, Gd, Xd, lr, M, H, C, K, mom)
+            for name, a, b, t0 in zip(("W", "bias", "mW", "mb"), seg, probe, state):
+                assert not torch.equal(a.cpu(), t0), (name, "the step changed nothing")
+                assert torch.equal(a.view(torch.int32), b.view(torch.int32)), (name, M, H, C, K)
+
+
 # ---------------------------------------------------------------------------------------------------------------- 4. repeatability
 def _probe(heads, C, D, seed=0, **kw):
     from vtp_amd import SegProbe

@@ -150,6 +150,25 @@ def test_logits_within_the_fp32_chain_bound(B, C, D):
     assert bool(got["wide"][:, C:].isnan().all()), "wrote past column C"
 
 
+@pytest.mark.parametrize("scale", [1.0, 100.0])
+@pytest.mark.parametrize("B", [1, 33, 70])
+def test_logits_have_the_bits_of_probe_logits_with_a_zero_bias(B, scale):
+    """Both kernels run the k unit of csrc/wave_f32.h, so the optional logits output is vtp_probe_logits on the same F and W with a
+    zero bias, bit for bit; with a scale, on (scale * F) formed in fp32 beforehand: "rounded once, then the product chain".
+    D = 36 ends in a unit tail, D = 8 is less than one unit."""
+    _gpu()
+    from vtp_amd import ops
+    for C in (7, 37, 100):
+        for D in (8, 36, 100):
+            f, wt, y = real_case(B, C, D)
+            fd, wd = _sliced(f), wt.to(DEV)
+            got = run_topk(fd, wd, y, scale)["logits"]
+            want = torch.full((B, C), NAN, device=DEV, dtype=F32)
+            scaled = fd if scale == 1.0 else _sliced(torch.tensor(scale, dtype=F32) * f)
+            ops.probe_logits(scaled, wd, torch.zeros(C, device=DEV, dtype=F32), want, B, C, D)
+            assert torch.equal(got.view(I32), want.cpu().view(I32)), (B, C, D, scale)
+
+
 # ---------------------------------------------------------------------------------------------------------------- 3. exact ranks
 @functools.lru_cache(maxsize=None)
 def dyadic_case(B, C, D):

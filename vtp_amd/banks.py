@@ -45,6 +45,17 @@ class Group:
         self.dist.all_gather(parts, src, group=self.group)
         return [p.to(t.device) for p in parts] if host else parts
 
+    def all_gather_rows(self, out: torch.Tensor, inp: torch.Tensor) -> None:
+        """out [world * B, ...] = the rows inp [B, ...] of every rank in rank order: RCCL all-gather into the tensor, or zero + copy +
+        all_reduce on backends without it"""
+        if self.dist.get_backend(self.group) == "nccl":
+            self.dist.all_gather_into_tensor(out, inp, group=self.group)
+        else:
+            B = inp.shape[0]
+            out.zero_()
+            out[self.rank * B:(self.rank + 1) * B].copy_(inp)
+            self.dist.all_reduce(out, group=self.group)
+
 
 def spans(n: int, step: int) -> Iterator[Tuple[int, int]]:
     """(lo, hi) of the pieces of at most `step` that cover range(n), in order"""

@@ -9,8 +9,8 @@
 // Every output element has exactly one writer and a reduction order that depends on neither its tile nor its position in it: two
 // heads with equal parameters stay bit-identical, and so do data-parallel replicas that run the same full-batch step.
 #include "common.h"
-#include "mfma_f32.h"
 #include "vtp_hip.h"
+#include "wave_f32.h"
 
 #include <limits.h>
 
@@ -19,28 +19,8 @@ namespace vtp {
 // ---------------------------------------------------------------------------------------------------------------- logits
 // One wave = 64 rows x 32 columns of the output over the whole of K; no LDS, no barrier.  Waves that share a column strip sit
 // next to each other (the row pair is the fast task index), so a W strip comes from HBM once and X (<= 2 MB) from L2.
-// A k unit is 32 wide: per 8-wide chunk c the lane half h = l >> 5 loads the 16 bytes at k0 + 8 c + 4 h of its row and the four
-// elements feed four MFMAs -- A and B use the same (h, element) -> k map, so the product only permutes the order of the sum.
-// Chunks past K load zeros (K % 4 == 0 keeps a 16-byte load inside its row).  The next unit is loaded before the current one's
-// 32 MFMAs (2048 cycles) are issued: one wave per SIMD has to cover the HBM latency by itself.
-struct ProbeUnit {
-  f32x4 w[4], x0[4], x1[4];
-};
-
-__device__ __forceinline__ void probe_load_unit(ProbeUnit& u, const float* __restrict__ wp, const float* __restrict__ xp0,
-                                                const float* __restrict__ xp1, int k0, int half, int K) {
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    const int k = k0 + 8 * c + 4 * half;
-    const int kc = k < K ? k : K - 4;
-    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-    const f32x4 w = *(const f32x4*)(wp + kc), a = *(const f32x4*)(xp0 + kc), b = *(const f32x4*)(xp1 + kc);
-    u.w[c] = k < K ? w : z;
-    u.x0[c] = k < K ? a : z;
-    u.x1[c] = k < K ? b : z;
-  }
-}
-
+// The k unit (32 wide, wave_f32.h) holds both rows.  The next unit is loaded before the current one's 32 MFMAs (2048 cycles) are
+// issued: one wave per SIMD has to cover the HBM latency by itself.
 __global__ __launch_bounds__(256) void probe_logits_kernel(const float* __restrict__ X, int ldx, const float* __restrict__ W,
                                                           const float* __restrict__ bias, float* __restrict__ logits, int ldl, int B,
                                                           int N, int K, int row_pairs, int tasks) {
@@ -51,31 +31,25 @@ __global__ __launch_bounds__(256) void probe_logits_kernel(const float* __restri
   const int n = n0 + r, nc = n < N ? n : N - 1;
   const int ba = b0 + r, bb = b0 + 32 + r;
   const float* wp = W + (long)nc * K;
-  const float* xp0 = X + (long)(ba < B ? ba : B - 1) * ldx;  // rows past B: a valid row, results never stored
-  const float* xp1 = X + (long)(bb < B ? bb : B - 1) * ldx;
+  // rows past B: a valid row, results never stored
+  const float* const xp[2] = {X + (long)(ba < B ? ba : B - 1) * ldx, X + (long)(bb < B ? bb : B - 1) * ldx};
   const float bn = bias[nc];
-  f32x16 acc0, acc1;
+  f32x16 acc[2];
 #pragma unroll
-  for (int i = 0; i < 16; ++i) acc0[i] = acc1[i] = bn;  // the bias opens the chain: K + 1 roundings per element
-  ProbeUnit cur, nxt;
-  probe_load_unit(cur, wp, xp0, xp1, 0, half, K);
+  for (int i = 0; i < 16; ++i) acc[0][i] = acc[1][i] = bn;  // the bias opens the chain: K + 1 roundings per element
+  WaveUnit<2> cur, nxt;
+  wave_load_unit<2, false>(cur, wp, xp, 0, half, K);
   for (int k0 = 0; k0 < K; k0 += 32) {
-    probe_load_unit(nxt, wp, xp0, xp1, k0 + 32, half, K);  // past K: clamped addresses, zeros (never used after the last unit)
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        acc0 = mfma32(cur.x0[c][e], cur.w[c][e], acc0);
-        acc1 = mfma32(cur.x1[c][e], cur.w[c][e], acc1);
-      }
+    wave_load_unit<2, false>(nxt, wp, xp, k0 + 32, half, K);  // past K: clamped addresses, zeros (never used after the last unit)
+    wave_mma_unit(cur, acc);
     cur = nxt;
   }
   if (n >= N) return;
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
     const int b = b0 + acc_row(i, half);
-    if (b < B) logits[(long)b * ldl + n] = acc0[i];
-    if (b + 32 < B) logits[(long)(b + 32) * ldl + n] = acc1[i];
+    if (b < B) logits[(long)b * ldl + n] = acc[0][i];
+    if (b + 32 < B) logits[(long)(b + 32) * ldl + n] = acc[1][i];
   }
 }
 
@@ -131,10 +105,9 @@ __global__ __launch_bounds__(256) void probe_ce_kernel(const float* __restrict__
 }
 
 // ---------------------------------------------------------------------------------------------------------------- SGD step
-// One wave = a 64 (rows n) x 64 (columns k) tile of W: dW = dlogits^T X over the batch in four independent 32x32 accumulators
-// (A = dlogits^T: lane l reads dlogits[b + (l >> 5)][n0 + (l & 31)], B = X[b + (l >> 5)][k0 + (l & 31)], both 128-byte rows from L2),
-// then one read-modify-write of mW and W in the accumulator layout -- 16 bytes of HBM traffic per parameter, dW never stored.
-// Rows of the batch past B are zeros (the MFMA k step is 2).  The waves of k tile 0 also form db and update bias / mb.
+// One wave = a 64 (rows n) x 64 (columns k) tile of W: dW = dlogits^T X over the whole batch (the G^T X tile of wave_f32.h), then one
+// read-modify-write of mW and W in the accumulator layout -- 16 bytes of HBM traffic per parameter, dW never stored.
+// The waves of k tile 0 also form db and update bias / mb.
 // The learning rate is looked up per output row n / C: 1000 classes are no multiple of 64, so a tile straddles heads.
 __global__ __launch_bounds__(256) void probe_sgd_kernel(float* __restrict__ W, float* __restrict__ bias, float* __restrict__ mW,
                                                        float* __restrict__ mb, const float* __restrict__ dl, int ldl,
@@ -145,52 +118,26 @@ __global__ __launch_bounds__(256) void probe_sgd_kernel(float* __restrict__ W, f
   if (task >= tasks) return;
   const int n0 = (task / k_tiles) * 64, k0 = (task % k_tiles) * 64;
   const int na = n0 + r, nb = n0 + 32 + r, ka = k0 + r, kb = k0 + 32 + r;
-  const float* dpa = dl + (na < N ? na : N - 1);
-  const float* dpb = dl + (nb < N ? nb : N - 1);
-  const float* xpa = X + (ka < K ? ka : K - 1);
-  const float* xpb = X + (kb < K ? kb : K - 1);
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) acc[0][0][i] = acc[0][1][i] = acc[1][0][i] = acc[1][1][i] = 0.f;
-#pragma unroll 4
-  for (int b0 = 0; b0 < B; b0 += 2) {
-    const int b = b0 + half;
-    const long bc = b < B ? b : B - 1;
-    float a0 = dpa[bc * ldl], a1 = dpb[bc * ldl], x0 = xpa[bc * ldx], x1 = xpb[bc * ldx];
-    a0 = (b < B && na < N) ? a0 : 0.f;
-    a1 = (b < B && nb < N) ? a1 : 0.f;
-    x0 = (b < B && ka < K) ? x0 : 0.f;
-    x1 = (b < B && kb < K) ? x1 : 0.f;
-    acc[0][0] = mfma32(a0, x0, acc[0][0]);
-    acc[0][1] = mfma32(a0, x1, acc[0][1]);
-    acc[1][0] = mfma32(a1, x0, acc[1][0]);
-    acc[1][1] = mfma32(a1, x1, acc[1][1]);
-  }
-#pragma unroll
-  for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int n = n0 + 32 * ti + acc_row(i, half);
-      if (n >= N) continue;
-      const float nlr = -lr[n / C];
-#pragma unroll
-      for (int tj = 0; tj < 2; ++tj) {
-        const int k = k0 + 32 * tj + r;
-        if (k >= K) continue;
+  wave_gtx_tile<1>(acc, dl + (na < N ? na : N - 1), dl + (nb < N ? nb : N - 1), ldl, X + (ka < K ? ka : K - 1), X + (kb < K ? kb : K - 1),
+                ldx, na >= N, nb >= N, ka >= K, kb >= K, 0, B, half);
+  wave_gtx_visit(
+      acc, n0, k0, N, K, r, half, [&](int n) { return -lr[n / C]; },
+      [&](int n, int k, float d, float nlr) {
         const long idx = (long)n * K + k;
-        const float m = fmaf(momentum, mW[idx], acc[ti][tj][i]);
+        float m = mW[idx];
+        float w = W[idx];
+        sgd_momentum_step(w, m, d, momentum, nlr);
         mW[idx] = m;
-        W[idx] = fmaf(nlr, m, W[idx]);
-      }
-    }
+        W[idx] = w;
+      });
   if (k0 == 0) {
     const int n = n0 + lane;
     if (n < N) {
-      float db = 0.f;
-      for (int b = 0; b < B; ++b) db += dl[(long)b * ldl + n];
-      const float m = fmaf(momentum, mb[n], db);
+      float w = bias[n], m = mb[n];
+      sgd_momentum_step(w, m, wave_gtx_colsum(dl + n, ldl, 0, B), momentum, -lr[n / C]);
       mb[n] = m;
-      bias[n] = fmaf(-lr[n / C], m, bias[n]);
+      bias[n] = w;
     }
   }
 }

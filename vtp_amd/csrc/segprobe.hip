@@ -8,8 +8,8 @@
 // of a pixel from that one function, and the blend from seg_blend, so the forward and the gradient agree on every pixel.
 // No float atomics anywhere: every float has one writer and one summation order; the confusion counts are integer atomics.
 #include "common.h"
-#include "mfma_f32.h"
 #include "vtp_hip.h"
+#include "wave_f32.h"
 
 #include <limits.h>
 
@@ -262,8 +262,8 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_dlogits_kernel(const float* _
 }
 
 // ---------------------------------------------------------------------------------------------------------------- weight step
-// probe_sgd_kernel's tile (one wave = 64 rows n x 64 columns k, four 32x32 accumulators, k-ordered fmaf chains) over ONE slice of
-// SEG_SLICE token rows; the partial tile goes to wsW [S, N, K], the partial column sums of G to wsb [S, N].
+// The G^T X tile of wave_f32.h (one wave = 64 rows n x 64 columns k, the tile of probe_sgd_kernel) over ONE slice of SEG_SLICE token
+// rows; the partial tile goes to wsW [S, N, K], the partial column sums of G to wsb [S, N].
 __global__ __launch_bounds__(SEG_THREADS) void seg_wgrad_kernel(const float* __restrict__ G, int ldg, const float* __restrict__ X, int ldx,
                                                                int M, int N, int K, int k_tiles, int n_tiles, long tasks,
                                                                float* __restrict__ wsW, float* __restrict__ wsb) {
@@ -275,57 +275,19 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_wgrad_kernel(const float* __r
   const int nt = (int)(t2 % n_tiles), s = (int)(t2 / n_tiles);
   const int n0 = nt * 64, k0 = kt * 64, m0 = s * SEG_SLICE, m1 = min(M, m0 + SEG_SLICE);
   const int na = n0 + r, nb = n0 + 32 + r, ka = k0 + r, kb = k0 + 32 + r;
-  const float* gpa = G + (na < N ? na : N - 1);
-  const float* gpb = G + (nb < N ? nb : N - 1);
-  const float* xpa = X + (ka < K ? ka : K - 1);
-  const float* xpb = X + (kb < K ? kb : K - 1);
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) acc[0][0][i] = acc[0][1][i] = acc[1][0][i] = acc[1][1][i] = 0.f;
-  for (int b0 = m0; b0 < m1; b0 += 8) {  // four k steps of 2 rows in flight; rows past the slice end are zeros: exact no-ops at the chain's end
-    float a0[4], a1[4], x0[4], x1[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int b = b0 + 2 * u + half;
-      const long bc = b < m1 ? b : m1 - 1;
-      a0[u] = gpa[bc * ldg], a1[u] = gpb[bc * ldg], x0[u] = xpa[bc * ldx], x1[u] = xpb[bc * ldx];
-      a0[u] = (b < m1 && na < N) ? a0[u] : 0.f;
-      a1[u] = (b < m1 && nb < N) ? a1[u] : 0.f;
-      x0[u] = (b < m1 && ka < K) ? x0[u] : 0.f;
-      x1[u] = (b < m1 && kb < K) ? x1[u] : 0.f;
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      acc[0][0] = mfma32(a0[u], x0[u], acc[0][0]);
-      acc[0][1] = mfma32(a0[u], x1[u], acc[0][1]);
-      acc[1][0] = mfma32(a1[u], x0[u], acc[1][0]);
-      acc[1][1] = mfma32(a1[u], x1[u], acc[1][1]);
-    }
-  }
+  wave_gtx_tile<4>(acc, G + (na < N ? na : N - 1), G + (nb < N ? nb : N - 1), ldg, X + (ka < K ? ka : K - 1), X + (kb < K ? kb : K - 1), ldx,
+                na >= N, nb >= N, ka >= K, kb >= K, m0, m1, half);
   float* out = wsW + (long)s * N * K;
-#pragma unroll
-  for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int n = n0 + 32 * ti + acc_row(i, half);
-      if (n >= N) continue;
-#pragma unroll
-      for (int tj = 0; tj < 2; ++tj) {
-        const int k = k0 + 32 * tj + r;
-        if (k < K) out[(long)n * K + k] = acc[ti][tj][i];
-      }
-    }
+  wave_gtx_visit(
+      acc, n0, k0, N, K, r, half, [&](int n) { return out + (long)n * K; }, [](int, int k, float d, float* out_row) { out_row[k] = d; });
   if (k0 == 0) {
     const int n = n0 + lane;
-    if (n < N) {
-      float db = 0.f;
-      for (int b = m0; b < m1; ++b) db += G[(long)b * ldg + n];
-      wsb[(long)s * N + n] = db;
-    }
+    if (n < N) wsb[(long)s * N + n] = wave_gtx_colsum(G + n, ldg, m0, m1);
   }
 }
 
-// one owner per four weights (or one bias): the S partials added in slice order, then the two fmaf lines of vtp_probe_sgd
+// one owner per four weights (or one bias): the S partials added in slice order, then vtp_probe_sgd's step (sgd_momentum_step)
 __global__ __launch_bounds__(SEG_THREADS) void seg_sgd_fold_kernel(float* __restrict__ W, float* __restrict__ bias, float* __restrict__ mW,
                                                                   float* __restrict__ mb, const float* __restrict__ wsW,
                                                                   const float* __restrict__ wsb, const float* __restrict__ lr, int S, int N,
@@ -339,8 +301,9 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_sgd_fold_kernel(float* __rest
     f32x4 m = ((f32x4*)mW)[i], x = ((f32x4*)W)[i];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      m[e] = fmaf(momentum, m[e], d[e]);
-      x[e] = fmaf(nlr, m[e], x[e]);
+      float we = x[e], me = m[e];
+      sgd_momentum_step(we, me, d[e], momentum, nlr);
+      x[e] = we, m[e] = me;
     }
     ((f32x4*)mW)[i] = m;
     ((f32x4*)W)[i] = x;
@@ -348,9 +311,10 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_sgd_fold_kernel(float* __rest
     const int n = (int)(i - nk4);
     float d = wsb[n];
     for (int s = 1; s < S; ++s) d += wsb[(long)s * N + n];
-    const float m = fmaf(momentum, mb[n], d);
+    float w = bias[n], m = mb[n];
+    sgd_momentum_step(w, m, d, momentum, -lr[n / C]);
     mb[n] = m;
-    bias[n] = fmaf(-lr[n / C], m, bias[n]);
+    bias[n] = w;
   }
 }
 

@@ -5,8 +5,8 @@
 // every logit is the same sequential fmaf chain over k whichever tile, lane or launch geometry computes it (no split of k).
 // Counters are integers and only integer atomics touch them: counts and ranks are bit-reproducible from run to run.
 #include "common.h"
-#include "mfma_f32.h"
 #include "vtp_hip.h"
+#include "wave_f32.h"
 
 #include <limits.h>
 
@@ -50,60 +50,36 @@ __global__ __launch_bounds__(256) void zs_class_mean_kernel(const float* __restr
 // unit of prefetch took 193 us, so neither occupancy nor prefetch depth is what it waits for.  Every lane loads its own row
 // (a wave's 16-byte loads touch 32 cache lines each, and every tile re-reads the feature block): operands staged through LDS
 // from line-wide loads, and a split of the classes over workgroups, are not built (profiles/README.md).
-//   k order of a chain: per 32-wide unit and 8-wide chunk c the lane half h = l >> 5 loads the 16 bytes at k0 + 8 c + 4 h of its
-//   row; element e of both operands feeds MFMA (c, e).  Chunks past K load zeros (K % 4 == 0 keeps a load inside its row).
-//   The feature is scaled as it is loaded: (scale * F) rounded once, then the product chain -- the tool's (100.0 * f) @ W.
+//   k order of a chain: the k unit of wave_f32.h, one row of F per lane.  The feature is scaled as it is loaded: (scale * F) rounded
+//   once, then the product chain -- the tool's (100.0 * f) @ W.
 // The target's logit: with one chunk it is read from LDS.  With several it is needed before its column has been computed, so
 // wave 0 first multiplies the row block by the 32 gathered target rows Wt[t_b] and keeps the diagonal -- the same chain on the
 // same operands as the element z[b, t_b] of the regular tile, hence the same bits.
 constexpr int ZS_ROWS = 32, ZS_MAX_CH = 1024, ZS_WAVES = 8, ZS_PER_LANE = ZS_MAX_CH / 64;
 
-struct ZsUnit {
-  f32x4 w[4], x[4];
-};
-
-__device__ __forceinline__ void zs_load_unit(ZsUnit& u, const float* __restrict__ wp, const float* __restrict__ xp, int k0, int half,
-                                             int K, float scale) {
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    const int k = k0 + 8 * c + 4 * half;
-    const int kc = k < K ? k : K - 4;
-    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-    const f32x4 w = *(const f32x4*)(wp + kc), x = *(const f32x4*)(xp + kc);
-    u.w[c] = k < K ? w : z;
-    u.x[c] = k < K ? x * scale : z;
-  }
-}
-
-__device__ __forceinline__ f32x16 zs_mma_unit(const ZsUnit& u, f32x16 acc) {
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc = mfma32(u.x[c][e], u.w[c][e], acc);
-  return acc;
-}
-
 // 32 rows (xp: the lane's row of F) x 32 columns (wp: the lane's row of Wt) over the whole of K.  Two units are in flight beyond
 // the one being multiplied (three named units in rotation, no register copies).  Loads past K go to clamped addresses and are
 // never multiplied.
 __device__ __forceinline__ f32x16 zs_tile(const float* __restrict__ wp, const float* __restrict__ xp, int half, int K, float scale) {
-  f32x16 acc;
+  f32x16 acc[1];
 #pragma unroll
-  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-  ZsUnit u0, u1, u2;
-  zs_load_unit(u0, wp, xp, 0, half, K, scale);
-  zs_load_unit(u1, wp, xp, 32, half, K, scale);
+  for (int i = 0; i < 16; ++i) acc[0][i] = 0.f;
+  const float* const xs[1] = {xp};
+  auto load = [&](WaveUnit<1>& u, int k0) { wave_load_unit<1, true>(u, wp, xs, k0, half, K, scale); };
+  WaveUnit<1> u0, u1, u2;
+  load(u0, 0);
+  load(u1, 32);
   for (int k0 = 0; k0 < K; k0 += 96) {
-    zs_load_unit(u2, wp, xp, k0 + 64, half, K, scale);
-    acc = zs_mma_unit(u0, acc);
+    load(u2, k0 + 64);
+    wave_mma_unit(u0, acc);
     if (k0 + 32 >= K) break;
-    zs_load_unit(u0, wp, xp, k0 + 96, half, K, scale);
-    acc = zs_mma_unit(u1, acc);
+    load(u0, k0 + 96);
+    wave_mma_unit(u1, acc);
     if (k0 + 64 >= K) break;
-    zs_load_unit(u1, wp, xp, k0 + 128, half, K, scale);
-    acc = zs_mma_unit(u2, acc);
+    load(u1, k0 + 128);
+    wave_mma_unit(u2, acc);
   }
-  return acc;
+  return acc[0];
 }
 
 __global__ __launch_bounds__(ZS_WAVES * 64) void zs_topk_kernel(const float* __restrict__ F, int ldf, const float* __restrict__ Wt,

@@ -603,7 +603,8 @@ def probe_sgd(w, bias, mw, mb, dlogits, x, lr, B, H, C, K, momentum):
                                      B, H, C, K, momentum, _s()), "vtp_probe_sgd")
 
 
-def _seg_bytes(fn, *args):
+def _size_or_raise(fn, *args):
+    """the size a library entry point returns; a negative one is a refusal: ValueError with the library's message"""
     n = fn(*args)
     if n < 0:
         raise ValueError(_lib_().vtp_last_error().decode(errors="replace"))
@@ -612,7 +613,7 @@ def _seg_bytes(fn, *args):
 
 def seg_ce_workspace_bytes(B, h, w, Hl, Wl, H, C):
     """bytes of workspace seg_ce needs; ValueError for arguments the kernel refuses or a workspace above 2 GiB"""
-    return _seg_bytes(_lib_().vtp_seg_ce_workspace_bytes, B, h, w, Hl, Wl, H, C)
+    return _size_or_raise(_lib_().vtp_seg_ce_workspace_bytes, B, h, w, Hl, Wl, H, C)
 
 
 def seg_ce(z, labels, hw, H, C, ignore_index, loss, call_counts, workspace, lse=None, conf=None, totals=None):
@@ -662,7 +663,7 @@ def seg_sgd_slice():
 
 def seg_sgd_workspace_bytes(M, N, K):
     """bytes of workspace seg_sgd needs for M token rows and N = H * C outputs; ValueError for refused arguments or above 2 GiB"""
-    return _seg_bytes(_lib_().vtp_seg_sgd_workspace_bytes, M, N, K)
+    return _size_or_raise(_lib_().vtp_seg_sgd_workspace_bytes, M, N, K)
 
 
 def seg_sgd(w, bias, mw, mb, g, x, lr, M, H, C, K, momentum, workspace):
@@ -694,10 +695,7 @@ KNN_MAX_K = 256
 def knn_workspace_bytes(B, K, splits=0):
     """bytes of workspace knn_topk needs for B queries, lists of K and that many splits (0: whatever the heuristic may pick at this
     B); ValueError for arguments the kernel refuses or a workspace above 2 GiB"""
-    n = _lib_().vtp_knn_workspace_bytes(B, K, splits)
-    if n < 0:
-        raise ValueError(_lib_().vtp_last_error().decode(errors="replace"))
-    return n
+    return _size_or_raise(_lib_().vtp_knn_workspace_bytes, B, K, splits)
 
 
 def knn_topk(q, x, index_base, K, sims, idx, workspace, splits=0, sims_out=None):
@@ -762,10 +760,7 @@ def _pr_rows(**tensors):
 def pr_workspace_bytes(B, splits=0):
     """bytes of workspace pr_knn_dist needs for B queries and that many splits (0: whatever the heuristic may pick at this B):
     splits * B * 32; ValueError for arguments the kernel refuses or a workspace above 2 GiB"""
-    n = _lib_().vtp_pr_workspace_bytes(B, splits)
-    if n < 0:
-        raise ValueError(_lib_().vtp_last_error().decode(errors="replace"))
-    return n
+    return _size_or_raise(_lib_().vtp_pr_workspace_bytes, B, splits)
 
 
 def pr_sqnorm(x, out):
@@ -827,10 +822,7 @@ MMD_MAX_DEGREE = 8
 def mmd_workspace_bytes(B, N, P=1):
     """bytes of the part buffer of mmd_poly_part for B queries, N bank rows and P problems: P * ceil(N / 128) * B * 8; ValueError for
     arguments the kernel refuses or a buffer above 2 GiB"""
-    n = _lib_().vtp_mmd_workspace_bytes(B, N, P)
-    if n < 0:
-        raise ValueError(_lib_().vtp_last_error().decode(errors="replace"))
-    return n
+    return _size_or_raise(_lib_().vtp_mmd_workspace_bytes, B, N, P)
 
 
 def mmd_poly_part(q, x, part, gamma, coef0=1.0, degree=3, query_base=-1, index_base=0, qi=None, xi=None):
@@ -982,10 +974,7 @@ def is_accum(p, h, state, row_base, split_size=None):
 def recon_scratch_size(B, H, W):
     """number of f64 elements the scratch of recon_metrics / recon_finalize must hold for a [B, 3, H, W] batch (two per tile of
     window positions); ValueError for a shape the kernels refuse (H or W below 11, W % 4 != 0, B < 1)"""
-    n = _lib_().vtp_recon_scratch_doubles(B, H, W)
-    if n < 0:
-        raise ValueError(_lib_().vtp_last_error().decode(errors="replace"))
-    return n
+    return _size_or_raise(_lib_().vtp_recon_scratch_doubles, B, H, W)
 
 
 def recon_metrics(images, recon, sub, div, scratch, ref_u8=None, rec_u8=None, ref_lp=None, rec_lp=None):
@@ -1007,10 +996,7 @@ def recon_finalize(scratch, B, H, W, psnr, ssim, acc, sse=None, lpips=None):
 def augment_scratch_size(N, S):
     """number of f32 elements the scratch of augment_crops must hold for N crops of S x S (the resampled crops and the per-tile
     gray sums); ValueError for a shape the kernels refuse (N < 1, S < 5)"""
-    n = _lib_().vtp_augment_scratch_floats(N, S)
-    if n < 0:
-        raise ValueError(_lib_().vtp_last_error().decode(errors="replace"))
-    return n
+    return _size_or_raise(_lib_().vtp_augment_scratch_floats, N, S)
 
 
 def augment_crops(u8_nhwc, table, out, mean, std, scratch):

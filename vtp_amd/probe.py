@@ -9,13 +9,13 @@ weight-gradient + SGD-momentum kernel (csrc/probe.hip) -- no nn.Linear, no autog
 There is no CPU path: tensors on the CPU raise."""
 from __future__ import annotations
 
-import math
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
 from . import ops
 from .banks import Group, eval_device
+from .heads import HeadGroup, HeadStore, cosine_factor
 
 DEFAULT_LEARNING_RATES = (1e-5, 2e-5, 5e-5, 1e-4, 2e-4, 5e-4, 1e-3, 2e-3, 5e-3, 1e-2, 2e-2, 5e-2, 0.1)  # the tool's sweep (:61-64)
 Head = Tuple[str, int, bool, float]  # (key, use_n_blocks, use_avgpool, lr)
@@ -57,24 +57,10 @@ def init_heads(heads: Sequence[Head], embed_dim: int, num_classes: int) -> Dict[
     return out
 
 
-def cosine_factor(step: int, max_iter: Optional[int]) -> float:
-    """CosineAnnealingLR(max_iter, eta_min=0) in closed form (fp64): the rate of optimizer step `step` (0-based) over its base"""
-    return 1.0 if max_iter is None else 0.5 * (1.0 + math.cos(math.pi * step / max_iter))
-
-
-class _Group:
-    """the heads that share one input: a contiguous column slice [col0, col0 + K) of X_all"""
-
-    def __init__(self, n: int, avgpool: bool):
-        self.n, self.avgpool = n, avgpool
-        self.keys: List[str] = []
-        self.base_lr: List[float] = []
-
-
 class LinearProbe:
     """heads: (key, use_n_blocks, use_avgpool, lr) tuples; heads with equal (use_n_blocks, use_avgpool) form a feature group and
-    are stored stacked (weight [H, C, in], bias [H, C] and their momentum buffers, contiguous fp32).  `keys` lists the heads
-    group by group, which is the order of every per-head vector (losses, counts); for a sweep it is the reference's order.
+    are stored stacked (heads.HeadStore: weight [H, C, in], bias [H, C] and their momentum buffers, contiguous fp32).  `keys` lists
+    the heads group by group, which is the order of every per-head vector (losses, counts); for a sweep it is the reference's order.
     model may be None when only step_features / evaluate_features are used (then pass embed_dim)."""
 
     def __init__(self, model, heads: Sequence[Head], num_classes: int, momentum: float = 0.9, max_iter: Optional[int] = None,
@@ -95,27 +81,16 @@ class LinearProbe:
             raise ValueError("no heads")
         init = init_heads(heads, self.D, self.C)
         self.n_max = max(h[1] for h in kept)
-        self.groups: List[_Group] = []
-        for key, n, avgpool, lr in kept:
+        for key, n, _, _ in kept:
             if n < 1:
                 raise ValueError(f"{key}: use_n_blocks must be >= 1")
-            g = next((g for g in self.groups if (g.n, g.avgpool) == (n, avgpool)), None)
-            if g is None:
-                g = _Group(n, avgpool)
-                self.groups.append(g)
-            g.keys.append(key)
-            g.base_lr.append(lr)
-        self.keys: List[str] = []
-        f32 = dict(device=self.device, dtype=torch.float32)
-        for g in self.groups:
-            g.H, g.K, g.col0, g.off = len(g.keys), (g.n + (1 if g.avgpool else 0)) * self.D, (self.n_max - g.n) * self.D, len(self.keys)
-            self.keys += g.keys
-            g.weight = torch.stack([init[k][0] for k in g.keys]).to(**f32).contiguous()
-            g.bias = torch.stack([init[k][1] for k in g.keys]).to(**f32).contiguous()
-            g.m_weight, g.m_bias = torch.zeros_like(g.weight), torch.zeros_like(g.bias)
-            g.lr = torch.zeros(g.H, **f32)
-            g.buf = {}
+        # a group reads the class tokens of its last n blocks and, with avgpool, the pooled patch tokens behind them
+        self.heads = HeadStore([(key, (n, avgpool), (n + (1 if avgpool else 0)) * self.D, (self.n_max - n) * self.D, lr)
+                                for key, n, avgpool, lr in kept], init, self.device, max_iter)
         del init
+        self.groups, self.keys = self.heads.groups, self.heads.keys
+        for g in self.groups:
+            g.buf = {}
         self.steps = 0
         self._correct = torch.zeros(len(self.keys), device=self.device, dtype=torch.int32)
         self._total = 0
@@ -156,28 +131,16 @@ class LinearProbe:
             raise ValueError(f"labels must be {B} integer class indices, got {labels.dtype} {tuple(labels.shape)}")
         return labels.detach().to(torch.int64).contiguous()
 
-    def _bufs(self, g: _Group, B: int):
+    def _bufs(self, g: HeadGroup, B: int):
         if B not in g.buf:
             f32 = dict(device=self.device, dtype=torch.float32)
             g.buf = {B: (torch.empty(B, g.H * self.C, **f32), torch.empty(B, g.H * self.C, **f32),
                          torch.empty(B * self.world, g.H * self.C, **f32) if self.world > 1 else None)}
         return g.buf[B]
 
-    def _all_gather_rows(self, out: torch.Tensor, inp: torch.Tensor):
-        """rows of every rank in rank order: RCCL all-gather, or all_reduce on backends without it (VTPTrainer._all_gather_rows)"""
-        dist = self._group.dist
-        if dist.get_backend(self.group) == "nccl":
-            dist.all_gather_into_tensor(out, inp, group=self.group)
-        else:
-            B = inp.shape[0]
-            out.zero_()
-            out[self.rank * B:(self.rank + 1) * B].copy_(inp)
-            dist.all_reduce(out, group=self.group)
-
     # ------------------------------------------------------------------------------------------------ training
     def learning_rates(self, step: Optional[int] = None) -> Dict[str, float]:
-        f = cosine_factor(self.steps if step is None else step, self.max_iter)
-        return {k: lr * f for g in self.groups for k, lr in zip(g.keys, g.base_lr)}
+        return self.heads.learning_rates(self.steps if step is None else step)
 
     def step(self, images: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
         return self.step_features(self.features(images), labels)
@@ -191,18 +154,18 @@ class LinearProbe:
         x_all = x
         if self.world > 1:  # DDP's gradient mean, without a dW to reduce: every rank runs the same full-batch update
             x_all = torch.empty(B * self.world, x.shape[1], device=self.device, dtype=torch.float32)
-            self._all_gather_rows(x_all, x)
+            self._group.all_gather_rows(x_all, x)
         losses = torch.zeros(len(self.keys), device=self.device, dtype=torch.float32)
         f = cosine_factor(self.steps, self.max_iter)
         for g in self.groups:
             N = g.H * self.C
             logits, dlogits, dl_all = self._bufs(g, B)
-            g.lr.copy_(torch.tensor([lr * f for lr in g.base_lr], dtype=torch.float64).to(torch.float32))
+            self.heads.set_lr(g, f)
             xs = x[:, g.col0:g.col0 + g.K]
             ops.probe_logits(xs, g.weight, g.bias, logits, B, N, g.K)
             ops.probe_ce(logits, y, B, g.H, self.C, 1.0 / (B * self.world), losses[g.off:g.off + g.H], None, dlogits)
             if self.world > 1:
-                self._all_gather_rows(dl_all, dlogits)
+                self._group.all_gather_rows(dl_all, dlogits)
                 dlogits = dl_all
             ops.probe_sgd(g.weight, g.bias, g.m_weight, g.m_bias, dlogits, x_all[:, g.col0:g.col0 + g.K], g.lr, B * self.world, g.H,
                           self.C, g.K, self.momentum)
@@ -254,15 +217,8 @@ class LinearProbe:
     def state_dict(self) -> Dict[str, torch.Tensor]:
         """the reference's AllClassifiers layout (classifiers_dict.<key>.linear.weight | bias); momentum buffers and the step count
         under the prefix `probe.`"""
-        sd = {}
-        for g in self.groups:
-            for i, k in enumerate(g.keys):
-                sd[f"classifiers_dict.{k}.linear.weight"] = g.weight[i].clone()
-                sd[f"classifiers_dict.{k}.linear.bias"] = g.bias[i].clone()
-        for g in self.groups:
-            for i, k in enumerate(g.keys):
-                sd[f"probe.momentum.{k}.weight"] = g.m_weight[i].clone()
-                sd[f"probe.momentum.{k}.bias"] = g.m_bias[i].clone()
+        sd = {f"classifiers_dict.{k}.linear.{p}": param.clone() for k, p, param, _ in self.heads.entries()}
+        sd.update({f"probe.momentum.{k}.{p}": mom.clone() for k, p, _, mom in self.heads.entries()})
         sd["probe.steps"] = torch.tensor(self.steps, dtype=torch.int64)
         return sd
 
@@ -274,16 +230,14 @@ class LinearProbe:
         have = {k for k in sd if k.startswith("classifiers_dict.")}
         if want != have:
             raise KeyError(f"load_state_dict: missing {sorted(want - have)}, unexpected {sorted(have - want)}")
-        for g in self.groups:
-            for i, k in enumerate(g.keys):
-                for dst, mom, p in ((g.weight, g.m_weight, "weight"), (g.bias, g.m_bias, "bias")):
-                    src = sd[f"classifiers_dict.{k}.linear.{p}"]
-                    if src.shape != dst[i].shape:
-                        raise ValueError(f"{k}.linear.{p}: shape {tuple(src.shape)}, expected {tuple(dst[i].shape)}")
-                    dst[i].copy_(src)
-                    m = sd.get(f"probe.momentum.{k}.{p}")
-                    if m is None:
-                        mom[i].zero_()
-                    else:
-                        mom[i].copy_(m)
+        for k, p, param, mom in self.heads.entries():
+            src = sd[f"classifiers_dict.{k}.linear.{p}"]
+            if src.shape != param.shape:
+                raise ValueError(f"{k}.linear.{p}: shape {tuple(src.shape)}, expected {tuple(param.shape)}")
+            param.copy_(src)
+            m = sd.get(f"probe.momentum.{k}.{p}")
+            if m is None:
+                mom.zero_()
+            else:
+                mom.copy_(m)
         self.steps = int(sd["probe.steps"]) if "probe.steps" in sd else 0

@@ -16,13 +16,13 @@ exists, no float is summed with atomics: a step repeats bit for bit.
 There is no CPU path: tensors on the CPU raise.  Training is single-process; evaluation sums its counters over a process group."""
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
 from . import ops
 from .banks import Group, Workspace, eval_device
-from .probe import cosine_factor
+from .heads import HeadGroup, HeadStore, cosine_factor
 
 Head = Tuple[str, int, float]  # (key, use_n_blocks, lr)
 SGD_WORKSPACE_BOUND = 64 << 20  # bytes of weight-gradient slices per launch; a group whose heads need more is stepped in chunks of heads
@@ -42,20 +42,11 @@ def miou_from_confusion(conf: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor,
     return miou, iou, acc
 
 
-class _Group:
-    """the heads that read the last n blocks: the trailing n D columns of X_all"""
-
-    def __init__(self, n: int):
-        self.n = n
-        self.keys: List[str] = []
-        self.base_lr: List[float] = []
-
-
 class SegProbe:
     """heads: (key, use_n_blocks, lr) tuples with unique keys; heads with equal use_n_blocks form a group and are stored stacked
-    (weight [H, C, K], bias [H, C] and their momentum buffers, contiguous fp32; normal_(0, 0.01) weights and zero biases drawn on the
-    host in creation order).  `keys` lists the heads group by group: the order of every per-head vector.  model may be None when
-    only step_features / evaluate_features are used (then pass embed_dim)."""
+    (heads.HeadStore: weight [H, C, K], bias [H, C] and their momentum buffers, contiguous fp32; normal_(0, 0.01) weights and zero
+    biases drawn on the host in creation order).  `keys` lists the heads group by group: the order of every per-head vector.  model
+    may be None when only step_features / evaluate_features are used (then pass embed_dim)."""
 
     def __init__(self, model, heads: Sequence[Head], num_classes: int, ignore_index: int = 255, momentum: float = 0.9,
                  max_iter: Optional[int] = None, group=None, *, embed_dim: Optional[int] = None, device=None):
@@ -82,25 +73,11 @@ class SegProbe:
         for key, n, _ in heads:
             if n < 1:
                 raise ValueError(f"{key}: use_n_blocks must be >= 1")
-            init[key] = torch.empty(self.C, n * self.D).normal_(mean=0.0, std=0.01)
-        self.groups: List[_Group] = []
-        for key, n, lr in heads:
-            g = next((g for g in self.groups if g.n == n), None)
-            if g is None:
-                g = _Group(n)
-                self.groups.append(g)
-            g.keys.append(key)
-            g.base_lr.append(lr)
-        self.keys: List[str] = []
-        f32 = dict(device=self.device, dtype=torch.float32)
-        for g in self.groups:
-            g.H, g.K, g.col0, g.off = len(g.keys), g.n * self.D, (self.n_max - g.n) * self.D, len(self.keys)
-            self.keys += g.keys
-            g.weight = torch.stack([init[k] for k in g.keys]).to(**f32).contiguous()
-            g.bias = torch.zeros(g.H, self.C, **f32)
-            g.m_weight, g.m_bias = torch.zeros_like(g.weight), torch.zeros_like(g.bias)
-            g.lr = torch.zeros(g.H, **f32)
+            init[key] = (torch.empty(self.C, n * self.D).normal_(mean=0.0, std=0.01), torch.zeros(self.C))
+        # a group reads the last n blocks: the trailing n D columns of X_all
+        self.heads = HeadStore([(key, n, n * self.D, (self.n_max - n) * self.D, lr) for key, n, lr in heads], init, self.device, max_iter)
         del init
+        self.groups, self.keys = self.heads.groups, self.heads.keys
         self.steps = 0
         self.head_chunk: Optional[int] = None  # heads per weight-step launch; None: as many as SGD_WORKSPACE_BOUND allows
         self._ws_ce, self._ws_sgd = Workspace(self.device), Workspace(self.device)
@@ -141,10 +118,7 @@ class SegProbe:
             y = torch.where((y < 0) | (y > 255), torch.full_like(y, 255), y).to(torch.uint8)
         return x, (h, w), y.contiguous()
 
-    def _lr(self, g: _Group, f: float) -> None:
-        g.lr.copy_(torch.tensor([lr * f for lr in g.base_lr], dtype=torch.float64).to(torch.float32))
-
-    def _head_chunk(self, g: _Group, M: int) -> int:
+    def _head_chunk(self, g: HeadGroup, M: int) -> int:
         if self.head_chunk is not None:
             return max(1, min(g.H, int(self.head_chunk)))
         per_head = ops.seg_sgd_workspace_bytes(M, self.C, g.K)
@@ -152,8 +126,7 @@ class SegProbe:
 
     # ------------------------------------------------------------------------------------------------ training
     def learning_rates(self, step: Optional[int] = None) -> Dict[str, float]:
-        f = cosine_factor(self.steps if step is None else step, self.max_iter)
-        return {k: lr * f for g in self.groups for k, lr in zip(g.keys, g.base_lr)}
+        return self.heads.learning_rates(self.steps if step is None else step)
 
     def step(self, images: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
         return self.step_features(self.features(images), self._hw(images), labels)
@@ -171,7 +144,7 @@ class SegProbe:
         f32 = dict(device=self.device, dtype=torch.float32)
         for g in self.groups:
             N = g.H * C
-            self._lr(g, f)
+            self.heads.set_lr(g, f)
             xs = x[:, g.col0:g.col0 + g.K]
             z, grad = torch.empty(M, N, **f32), torch.empty(M, N, **f32)
             lse = torch.empty(g.H, B, Hl, Wl, **f32)
@@ -242,23 +215,20 @@ class SegProbe:
 
     # ------------------------------------------------------------------------------------------------ checkpoints
     def state_dict(self) -> Dict[str, torch.Tensor]:
-        sd = {}
-        for g in self.groups:
-            for i, k in enumerate(g.keys):
-                sd[f"heads.{k}.weight"], sd[f"heads.{k}.bias"] = g.weight[i].clone(), g.bias[i].clone()
-                sd[f"momentum.{k}.weight"], sd[f"momentum.{k}.bias"] = g.m_weight[i].clone(), g.m_bias[i].clone()
-        sd["steps"] = torch.tensor(self.steps, dtype=torch.int64)
-        return sd
+        return {**{name: t.clone() for name, t in self._named()}, "steps": torch.tensor(self.steps, dtype=torch.int64)}
+
+    def _named(self):
+        """(checkpoint key, tensor view) per head: heads.<key>.weight, heads.<key>.bias, momentum.<key>.weight, momentum.<key>.bias"""
+        entries = list(self.heads.entries())
+        for (k, _, w, mw), (_, _, b, mb) in zip(entries[0::2], entries[1::2]):  # a head's weight entry, then its bias entry
+            yield from ((f"heads.{k}.weight", w), (f"heads.{k}.bias", b), (f"momentum.{k}.weight", mw), (f"momentum.{k}.bias", mb))
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
         want = {f"{p}.{k}.{q}" for k in self.keys for p in ("heads", "momentum") for q in ("weight", "bias")} | {"steps"}
         if want != set(sd):
             raise KeyError(f"load_state_dict: missing {sorted(want - set(sd))}, unexpected {sorted(set(sd) - want)}")
-        for g in self.groups:
-            for i, k in enumerate(g.keys):
-                for dst, name in ((g.weight, f"heads.{k}.weight"), (g.bias, f"heads.{k}.bias"), (g.m_weight, f"momentum.{k}.weight"),
-                                  (g.m_bias, f"momentum.{k}.bias")):
-                    if sd[name].shape != dst[i].shape:
-                        raise ValueError(f"{name}: shape {tuple(sd[name].shape)}, expected {tuple(dst[i].shape)}")
-                    dst[i].copy_(sd[name])
+        for name, dst in self._named():
+            if sd[name].shape != dst.shape:
+                raise ValueError(f"{name}: shape {tuple(sd[name].shape)}, expected {tuple(dst.shape)}")
+            dst.copy_(sd[name])
         self.steps = int(sd["steps"])
