@@ -558,6 +558,46 @@ int vtp_seg_sgd_workspace_bytes(int M, int N, int K);
 int vtp_seg_sgd(float* W, float* bias, float* mW, float* mb, const float* G, int ldg, const float* X, int ldx, const float* lr, int M,
                 int H, int C, int K, float momentum, void* workspace, long workspace_bytes, void* stream);
 
+/* ---- linear depth probe (depthprobe.hip): a linear layer on frozen patch tokens whose 2 <= C <= 1024 outputs per head are uniform
+ * bins of depth, logits upsampled bilinearly to the label map exactly as above (the same tap and blend functions), AdaBins' linear
+ * normalisation and the scale-invariant log loss of Eigen et al. -- the DINOv2 "lin." depth protocol restated from the papers
+ * (parity with their programs is unpinned).  Z f32 [M = B*h*w, H*C] as for the segmentation probe; gt f32 [B, Hl, Wl] metric depth.
+ * Bin centres e_c = min_depth + ((max_depth - min_depth) * c) / (C - 1) in fp32, 0 < min_depth < max_depth.  Per pixel p and head:
+ *   a_c = max(z_p[c], 0) + 0.1;  S_p = sum_c a_c;  dhat_p = (sum_c a_c e_c) / S_p   (both sums in ascending c, the second an fmaf chain)
+ * A pixel is valid iff gt_p > 0 && gt_p <= max_depth (NaN and inf are invalid); n = valid pixels of the call.  Over the valid pixels
+ *   g_p = logf(dhat_p) - logf(gt_p);  m1 = sum g / n;  m2 = sum g^2 / n   (fp64: one partial per workgroup, folded in workgroup order)
+ *   L = sqrt(max(m2 - lam * m1^2, 0)), 0 when n = 0.
+ * No atomics: every result repeats bit for bit.
+ *
+ * vtp_depth_pix:
+ *   dhat[h,b,y,x]   f32 [H, B, Hl, Wl], written for EVERY pixel, valid or not                      -- NULL: not written
+ *   aux             opaque per-pixel planes for vtp_depth_dlogits,
+ *                   vtp_depth_pix_workspace_bytes(..., aux_plane = 1) bytes                        -- NULL: an evaluation call
+ *   loss[h]         = (float)L                                                                     (overwritten)
+ *   stats[h]        = (n, m1, m2, L), f64 [H, 4]                                                   (overwritten)
+ *   eval_counts[h] += (valid, #{max(dhat/gt, gt/dhat) < 1.25^k}, k = 1, 2, 3), int64 [H, 4]        -- NULL (both): not kept
+ *   eval_sums[h]   += sums over the valid pixels of |dhat-gt|/gt, (dhat-gt)^2/gt, (dhat-gt)^2, formed in fp64 from the fp32 dhat,
+ *                     stored as f64 [H, 6] = (g, g^2, abs_rel, sq_rel, sq, |g| / ln 10).  Each image's sums are formed in the tile
+ *                     order of the image alone and one owner adds them to the accumulator image by image in batch order: any split
+ *                     of an image sequence into batches leaves the same bits.
+ * gt may be NULL when dhat is given (prediction: only dhat is written; loss, stats and workspace may then be NULL too).
+ * workspace: vtp_depth_pix_workspace_bytes(..., aux_plane = 0) bytes, 8-byte aligned; that function returns the bytes, or -1 (bad
+ * argument or more than 2 GiB). */
+int vtp_depth_pix_workspace_bytes(int B, int h, int w, int Hl, int Wl, int H, int C, int aux_plane);
+int vtp_depth_pix(const float* Z, int ldz, const float* gt, int B, int h, int w, int Hl, int Wl, int H, int C, float min_depth,
+                  float max_depth, float lam, float* dhat, float* aux, float* loss, double* stats, long* eval_counts, double* eval_sums,
+                  void* workspace, long workspace_bytes, void* stream);
+/* G[(b,i,j), h*C + c] = sum_p w_p(i,j) q_p [z_p[c] > 0] (e_c - dhat_p),  q_p = (g_p - lam m1) / (n L dhat_p S_p), over the valid pixels
+ * that have cell (i, j) among their four taps (row stride ldg); aux and stats as vtp_depth_pix left them, z_p[c] re-blended from the
+ * cell's 3 x 3 neighbourhood.  A gather: one writer and one raster-order sum per element; a cell without support gets exactly 0, and
+ * so does everything when n = 0 or L = 0. */
+int vtp_depth_dlogits(const float* Z, int ldz, const float* aux, const double* stats, float* G, int ldg, int B, int h, int w, int Hl,
+                      int Wl, int H, int C, float min_depth, float max_depth, float lam, void* stream);
+/* vtp_seg_sgd for 1 <= C <= 1024: the same two kernels through the same launcher, the same bits for the same operands. */
+int vtp_depth_sgd_workspace_bytes(int M, int N, int K);
+int vtp_depth_sgd(float* W, float* bias, float* mW, float* mb, const float* G, int ldg, const float* X, int ldx, const float* lr, int M,
+                  int H, int C, int K, float momentum, void* workspace, long workspace_bytes, void* stream);
+
 /* ---- zero-shot classification (zeroshot.hip; reference: tools/test_zero_shot_hf.py at precision 'fp32') ------------------
  * The tool's own arithmetic, fp32 in and out, products on the f32-input MFMA.  D % 4 == 0, leading dimensions % 4 == 0 and
  * >= D, feat / F / Wt 16-byte aligned.  The classifier is kept as Wt f32 [C, D] (one row per class); the tool's [D, C]

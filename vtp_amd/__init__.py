@@ -2,7 +2,8 @@
 
 Public surface mirrors the reference (`from vtp.models.vtp_hf import VTPConfig, VTPModel`):
     from vtp_amd import VTPConfig, VTPModel, VTPTrainer, LinearProbe, ZeroShot, Knn, ReconEval, MultiCrop, Preprocess, FID,
-    InceptionFeatures, FrechetStats, frechet_distance, PrecisionRecall, InceptionScore, GenEval, Retrieval, KID, SegProbe
+    InceptionFeatures, FrechetStats, frechet_distance, PrecisionRecall, InceptionScore, GenEval, Retrieval, KID, SegProbe,
+    DepthProbe
 Everything below the Python API is hand-written HIP in libvtp_hip.so (C ABI: include/vtp_hip.h)."""
 from .config import VTPConfig  # noqa: F401
 
@@ -32,6 +33,9 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name == "SegProbe":
         from .segprobe import SegProbe
         return SegProbe
+    if name == "DepthProbe":
+        from .depthprobe import DepthProbe
+        return DepthProbe
     if name == "ZeroShot":
         from .zeroshot import ZeroShot
         return ZeroShot

@@ -141,6 +141,15 @@ SIGNATURES = {
     "vtp_seg_sgd_workspace_bytes": [_I, _I, _I],  # M N K -> bytes, or -1
     # W bias mW mb G ldg X ldx lr M H C K momentum workspace workspace_bytes stream
     "vtp_seg_sgd": [_P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _F, _P, _L, _P],
+    # linear depth probe (depthprobe.hip)
+    "vtp_depth_pix_workspace_bytes": [_I, _I, _I, _I, _I, _I, _I, _I],  # B h w Hl Wl H C aux_plane -> bytes, or -1
+    # Z ldz gt B h w Hl Wl H C min_depth max_depth lam dhat aux loss stats eval_counts eval_sums workspace workspace_bytes stream
+    "vtp_depth_pix": [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P, _L, _P],
+    # Z ldz aux stats G ldg B h w Hl Wl H C min_depth max_depth lam stream
+    "vtp_depth_dlogits": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _F, _P],
+    "vtp_depth_sgd_workspace_bytes": [_I, _I, _I],  # M N K -> bytes, or -1
+    # W bias mW mb G ldg X ldx lr M H C K momentum workspace workspace_bytes stream
+    "vtp_depth_sgd": [_P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _F, _P, _L, _P],
     "vtp_zs_class_mean": [_P, _I, _P, _I, _I, _I, _I, _F, _P],  # feat ldf Wt ldw C T D eps stream
     # F ldf Wt ldw targets scale B C D counts per_class rank pred logits ldl stream
     "vtp_zs_topk": [_P, _I, _P, _I, _P, _F, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P],

@@ -4,84 +4,24 @@
 //   vtp_seg_ce      : per pixel and head the interpolated logits from LDS-staged cells -> lse, argmax, loss partials, confusion counts
 //   vtp_seg_dlogits : G = d loss / d Z as a GATHER: one wave per (cell, head, 64 classes) walks the pixels of the cell's support
 //   vtp_seg_sgd     : dW = G^T X on the f32-input MFMA in fixed slices of the token rows, folded in slice order into the SGD step
-// ATen's upsample_bilinear2d (align_corners=False, no antialias) per axis is seg_tap below; every kernel takes the taps and weights
-// of a pixel from that one function, and the blend from seg_blend, so the forward and the gradient agree on every pixel.
+// ATen's upsample_bilinear2d (align_corners=False, no antialias) per axis is seg_tap (seg_bilinear.h, shared with depthprobe.hip); every
+// kernel takes the taps and weights of a pixel from that one function, and the blend from seg_blend, so the forward and the gradient
+// agree on every pixel.  The weight step's launcher, seg_sgd_launch, also serves vtp_depth_sgd: its two kernels exist once, here.
 // No float atomics anywhere: every float has one writer and one summation order; the confusion counts are integer atomics.
 #include "common.h"
+#include "seg_bilinear.h"
 #include "vtp_hip.h"
 #include "wave_f32.h"
 
-#include <limits.h>
-
 namespace vtp {
 
-constexpr int SEG_THREADS = 256;
-constexpr int SEG_CELL_FLOATS = 10240;  // LDS floats for the staged cells of one head (40 KB)
-constexpr int SEG_HASH = 2048;          // slots of the workgroup's (target, prediction) table: twice the pixels of the largest tile
-constexpr int SEG_TILE = 32;            // label pixels per tile edge where the footprint allows it
-constexpr int SEG_SLICE = 512;          // token rows per weight-gradient slice: a constant, never derived from the device
-constexpr int SEG_MAX_EDGE = 32768;     // h, w, Hl, Wl: keeps the integer inverse map and B Hl Wl checks simple
-
-struct SegTap {
-  int i0, i1;
-  float l0, l1;
-};
-
-// taps and weights of output index dst on an axis resampled from `in` to `out` entries.  No contraction: the host plans the LDS
-// footprint with the same function and has to get the same integers.
-__host__ __device__ inline SegTap seg_tap(int dst, int in, int out) {
-#pragma clang fp contract(off)
-  const float scale = (float)in / (float)out;
-  float src = scale * ((float)dst + 0.5f) - 0.5f;
-  src = src < 0.f ? 0.f : src;
-  SegTap t;
-  t.i0 = (int)src;
-  if (t.i0 > in - 1) t.i0 = in - 1;  // cannot happen for dst < out; keeps every index inside the map whatever the rounding
-  t.i1 = t.i0 + (t.i0 < in - 1 ? 1 : 0);
-  t.l1 = src - (float)t.i0;
-  t.l0 = 1.f - t.l1;
-  return t;
-}
-
-// 7 roundings, the same in every kernel
-__device__ __forceinline__ float seg_blend(float v00, float v01, float v10, float v11, const SegTap& ty, const SegTap& tx) {
-#pragma clang fp contract(off)
-  return ty.l0 * (tx.l0 * v00 + tx.l1 * v01) + ty.l1 * (tx.l0 * v10 + tx.l1 * v11);
-}
+constexpr int SEG_HASH = 2048;   // slots of the workgroup's (target, prediction) table: twice the pixels of the largest tile
+constexpr int SEG_SLICE = 512;   // token rows per weight-gradient slice: a constant, never derived from the device
 
 __device__ __forceinline__ bool seg_valid(int lab, int C, int ignore) { return lab != ignore && lab < C; }
 
 // ---------------------------------------------------------------------------------------------------------------- pixel pass
-// The tiling of the label map: tiles of th x tw pixels whose cell footprint (fy x fx cells of C | 1 floats) fits the LDS budget.
-struct SegPlan {
-  int th, tw, tiles_y, tiles_x;
-};
-
-static int seg_footprint(int tile, int in, int out) {
-  int worst = 1;
-  for (int p0 = 0; p0 < out; p0 += tile) {
-    const int p1 = (p0 + tile < out ? p0 + tile : out) - 1;
-    const int n = seg_tap(p1, in, out).i1 - seg_tap(p0, in, out).i0 + 1;
-    worst = n > worst ? n : worst;
-  }
-  return worst;
-}
-
-static SegPlan seg_plan(int h, int w, int Hl, int Wl, int C) {
-  SegPlan p;
-  p.th = p.tw = SEG_TILE;
-  const int Cs = C | 1;
-  for (;;) {
-    const int fy = seg_footprint(p.th, h, Hl), fx = seg_footprint(p.tw, w, Wl);
-    if ((long)fy * fx * Cs <= SEG_CELL_FLOATS || (p.th == 1 && p.tw == 1)) break;  // 1 x 1 pixel: at most 2 x 2 cells of 255 floats
-    if ((fy >= fx && p.th > 1) || p.tw == 1) p.th /= 2;
-    else p.tw /= 2;
-  }
-  p.tiles_y = cdiv(Hl, p.th);
-  p.tiles_x = cdiv(Wl, p.tw);
-  return p;
-}
-
+// (the tiling of the label map, seg_plan, is seg_bilinear.h's)
 __device__ __forceinline__ int block_sum_int(int v, int* red) {
   v = wave_sum_int(v);
   __syncthreads();
@@ -201,8 +141,6 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_ce_fold_kernel(const float* _
 }
 
 // ---------------------------------------------------------------------------------------------------------------- cell pass
-__device__ __forceinline__ float seg_pick(float a, float b, float c, int k) { return k == 0 ? a : (k == 1 ? b : c); }
-
 // One wave per (cell, head, chunk of 64 classes), lane = class.  A pixel that has the cell among its taps has its other taps in
 // the cell's 3 x 3 neighbourhood, whatever the scale: the nine logits of the lane's class sit in registers and the walk over the
 // candidate pixels (raster order, wave-uniform) reads only the label and lse of each pixel.
@@ -318,13 +256,36 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_sgd_fold_kernel(float* __rest
   }
 }
 
-static bool seg_shape_ok(int B, int h, int w, int Hl, int Wl) {
-  return B >= 1 && B <= 65535 && h >= 1 && w >= 1 && h <= SEG_MAX_EDGE && w <= SEG_MAX_EDGE && Hl <= SEG_MAX_EDGE && Wl <= SEG_MAX_EDGE &&
-         (long)B * h * w <= INT_MAX && (long)B * Hl * Wl <= INT_MAX;
-}
-
 static long seg_ce_bytes(const SegPlan& p, int B, int H) { return ((long)H + 2) * p.tiles_y * p.tiles_x * B * 4; }
 static long seg_sgd_bytes(int M, int N, int K) { return (long)cdiv(M, SEG_SLICE) * N * ((long)K + 1) * 4; }
+
+int seg_sgd_workspace(const char* who, int M, int N, int K) {
+  VTP_REQUIRE(M >= 1 && N >= 1 && K >= 4 && K % 4 == 0, "%s: bad shape (M, N >= 1, K %% 4 == 0)", who);
+  const long n = seg_sgd_bytes(M, N, K);
+  VTP_REQUIRE(n <= INT_MAX, "%s: more than 2 GiB (pass fewer heads per call)", who);
+  return (int)n;
+}
+
+int seg_sgd_launch(const char* who, float* W, float* bias, float* mW, float* mb, const float* G, int ldg, const float* X, int ldx,
+                   const float* lr, int M, int H, int C, int K, float momentum, void* workspace, long workspace_bytes, void* stream) {
+  VTP_REQUIRE(W && bias && mW && mb && G && X && lr && workspace, "%s: null pointer", who);
+  VTP_REQUIRE(M >= 1 && H >= 1 && C >= 1 && (long)H * C <= INT_MAX && K >= 4 && K % 4 == 0, "%s: bad shape (M, H, C >= 1, K %% 4 == 0)", who);
+  VTP_REQUIRE(ldx >= K && ldx % 4 == 0 && ldg >= (long)H * C, "%s: bad leading dimension (ldx >= K, ldx %% 4 == 0, ldg >= H * C)", who);
+  VTP_REQUIRE(aligned16(X) && aligned16(W) && aligned16(mW) && aligned16(workspace),
+              "%s: X, W, mW and workspace must be 16-byte aligned", who);
+  const int N = H * C, S = cdiv(M, SEG_SLICE);
+  VTP_REQUIRE(workspace_bytes >= seg_sgd_bytes(M, N, K), "%s: workspace too small (%s_workspace_bytes)", who, who);
+  const int k_tiles = cdiv(K, 64), n_tiles = cdiv(N, 64);
+  const long tasks = (long)k_tiles * n_tiles * S, nk4 = (long)N * K / 4;
+  VTP_REQUIRE((tasks + 3) / 4 <= INT_MAX && (nk4 + N) / SEG_THREADS < INT_MAX, "%s: too many tiles", who);
+  float* wsW = (float*)workspace;
+  float* wsb = wsW + (long)S * N * K;
+  hipLaunchKernelGGL(seg_wgrad_kernel, dim3(cdiv(tasks, 4)), dim3(SEG_THREADS), 0, (hipStream_t)stream, G, ldg, X, ldx, M, N, K, k_tiles,
+                     n_tiles, tasks, wsW, wsb);
+  hipLaunchKernelGGL(seg_sgd_fold_kernel, dim3(cdiv(nk4 + N, SEG_THREADS)), dim3(SEG_THREADS), 0, (hipStream_t)stream, W, bias, mW, mb, wsW,
+                     wsb, lr, S, N, C, K, momentum);
+  return check_launch(who + 4);  // without the "vtp_"
+}
 
 }  // namespace vtp
 
@@ -379,31 +340,12 @@ extern "C" int vtp_seg_dlogits(const float* Z, int ldz, const unsigned char* lab
 extern "C" int vtp_seg_sgd_slice(void) { return SEG_SLICE; }
 
 extern "C" int vtp_seg_sgd_workspace_bytes(int M, int N, int K) {
-  VTP_REQUIRE(M >= 1 && N >= 1 && K >= 4 && K % 4 == 0, "vtp_seg_sgd_workspace_bytes: bad shape (M, N >= 1, K %% 4 == 0)");
-  const long n = seg_sgd_bytes(M, N, K);
-  VTP_REQUIRE(n <= INT_MAX, "vtp_seg_sgd_workspace_bytes: more than 2 GiB (pass fewer heads per call)");
-  return (int)n;
+  return seg_sgd_workspace("vtp_seg_sgd_workspace_bytes", M, N, K);
 }
 
 extern "C" int vtp_seg_sgd(float* W, float* bias, float* mW, float* mb, const float* G, int ldg, const float* X, int ldx, const float* lr,
                            int M, int H, int C, int K, float momentum, void* workspace, long workspace_bytes, void* stream) {
   VTP_REQUIRE(W && bias && mW && mb && G && X && lr && workspace, "vtp_seg_sgd: null pointer");
   VTP_REQUIRE(C >= 1 && C <= 255, "vtp_seg_sgd: bad shape (1 <= C <= 255)");
-  VTP_REQUIRE(M >= 1 && H >= 1 && (long)H * C <= INT_MAX && K >= 4 && K % 4 == 0, "vtp_seg_sgd: bad shape (M, H >= 1, K %% 4 == 0)");
-  VTP_REQUIRE(ldx >= K && ldx % 4 == 0 && ldg >= (long)H * C,
-              "vtp_seg_sgd: bad leading dimension (ldx >= K, ldx %% 4 == 0, ldg >= H * C)");
-  VTP_REQUIRE(aligned16(X) && aligned16(W) && aligned16(mW) && aligned16(workspace),
-              "vtp_seg_sgd: X, W, mW and workspace must be 16-byte aligned");
-  const int N = H * C, S = cdiv(M, SEG_SLICE);
-  VTP_REQUIRE(workspace_bytes >= seg_sgd_bytes(M, N, K), "vtp_seg_sgd: workspace too small (vtp_seg_sgd_workspace_bytes)");
-  const int k_tiles = cdiv(K, 64), n_tiles = cdiv(N, 64);
-  const long tasks = (long)k_tiles * n_tiles * S, nk4 = (long)N * K / 4;
-  VTP_REQUIRE((tasks + 3) / 4 <= INT_MAX && (nk4 + N) / SEG_THREADS < INT_MAX, "vtp_seg_sgd: too many tiles");
-  float* wsW = (float*)workspace;
-  float* wsb = wsW + (long)S * N * K;
-  hipLaunchKernelGGL(seg_wgrad_kernel, dim3(cdiv(tasks, 4)), dim3(SEG_THREADS), 0, (hipStream_t)stream, G, ldg, X, ldx, M, N, K, k_tiles,
-                     n_tiles, tasks, wsW, wsb);
-  hipLaunchKernelGGL(seg_sgd_fold_kernel, dim3(cdiv(nk4 + N, SEG_THREADS)), dim3(SEG_THREADS), 0, (hipStream_t)stream, W, bias, mW, mb, wsW,
-                     wsb, lr, S, N, C, K, momentum);
-  return check_launch("seg_sgd");
+  return seg_sgd_launch("vtp_seg_sgd", W, bias, mW, mb, G, ldg, X, ldx, lr, M, H, C, K, momentum, workspace, workspace_bytes, stream);
 }

@@ -676,6 +676,78 @@ def seg_sgd(w, bias, mw, mb, g, x, lr, M, H, C, K, momentum, workspace):
                                    _p(workspace), workspace.numel(), _s()), "vtp_seg_sgd")
 
 
+def depth_pix_workspace_bytes(B, h, w, Hl, Wl, H, C, aux=False):
+    """bytes of workspace depth_pix needs, or with aux=True bytes of its aux plane; ValueError for refused arguments or above 2 GiB"""
+    return _size_or_raise(_lib_().vtp_depth_pix_workspace_bytes, B, h, w, Hl, Wl, H, C, int(bool(aux)))
+
+
+def depth_pix(z, gt, hw, H, C, min_depth, max_depth, lam, *, out_hw=None, dhat=None, aux=None, loss=None, stats=None, workspace=None,
+              eval_counts=None, eval_sums=None):
+    """pixel pass of the depth probe: z f32 [B*h*w, >= H*C] low-resolution logits (probe_logits), gt f32 [B, Hl, Wl] -> loss f32 [H]
+    and stats f64 [H, 4] = (n, m1, m2, L) (overwritten); optional dhat f32 [H, B, Hl, Wl] (every pixel), aux u8 [depth_pix_workspace_bytes(
+    ..., aux=True)] (training), eval_counts int64 [H, 4] and eval_sums f64 [H, 6] (accumulated).  gt=None with out_hw=(Hl, Wl): only
+    dhat is written (prediction)"""
+    h, w = hw
+    if gt is None:
+        _need(dhat, "dhat", torch.float32, dims=4)
+        B, (Hl, Wl) = dhat.shape[1], out_hw
+    else:
+        _need(gt, "gt", torch.float32, dims=3)
+        B, Hl, Wl = gt.shape
+    if dhat is not None:
+        _need(dhat, "dhat", torch.float32, (H, B, Hl, Wl))
+    if gt is not None:
+        _need(loss, "loss", torch.float32, (H,))
+        _need(stats, "stats", torch.float64, (H, 4))
+        _need(workspace, "workspace", torch.uint8, dims=1)
+    if aux is not None:
+        _need(aux, "aux", torch.uint8, dims=1)
+        if aux.numel() < depth_pix_workspace_bytes(B, h, w, Hl, Wl, H, C, aux=True) or aux.data_ptr() % 4:
+            raise ValueError("aux is smaller than depth_pix_workspace_bytes(..., aux=True) or not 4-byte aligned")
+    if eval_counts is not None:
+        _need(eval_counts, "eval_counts", torch.int64, (H, 4))
+    if eval_sums is not None:
+        _need(eval_sums, "eval_sums", torch.float64, (H, 6))
+    _need_f32(z=z)
+    _need_gpu(gt=gt, dhat=dhat, aux=aux, loss=loss, stats=stats, workspace=workspace, eval_counts=eval_counts, eval_sums=eval_sums)
+    if z.dim() != 2 or z.shape[0] != B * h * w or z.stride(1) != 1:
+        raise ValueError(f"z must be [{B * h * w}, >= {H * C}] with unit column stride, got {tuple(z.shape)}")
+    _lib.check(_lib_().vtp_depth_pix(_p(z), z.stride(0), _p(gt), B, h, w, Hl, Wl, H, C, min_depth, max_depth, lam, _p(dhat), _p(aux),
+                                     _p(loss), _p(stats), _p(eval_counts), _p(eval_sums), _p(workspace),
+                                     0 if workspace is None else workspace.numel(), _s()), "vtp_depth_pix")
+
+
+def depth_dlogits(z, label_hw, hw, H, C, min_depth, max_depth, lam, aux, stats, g):
+    """cell pass: g f32 [B*h*w, >= H*C] = d L / d z, gathered per cell from aux and stats of depth_pix; label_hw = (B, Hl, Wl)"""
+    h, w = hw
+    B, Hl, Wl = label_hw
+    _need(aux, "aux", torch.uint8, dims=1)
+    _need(stats, "stats", torch.float64, (H, 4))
+    if aux.numel() < depth_pix_workspace_bytes(B, h, w, Hl, Wl, H, C, aux=True) or aux.data_ptr() % 4:
+        raise ValueError("aux is smaller than depth_pix_workspace_bytes(..., aux=True) or not 4-byte aligned")
+    _need_f32(z=z, g=g)
+    _need_gpu(aux=aux, stats=stats)
+    for name, t in (("z", z), ("g", g)):
+        if t.dim() != 2 or t.shape[0] != B * h * w or t.stride(1) != 1:
+            raise ValueError(f"{name} must be [{B * h * w}, >= {H * C}] with unit column stride, got {tuple(t.shape)}")
+    _lib.check(_lib_().vtp_depth_dlogits(_p(z), z.stride(0), _p(aux), _p(stats), _p(g), g.stride(0), B, h, w, Hl, Wl, H, C, min_depth,
+                                         max_depth, lam, _s()), "vtp_depth_dlogits")
+
+
+def depth_sgd_workspace_bytes(M, N, K):
+    """bytes of workspace depth_sgd needs for M token rows and N = H * C outputs; ValueError for refused arguments or above 2 GiB"""
+    return _size_or_raise(_lib_().vtp_depth_sgd_workspace_bytes, M, N, K)
+
+
+def depth_sgd(w, bias, mw, mb, g, x, lr, M, H, C, K, momentum, workspace):
+    """seg_sgd for up to 1024 outputs per head: the same kernels, the same bits"""
+    _need(workspace, "workspace", torch.uint8, dims=1)
+    _need_f32(w=w, bias=bias, mw=mw, mb=mb, g=g, x=x, lr=lr)
+    _need_gpu(workspace=workspace)
+    _lib.check(_lib_().vtp_depth_sgd(_p(w), _p(bias), _p(mw), _p(mb), _p(g), g.stride(0), _p(x), x.stride(0), _p(lr), M, H, C, K,
+                                     momentum, _p(workspace), workspace.numel(), _s()), "vtp_depth_sgd")
+
+
 def zs_class_mean(feat, wt, C, T, D, eps=1e-12):
     """wt[c] f32 [C, D] = F.normalize(mean over t of feat[c * T + t]) (feat f32 [C * T, D], template t of class c in row c * T + t);
     feat and wt may be row / column slices of wider matrices (row strides taken from the tensors)"""
