@@ -126,7 +126,8 @@ CASES = [(1, 1, 1, 5, 7, 2, 40),         # every tap clamps, two bins
          (2, 5, 4, 3, 2, 256, 40),       # downsampling
          (1, 4, 4, 4, 4, 256, 132),      # scale 1: the identity
          (2, 3, 5, 48, 80, 256, 132),    # the largest case
-         (1, 7, 6, 2, 2, 5, 40)]         # strong downsampling: cells with empty support
+         (1, 7, 6, 2, 2, 5, 40),         # strong downsampling: cells with empty support
+         (1, 8, 8, 8, 8, 256, 40)]       # 8 x 8 x 257 floats of cells do not fit the LDS budget: seg_plan ends at 4 x 4-pixel tiles, 2 x 2
 VARIANTS = (None, "all_invalid", "nan", "inf", "far")
 
 

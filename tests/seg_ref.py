@@ -150,7 +150,8 @@ CASES = [(1, 1, 1, 5, 7, 2, 40),         # every tap clamps
          (2, 5, 4, 3, 2, 21, 40),        # downsampling
          (1, 4, 4, 4, 4, 150, 132),      # scale 1: the identity
          (2, 3, 5, 48, 80, 150, 260),
-         (1, 7, 6, 2, 2, 5, 40)]         # strong downsampling: cells with empty support
+         (1, 7, 6, 2, 2, 5, 40),         # strong downsampling: cells with empty support
+         (1, 9, 9, 9, 9, 150, 40)]       # 9 x 9 x 151 floats of cells do not fit the LDS budget: seg_plan shrinks th to 4 (tw stays 32), 3 x 1 tiles
 
 
 def make_case(i, H, all_ignored=False):

@@ -37,14 +37,6 @@ __device__ __forceinline__ double block_sum_f64(double v, double* red) {
   return ((red[0] + red[1]) + red[2]) + red[3];
 }
 
-__device__ __forceinline__ int block_sum_i32(int v, int* red) {
-  v = wave_sum_int(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-
 // ---------------------------------------------------------------------------------------------------------------- pixel pass
 // grid (tiles, B), workgroup blk = b * tiles + tile.  part_sum f64 [H, DEPTH_SUMS, nblocks], part_cnt i32 [H, DEPTH_CNTS, nblocks] and
 // part_n i32 [nblocks] get one entry per workgroup; without `eval` only the first two sums are written (and read by the fold).
@@ -59,13 +51,8 @@ __global__ __launch_bounds__(SEG_THREADS) void depth_pix_kernel(const float* __r
   __shared__ int redi[4];
   const int tid = threadIdx.x, b = blockIdx.y, B = gridDim.y, tile = blockIdx.x;
   const long nblocks = (long)gridDim.x * gridDim.y, blk = (long)b * gridDim.x + tile;
-  const int y0 = (tile / tiles_x) * th, x0 = (tile % tiles_x) * tw;
-  const int y1 = min(y0 + th, Hl) - 1, x1 = min(x0 + tw, Wl) - 1;
-  const int fy0 = seg_tap(y0, h, Hl).i0, fx0 = seg_tap(x0, w, Wl).i0;
-  const int ncy = seg_tap(y1, h, Hl).i1 - fy0 + 1, ncx = seg_tap(x1, w, Wl).i1 - fx0 + 1;
-  const int Cs = C | 1;  // odd row length: the cells of neighbouring pixels land on different LDS banks
-  const int ncell = min(ncy * ncx, SEG_CELL_FLOATS / Cs);  // the host planned the tile so that the footprint fits
-  const int npix = th * tw;
+  const SegTile geo(tile, tiles_x, th, tw, h, w, Hl, Wl, C);
+  const int y0 = geo.y0, x0 = geo.x0, y1 = geo.y1, x1 = geo.x1, npix = th * tw;
   const long plane = (long)Hl * Wl;
   const float* gt_b = gt ? gt + b * plane : nullptr;
   const double inv_ln10 = 0.43429448190325182765;
@@ -78,17 +65,13 @@ __global__ __launch_bounds__(SEG_THREADS) void depth_pix_kernel(const float* __r
       if (py > y1 || px > x1) continue;
       nv += depth_valid(gt_b[(long)py * Wl + px], hi) ? 1 : 0;
     }
-    nv = block_sum_i32(nv, redi);
+    nv = block_sum_int(nv, redi);
     if (tid == 0) part_n[blk] = nv;
   }
 
   for (int hh = 0; hh < H; ++hh) {
     __syncthreads();
-    for (int i = tid; i < ncell * C; i += SEG_THREADS) {
-      const int cell = i / C, c = i - cell * C;
-      const long row = ((long)b * h + fy0 + cell / ncx) * w + fx0 + cell % ncx;
-      cells[cell * Cs + c] = Z[row * ldz + (long)hh * C + c];
-    }
+    geo.stage(cells, Z, ldz, b, hh, h, w, C);
     __syncthreads();
     double s[DEPTH_SUMS] = {0., 0., 0., 0., 0., 0.};
     int k[DEPTH_CNTS] = {0, 0, 0};
@@ -103,13 +86,10 @@ __global__ __launch_bounds__(SEG_THREADS) void depth_pix_kernel(const float* __r
         for (int a = 0; a < DEPTH_AUX; ++a) aux[(long)a * H * B * plane + at] = 0.f;
       if (!ok && !dhat) continue;
       const SegTap ty = seg_tap(py, h, Hl), tx = seg_tap(px, w, Wl);
-      const float* c00 = cells + ((ty.i0 - fy0) * ncx + (tx.i0 - fx0)) * Cs;
-      const float* c01 = cells + ((ty.i0 - fy0) * ncx + (tx.i1 - fx0)) * Cs;
-      const float* c10 = cells + ((ty.i1 - fy0) * ncx + (tx.i0 - fx0)) * Cs;
-      const float* c11 = cells + ((ty.i1 - fy0) * ncx + (tx.i1 - fx0)) * Cs;
+      const SegCorners q = geo.corners(cells, ty, tx);
       float S = 0.f, T = 0.f;
       for (int c = 0; c < C; ++c) {
-        const float v = seg_blend(c00[c], c01[c], c10[c], c11[c], ty, tx);
+        const float v = seg_blend(q.c00[c], q.c01[c], q.c10[c], q.c11[c], ty, tx);
         const float a = (v > 0.f ? v : 0.f) + 0.1f;
         S += a;
         T = fmaf(a, bins[c], T);
@@ -144,7 +124,7 @@ __global__ __launch_bounds__(SEG_THREADS) void depth_pix_kernel(const float* __r
     }
     if (eval)
       for (int q = 0; q < DEPTH_CNTS; ++q) {
-        const int v = block_sum_i32(k[q], redi);
+        const int v = block_sum_int(k[q], redi);
         if (tid == 0) part_cnt[((long)hh * DEPTH_CNTS + q) * nblocks + blk] = v;
       }
   }
@@ -191,68 +171,41 @@ __global__ __launch_bounds__(SEG_THREADS) void depth_fold_kernel(const double* _
 }
 
 // ---------------------------------------------------------------------------------------------------------------- cell pass
-// One wave per (cell, head, chunk of 64 bins), lane = bin: seg_dlogits_kernel's walk.  The nine logits of the lane's bin sit in
-// registers; the walk over the candidate pixels (raster order, wave-uniform) reads only the three aux numbers of each pixel.
+// seg_cell_walk (seg_bilinear.h) with one wave per (cell, head, chunk of 64 bins), lane = bin: the walk reads only the three aux
+// numbers of each pixel.
 //   q_p = ((g_p - fl(lam m1)) * r_p) * fl(1 / (n L)),  G += (wy wx) * [z_p[c] > 0] * (q_p * (e_c - dhat_p))
 __global__ __launch_bounds__(SEG_THREADS) void depth_dlogits_kernel(const float* __restrict__ Z, int ldz, const float* __restrict__ aux,
                                                                    const double* __restrict__ stats, float* __restrict__ G, int ldg, int B,
                                                                    int h, int w, int Hl, int Wl, int H, int C, float lo, float hi, float lam,
                                                                    int chunks, long tasks) {
-  const int lane = threadIdx.x & 63;
-  const long task = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const long task = seg_cell_task();
   if (task >= tasks) return;
-  const int cc = (int)(task % chunks);
-  const long t2 = task / chunks;
-  const int hh = (int)(t2 % H);
-  const long cell = t2 / H;
-  const int hw = h * w, b = (int)(cell / hw), iy = (int)(cell % hw) / w, ix = (int)(cell % w);
-  const int c = cc * 64 + lane, cl = c < C ? c : C - 1;
+  const SegCell t(task, h, w, H, C, chunks);
+  const int c = t.c, hh = t.hh;
   const double n = stats[4 * hh], m1 = stats[4 * hh + 1], L = stats[4 * hh + 3];
   if (!(n > 0. && L > 0.)) {  // wave-uniform
-    if (c < C) G[cell * ldg + (long)hh * C + c] = 0.f;
+    if (c < C) G[t.cell * ldg + (long)hh * C + c] = 0.f;
     return;
   }
   const float lm1 = (float)((double)lam * m1), inv_nl = (float)(1. / (n * L));
-  const float e = depth_bin(cl, C, lo, hi);
-  float nb[3][3];
-#pragma unroll
-  for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-    for (int dx = 0; dx < 3; ++dx) {
-      const int yy = min(max(iy + dy - 1, 0), h - 1), xx = min(max(ix + dx - 1, 0), w - 1);  // a clamped neighbour is never a tap
-      nb[dy][dx] = Z[((long)b * hw + (long)yy * w + xx) * ldz + (long)hh * C + cl];
-    }
-  // candidate pixels from the inverse map in integers, as in seg_dlogits_kernel; membership and weight are the tap function's
-  const int ylo = (int)max(0L, (2L * iy - 1) * Hl / (2L * h) - 2), yhi = (int)min((long)Hl - 1, ((2L * iy + 3) * Hl + 2L * h - 1) / (2L * h) + 1);
-  const int xlo = (int)max(0L, (2L * ix - 1) * Wl / (2L * w) - 2), xhi = (int)min((long)Wl - 1, ((2L * ix + 3) * Wl + 2L * w - 1) / (2L * w) + 1);
+  const float e = depth_bin(t.cl, C, lo, hi);
   const long plane = (long)Hl * Wl, planes = (long)H * B * plane;
-  const float* aux_d = aux + ((long)hh * B + b) * plane;
+  const float* aux_d = aux + ((long)hh * B + t.b) * plane;
   const float* aux_g = aux_d + planes;
   const float* aux_r = aux_g + planes;
-  float acc = 0.f;
-  for (int py = ylo; py <= yhi; ++py) {
-    const SegTap ty = seg_tap(py, h, Hl);
-    if (ty.i0 != iy && ty.i1 != iy) continue;
-    const float wy = (ty.i0 == iy ? ty.l0 : 0.f) + (ty.i1 == iy ? ty.l1 : 0.f);
-    const int ka = ty.i0 - iy + 1, kb = ty.i1 - iy + 1;
-    float ra[3], rb[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) ra[j] = seg_pick(nb[0][j], nb[1][j], nb[2][j], ka), rb[j] = seg_pick(nb[0][j], nb[1][j], nb[2][j], kb);
-    for (int px = xlo; px <= xhi; ++px) {
-      const SegTap tx = seg_tap(px, w, Wl);
-      if (tx.i0 != ix && tx.i1 != ix) continue;
-      const float r = aux_r[(long)py * Wl + px];
-      if (r == 0.f) continue;  // an invalid pixel
-      const float wx = (tx.i0 == ix ? tx.l0 : 0.f) + (tx.i1 == ix ? tx.l1 : 0.f);
-      const int ja = tx.i0 - ix + 1, jb = tx.i1 - ix + 1;
-      const float z = seg_blend(seg_pick(ra[0], ra[1], ra[2], ja), seg_pick(ra[0], ra[1], ra[2], jb), seg_pick(rb[0], rb[1], rb[2], ja),
-                                seg_pick(rb[0], rb[1], rb[2], jb), ty, tx);
-      const float q = ((aux_g[(long)py * Wl + px] - lm1) * r) * inv_nl;
-      const float t = q * (e - aux_d[(long)py * Wl + px]);
-      acc = fmaf(wy * wx, z > 0.f ? t : 0.f, acc);
-    }
-  }
-  if (c < C) G[cell * ldg + (long)hh * C + c] = acc;
+  float r;
+  const float acc = seg_cell_walk(
+      t, Z, ldz, h, w, Hl, Wl, C,
+      [&](int py, int px) {
+        r = aux_r[(long)py * Wl + px];
+        return r != 0.f;  // 0 marks an invalid pixel
+      },
+      [&](int py, int px, float z) {
+        const float q = ((aux_g[(long)py * Wl + px] - lm1) * r) * inv_nl;
+        const float d = q * (e - aux_d[(long)py * Wl + px]);
+        return z > 0.f ? d : 0.f;
+      });
+  if (c < C) G[t.cell * ldg + (long)hh * C + c] = acc;
 }
 
 static long depth_pix_bytes(const SegPlan& p, int B, int H) {
@@ -266,9 +219,8 @@ static bool depth_range_ok(float lo, float hi) { return lo > 0.f && lo < hi && h
 using namespace vtp;
 
 extern "C" int vtp_depth_pix_workspace_bytes(int B, int h, int w, int Hl, int Wl, int H, int C, int aux_plane) {
-  VTP_REQUIRE(Hl >= 1 && Wl >= 1, "vtp_depth_pix_workspace_bytes: bad label size (Hl, Wl >= 1)");
-  VTP_REQUIRE(C >= 2 && C <= DEPTH_MAX_BINS && H >= 1, "vtp_depth_pix_workspace_bytes: bad shape (H >= 1, 2 <= C <= 1024)");
-  VTP_REQUIRE(seg_shape_ok(B, h, w, Hl, Wl), "vtp_depth_pix_workspace_bytes: bad shape (B, h, w >= 1; edges <= 32768; B Hl Wl < 2^31)");
+  if (seg_check("vtp_depth_pix_workspace_bytes", B, h, w, Hl, Wl, H, C, 2, DEPTH_MAX_BINS, 0, nullptr, 0, nullptr, nullptr))
+    return VTP_ERR_ARG;
   const long n = aux_plane ? (long)DEPTH_AUX * H * B * Hl * Wl * 4 : depth_pix_bytes(seg_plan(h, w, Hl, Wl, C), B, H);
   VTP_REQUIRE(n <= INT_MAX, "vtp_depth_pix_workspace_bytes: more than 2 GiB (pass fewer heads per call)");
   return (int)n;
@@ -281,14 +233,10 @@ extern "C" int vtp_depth_pix(const float* Z, int ldz, const float* gt, int B, in
   VTP_REQUIRE(!gt || (loss && stats && workspace), "vtp_depth_pix: null pointer (labels need loss, stats and a workspace)");
   VTP_REQUIRE(gt || (!aux && !eval_counts && !eval_sums), "vtp_depth_pix: aux and the evaluation counters need labels");
   VTP_REQUIRE(!eval_counts == !eval_sums, "vtp_depth_pix: eval_counts and eval_sums go together");
-  VTP_REQUIRE(Hl >= 1 && Wl >= 1, "vtp_depth_pix: bad label size (Hl, Wl >= 1)");
-  VTP_REQUIRE(C >= 2 && C <= DEPTH_MAX_BINS && H >= 1 && (long)H * C <= INT_MAX, "vtp_depth_pix: bad shape (H >= 1, 2 <= C <= 1024)");
-  VTP_REQUIRE(seg_shape_ok(B, h, w, Hl, Wl), "vtp_depth_pix: bad shape (B, h, w >= 1; edges <= 32768; B Hl Wl < 2^31)");
-  VTP_REQUIRE(ldz >= (long)H * C, "vtp_depth_pix: bad leading dimension (ldz >= H * C)");
+  SegPlan p;
+  if (seg_check("vtp_depth_pix", B, h, w, Hl, Wl, H, C, 2, DEPTH_MAX_BINS, C, "ldz", ldz, &p, nullptr)) return VTP_ERR_ARG;
   VTP_REQUIRE(depth_range_ok(min_depth, max_depth), "vtp_depth_pix: bad depth range (0 < min_depth < max_depth)");
-  const SegPlan p = seg_plan(h, w, Hl, Wl, C);
   const long tiles = (long)p.tiles_y * p.tiles_x, nblocks = tiles * B;
-  VTP_REQUIRE(nblocks <= INT_MAX / 4, "vtp_depth_pix: too many tiles");
   VTP_REQUIRE(!gt || (workspace_bytes >= depth_pix_bytes(p, B, H) && ((uintptr_t)workspace & 7) == 0),
               "vtp_depth_pix: workspace too small (vtp_depth_pix_workspace_bytes) or not 8-byte aligned");
   double* part_sum = (double*)workspace;
@@ -305,14 +253,11 @@ extern "C" int vtp_depth_pix(const float* Z, int ldz, const float* gt, int B, in
 extern "C" int vtp_depth_dlogits(const float* Z, int ldz, const float* aux, const double* stats, float* G, int ldg, int B, int h, int w,
                                  int Hl, int Wl, int H, int C, float min_depth, float max_depth, float lam, void* stream) {
   VTP_REQUIRE(Z && aux && stats && G, "vtp_depth_dlogits: null pointer");
-  VTP_REQUIRE(Hl >= 1 && Wl >= 1, "vtp_depth_dlogits: bad label size (Hl, Wl >= 1)");
-  VTP_REQUIRE(C >= 2 && C <= DEPTH_MAX_BINS && H >= 1 && (long)H * C <= INT_MAX, "vtp_depth_dlogits: bad shape (H >= 1, 2 <= C <= 1024)");
-  VTP_REQUIRE(seg_shape_ok(B, h, w, Hl, Wl), "vtp_depth_dlogits: bad shape (B, h, w >= 1; edges <= 32768; B Hl Wl < 2^31)");
-  VTP_REQUIRE(ldz >= (long)H * C && ldg >= (long)H * C, "vtp_depth_dlogits: bad leading dimension (ldz, ldg >= H * C)");
+  long tasks;
+  if (seg_check("vtp_depth_dlogits", B, h, w, Hl, Wl, H, C, 2, DEPTH_MAX_BINS, C, "ldz, ldg", min(ldz, ldg), nullptr, &tasks))
+    return VTP_ERR_ARG;
   VTP_REQUIRE(depth_range_ok(min_depth, max_depth), "vtp_depth_dlogits: bad depth range (0 < min_depth < max_depth)");
   const int chunks = cdiv(C, 64);
-  const long tasks = (long)B * h * w * H * chunks;
-  VTP_REQUIRE((tasks + 3) / 4 <= INT_MAX, "vtp_depth_dlogits: too many tiles");
   hipLaunchKernelGGL(depth_dlogits_kernel, dim3(cdiv(tasks, 4)), dim3(SEG_THREADS), 0, (hipStream_t)stream, Z, ldz, aux, stats, G, ldg, B, h,
                      w, Hl, Wl, H, C, min_depth, max_depth, lam, chunks, tasks);
   return check_launch("depth_dlogits");

@@ -21,15 +21,7 @@ constexpr int SEG_SLICE = 512;   // token rows per weight-gradient slice: a cons
 __device__ __forceinline__ bool seg_valid(int lab, int C, int ignore) { return lab != ignore && lab < C; }
 
 // ---------------------------------------------------------------------------------------------------------------- pixel pass
-// (the tiling of the label map, seg_plan, is seg_bilinear.h's)
-__device__ __forceinline__ int block_sum_int(int v, int* red) {
-  v = wave_sum_int(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-
+// (the tiling of the label map, seg_plan, and a tile's geometry and cells, SegTile, are seg_bilinear.h's)
 // grid (tiles, B).  part_loss f32 [H, nblocks] and part_cnt i32 [2, nblocks] (valid, out of range) get one entry per workgroup;
 // seg_ce_fold_kernel adds them in workgroup order.
 __global__ __launch_bounds__(SEG_THREADS) void seg_ce_kernel(const float* __restrict__ Z, int ldz, const uint8_t* __restrict__ labels,
@@ -42,13 +34,8 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_ce_kernel(const float* __rest
   __shared__ int redi[4];
   const int tid = threadIdx.x, b = blockIdx.y, B = gridDim.y, tile = blockIdx.x;
   const int nblocks = gridDim.x * gridDim.y, blk = b * gridDim.x + tile;
-  const int y0 = (tile / tiles_x) * th, x0 = (tile % tiles_x) * tw;
-  const int y1 = min(y0 + th, Hl) - 1, x1 = min(x0 + tw, Wl) - 1;
-  const int fy0 = seg_tap(y0, h, Hl).i0, fx0 = seg_tap(x0, w, Wl).i0;
-  const int ncy = seg_tap(y1, h, Hl).i1 - fy0 + 1, ncx = seg_tap(x1, w, Wl).i1 - fx0 + 1;
-  const int Cs = C | 1;  // odd row length: the cells of neighbouring pixels land on different LDS banks
-  const int ncell = min(ncy * ncx, SEG_CELL_FLOATS / Cs);  // the host planned the tile so that the footprint fits
-  const int npix = th * tw;
+  const SegTile geo(tile, tiles_x, th, tw, h, w, Hl, Wl, C);
+  const int y0 = geo.y0, x0 = geo.x0, y1 = geo.y1, x1 = geo.x1, npix = th * tw;
   const long plane = (long)Hl * Wl;
   const uint8_t* lab_b = labels + b * plane;
 
@@ -67,11 +54,7 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_ce_kernel(const float* __rest
 
   for (int hh = 0; hh < H; ++hh) {
     __syncthreads();
-    for (int i = tid; i < ncell * C; i += SEG_THREADS) {
-      const int cell = i / C, c = i - cell * C;
-      const long row = ((long)b * h + fy0 + cell / ncx) * w + fx0 + cell % ncx;
-      cells[cell * Cs + c] = Z[row * ldz + (long)hh * C + c];
-    }
+    geo.stage(cells, Z, ldz, b, hh, h, w, C);
     if (conf)
       for (int i = tid; i < SEG_HASH; i += SEG_THREADS) hkey[i] = -1, hcnt[i] = 0;
     __syncthreads();
@@ -83,22 +66,19 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_ce_kernel(const float* __rest
       const bool ok = seg_valid(lab, C, ignore);
       if (!ok && !lse) continue;
       const SegTap ty = seg_tap(py, h, Hl), tx = seg_tap(px, w, Wl);
-      const float* c00 = cells + ((ty.i0 - fy0) * ncx + (tx.i0 - fx0)) * Cs;
-      const float* c01 = cells + ((ty.i0 - fy0) * ncx + (tx.i1 - fx0)) * Cs;
-      const float* c10 = cells + ((ty.i1 - fy0) * ncx + (tx.i0 - fx0)) * Cs;
-      const float* c11 = cells + ((ty.i1 - fy0) * ncx + (tx.i1 - fx0)) * Cs;
+      const SegCorners q = geo.corners(cells, ty, tx);
       float m = -INFINITY;
       int mi = 0;
       for (int c = 0; c < C; ++c) {
-        const float v = seg_blend(c00[c], c01[c], c10[c], c11[c], ty, tx);
+        const float v = seg_blend(q.c00[c], q.c01[c], q.c10[c], q.c11[c], ty, tx);
         if (v > m) m = v, mi = c;  // strict >: the lowest index of the maximum stays
       }
       float s = 0.f;
-      for (int c = 0; c < C; ++c) s += expf(seg_blend(c00[c], c01[c], c10[c], c11[c], ty, tx) - m);
+      for (int c = 0; c < C; ++c) s += expf(seg_blend(q.c00[c], q.c01[c], q.c10[c], q.c11[c], ty, tx) - m);
       const float l = m + logf(s);
       if (lse) lse[((long)hh * B + b) * plane + (long)py * Wl + px] = l;
       if (!ok) continue;
-      loss += l - seg_blend(c00[lab], c01[lab], c10[lab], c11[lab], ty, tx);
+      loss += l - seg_blend(q.c00[lab], q.c01[lab], q.c10[lab], q.c11[lab], ty, tx);
       if (conf) {  // integer counts in an LDS table first: one global atomic per (target, prediction) pair the tile holds
         const int key = lab * C + mi;
         unsigned slot = ((unsigned)key * 2654435761u) >> 21;
@@ -141,62 +121,30 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_ce_fold_kernel(const float* _
 }
 
 // ---------------------------------------------------------------------------------------------------------------- cell pass
-// One wave per (cell, head, chunk of 64 classes), lane = class.  A pixel that has the cell among its taps has its other taps in
-// the cell's 3 x 3 neighbourhood, whatever the scale: the nine logits of the lane's class sit in registers and the walk over the
-// candidate pixels (raster order, wave-uniform) reads only the label and lse of each pixel.
+// seg_cell_walk (seg_bilinear.h) with one wave per (cell, head, chunk of 64 classes), lane = class: the walk reads only the label and
+// lse of each pixel, its term is softmax minus one-hot.
 __global__ __launch_bounds__(SEG_THREADS) void seg_dlogits_kernel(const float* __restrict__ Z, int ldz, const uint8_t* __restrict__ labels,
                                                                  const float* __restrict__ lse, const int* __restrict__ call_counts,
                                                                  float* __restrict__ G, int ldg, int B, int h, int w, int Hl, int Wl, int H,
                                                                  int C, int ignore, int chunks, long tasks) {
-  const int lane = threadIdx.x & 63;
-  const long task = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const long task = seg_cell_task();
   if (task >= tasks) return;
-  const int cc = (int)(task % chunks);
-  const long t2 = task / chunks;
-  const int hh = (int)(t2 % H);
-  const long cell = t2 / H;
-  const int hw = h * w, b = (int)(cell / hw), iy = (int)(cell % hw) / w, ix = (int)(cell % w);
-  const int c = cc * 64 + lane, cl = c < C ? c : C - 1;
-  float nb[3][3];
-#pragma unroll
-  for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-    for (int dx = 0; dx < 3; ++dx) {
-      const int yy = min(max(iy + dy - 1, 0), h - 1), xx = min(max(ix + dx - 1, 0), w - 1);  // a clamped neighbour is never a tap
-      nb[dy][dx] = Z[((long)b * hw + (long)yy * w + xx) * ldz + (long)hh * C + cl];
-    }
-  // candidate pixels from the inverse map in integers, two pixels wider than src in [i - 1, i + 1) asks for; membership and weight
-  // are the tap function's
-  const int ylo = (int)max(0L, (2L * iy - 1) * Hl / (2L * h) - 2), yhi = (int)min((long)Hl - 1, ((2L * iy + 3) * Hl + 2L * h - 1) / (2L * h) + 1);
-  const int xlo = (int)max(0L, (2L * ix - 1) * Wl / (2L * w) - 2), xhi = (int)min((long)Wl - 1, ((2L * ix + 3) * Wl + 2L * w - 1) / (2L * w) + 1);
+  const SegCell t(task, h, w, H, C, chunks);
+  const int c = t.c;
   const long plane = (long)Hl * Wl;
-  const uint8_t* lab_b = labels + b * plane;
-  const float* lse_b = lse + ((long)hh * B + b) * plane;
-  float acc = 0.f;
-  for (int py = ylo; py <= yhi; ++py) {
-    const SegTap ty = seg_tap(py, h, Hl);
-    if (ty.i0 != iy && ty.i1 != iy) continue;
-    const float wy = (ty.i0 == iy ? ty.l0 : 0.f) + (ty.i1 == iy ? ty.l1 : 0.f);
-    const int ka = ty.i0 - iy + 1, kb = ty.i1 - iy + 1;
-    float ra[3], rb[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) ra[j] = seg_pick(nb[0][j], nb[1][j], nb[2][j], ka), rb[j] = seg_pick(nb[0][j], nb[1][j], nb[2][j], kb);
-    for (int px = xlo; px <= xhi; ++px) {
-      const SegTap tx = seg_tap(px, w, Wl);
-      if (tx.i0 != ix && tx.i1 != ix) continue;
-      const int lab = lab_b[(long)py * Wl + px];
-      if (!seg_valid(lab, C, ignore)) continue;
-      const float wx = (tx.i0 == ix ? tx.l0 : 0.f) + (tx.i1 == ix ? tx.l1 : 0.f);
-      const int ja = tx.i0 - ix + 1, jb = tx.i1 - ix + 1;
-      const float z = seg_blend(seg_pick(ra[0], ra[1], ra[2], ja), seg_pick(ra[0], ra[1], ra[2], jb), seg_pick(rb[0], rb[1], rb[2], ja),
-                                seg_pick(rb[0], rb[1], rb[2], jb), ty, tx);
-      const float g = expf(z - lse_b[(long)py * Wl + px]) - (lab == c ? 1.f : 0.f);
-      acc = fmaf(wy * wx, g, acc);
-    }
-  }
+  const uint8_t* lab_b = labels + t.b * plane;
+  const float* lse_b = lse + ((long)t.hh * B + t.b) * plane;
+  int lab;
+  const float acc = seg_cell_walk(
+      t, Z, ldz, h, w, Hl, Wl, C,
+      [&](int py, int px) {
+        lab = lab_b[(long)py * Wl + px];
+        return seg_valid(lab, C, ignore);
+      },
+      [&](int py, int px, float z) { return expf(z - lse_b[(long)py * Wl + px]) - (lab == c ? 1.f : 0.f); });
   const int nv = call_counts[0];
   const float inv = nv > 0 ? 1.f / (float)nv : 0.f;
-  if (c < C) G[cell * ldg + (long)hh * C + c] = acc * inv;
+  if (c < C) G[t.cell * ldg + (long)t.hh * C + c] = acc * inv;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- weight step
@@ -292,9 +240,7 @@ int seg_sgd_launch(const char* who, float* W, float* bias, float* mW, float* mb,
 using namespace vtp;
 
 extern "C" int vtp_seg_ce_workspace_bytes(int B, int h, int w, int Hl, int Wl, int H, int C) {
-  VTP_REQUIRE(Hl >= 1 && Wl >= 1, "vtp_seg_ce_workspace_bytes: bad label size (Hl, Wl >= 1)");
-  VTP_REQUIRE(C >= 1 && C <= 255 && H >= 1, "vtp_seg_ce_workspace_bytes: bad shape (H >= 1, 1 <= C <= 255)");
-  VTP_REQUIRE(seg_shape_ok(B, h, w, Hl, Wl), "vtp_seg_ce_workspace_bytes: bad shape (B, h, w >= 1; edges <= 32768; B Hl Wl < 2^31)");
+  if (seg_check("vtp_seg_ce_workspace_bytes", B, h, w, Hl, Wl, H, C, 1, 255, 0, nullptr, 0, nullptr, nullptr)) return VTP_ERR_ARG;
   const long n = seg_ce_bytes(seg_plan(h, w, Hl, Wl, C), B, H);
   VTP_REQUIRE(n <= INT_MAX, "vtp_seg_ce_workspace_bytes: more than 2 GiB (pass fewer heads per call)");
   return (int)n;
@@ -304,13 +250,9 @@ extern "C" int vtp_seg_ce(const float* Z, int ldz, const unsigned char* labels, 
                           int ignore_index, float* lse, long* conf, float* loss, int* call_counts, long* totals, void* workspace,
                           long workspace_bytes, void* stream) {
   VTP_REQUIRE(Z && labels && loss && call_counts && workspace, "vtp_seg_ce: null pointer");
-  VTP_REQUIRE(Hl >= 1 && Wl >= 1, "vtp_seg_ce: bad label size (Hl, Wl >= 1)");
-  VTP_REQUIRE(C >= 1 && C <= 255 && H >= 1 && (long)H * C * C <= INT_MAX, "vtp_seg_ce: bad shape (H >= 1, 1 <= C <= 255)");
-  VTP_REQUIRE(seg_shape_ok(B, h, w, Hl, Wl), "vtp_seg_ce: bad shape (B, h, w >= 1; edges <= 32768; B Hl Wl < 2^31)");
-  VTP_REQUIRE(ldz >= (long)H * C, "vtp_seg_ce: bad leading dimension (ldz >= H * C)");
-  const SegPlan p = seg_plan(h, w, Hl, Wl, C);
+  SegPlan p;
+  if (seg_check("vtp_seg_ce", B, h, w, Hl, Wl, H, C, 1, 255, (long)C * C, "ldz", ldz, &p, nullptr)) return VTP_ERR_ARG;
   const long tiles = (long)p.tiles_y * p.tiles_x, nblocks = tiles * B;
-  VTP_REQUIRE(nblocks <= INT_MAX / 4, "vtp_seg_ce: too many tiles");
   VTP_REQUIRE(workspace_bytes >= seg_ce_bytes(p, B, H) && ((uintptr_t)workspace & 3) == 0,
               "vtp_seg_ce: workspace too small (vtp_seg_ce_workspace_bytes) or not 4-byte aligned");
   float* part_loss = (float*)workspace;
@@ -325,13 +267,9 @@ extern "C" int vtp_seg_ce(const float* Z, int ldz, const unsigned char* labels, 
 extern "C" int vtp_seg_dlogits(const float* Z, int ldz, const unsigned char* labels, const float* lse, const int* call_counts, float* G,
                                int ldg, int B, int h, int w, int Hl, int Wl, int H, int C, int ignore_index, void* stream) {
   VTP_REQUIRE(Z && labels && lse && call_counts && G, "vtp_seg_dlogits: null pointer");
-  VTP_REQUIRE(Hl >= 1 && Wl >= 1, "vtp_seg_dlogits: bad label size (Hl, Wl >= 1)");
-  VTP_REQUIRE(C >= 1 && C <= 255 && H >= 1 && (long)H * C <= INT_MAX, "vtp_seg_dlogits: bad shape (H >= 1, 1 <= C <= 255)");
-  VTP_REQUIRE(seg_shape_ok(B, h, w, Hl, Wl), "vtp_seg_dlogits: bad shape (B, h, w >= 1; edges <= 32768; B Hl Wl < 2^31)");
-  VTP_REQUIRE(ldz >= (long)H * C && ldg >= (long)H * C, "vtp_seg_dlogits: bad leading dimension (ldz, ldg >= H * C)");
+  long tasks;
+  if (seg_check("vtp_seg_dlogits", B, h, w, Hl, Wl, H, C, 1, 255, C, "ldz, ldg", min(ldz, ldg), nullptr, &tasks)) return VTP_ERR_ARG;
   const int chunks = cdiv(C, 64);
-  const long tasks = (long)B * h * w * H * chunks;
-  VTP_REQUIRE((tasks + 3) / 4 <= INT_MAX, "vtp_seg_dlogits: too many tiles");
   hipLaunchKernelGGL(seg_dlogits_kernel, dim3(cdiv(tasks, 4)), dim3(SEG_THREADS), 0, (hipStream_t)stream, Z, ldz, labels, lse, call_counts,
                      G, ldg, B, h, w, Hl, Wl, H, C, ignore_index, chunks, tasks);
   return check_launch("seg_dlogits");

@@ -28,11 +28,10 @@ from typing import Dict, Optional, Sequence, Tuple
 import torch
 
 from . import ops
-from .banks import Group, Workspace, eval_device
-from .heads import HeadGroup, HeadStore, cosine_factor
+from .banks import Workspace
+from .denseprobe import SGD_WORKSPACE_BOUND, DenseProbe, Head  # noqa: F401 (re-exported)
+from .heads import cosine_factor
 
-Head = Tuple[str, int, float]  # (key, use_n_blocks, lr)
-SGD_WORKSPACE_BOUND = 64 << 20  # bytes of weight-gradient slices per launch; a group whose heads need more is stepped in chunks of heads
 METRICS = ("abs_rel", "sq_rel", "rmse", "rmse_log", "log10", "silog", "d1", "d2", "d3", "valid")
 
 
@@ -48,120 +47,42 @@ def metrics_from_counters(counts: torch.Tensor, sums: torch.Tensor) -> Dict[str,
             "d3": int(counts[3]) / n, "valid": n}
 
 
-class DepthProbe:
-    """heads: (key, use_n_blocks, lr) tuples with unique keys; heads with equal use_n_blocks form a group and are stored stacked
-    (heads.HeadStore: weight [H, n_bins, K], bias [H, n_bins] and their momentum buffers, contiguous fp32; normal_(0, 0.01) weights and
-    zero biases drawn on the host in creation order).  `keys` lists the heads group by group: the order of every per-head vector.
+class DepthProbe(DenseProbe):
+    """heads: (key, use_n_blocks, lr) tuples with unique keys, grouped and stored as denseprobe.DenseProbe describes (C = n_bins).
     cls_concat appends each block's class token to every one of its patch tokens (K = 2 D per block).  model may be None when only
     the *_features methods are used (then pass embed_dim)."""
+
+    _COLS = "n_max Dc"
+    _sgd = staticmethod(ops.depth_sgd)
+    _sgd_workspace_bytes = staticmethod(ops.depth_sgd_workspace_bytes)
 
     def __init__(self, model, heads: Sequence[Head], min_depth: float = 0.001, max_depth: float = 10.0, n_bins: int = 256,
                  lam: float = 0.85, momentum: float = 0.9, max_iter: Optional[int] = None, group=None, *, cls_concat: bool = False,
                  embed_dim: Optional[int] = None, device=None):
-        self.device = eval_device("DepthProbe", model, device)
-        self.model = model
-        self.D = int(embed_dim if embed_dim is not None else model.config.vision_embed_dim)
-        if self.D % 4:
-            raise ValueError(f"embed_dim must be a multiple of 4 (16-byte column slices), got {self.D}")
         if not 2 <= int(n_bins) <= 1024:
             raise ValueError(f"n_bins must be in [2, 1024], got {n_bins}")
         if not 0.0 < float(min_depth) < float(max_depth) < math.inf:
             raise ValueError(f"need 0 < min_depth < max_depth, got {min_depth}, {max_depth}")
-        if max_iter is not None and max_iter < 1:
-            raise ValueError("max_iter must be >= 1 (or None for constant learning rates)")
-        self.C, self.min_depth, self.max_depth, self.lam = int(n_bins), float(min_depth), float(max_depth), float(lam)
-        self.momentum, self.max_iter, self.cls_concat = float(momentum), max_iter, bool(cls_concat)
-        self.Dc = 2 * self.D if self.cls_concat else self.D
-        self.group = group
-        self._group = Group(group)
-        self.world, self.rank = self._group.world, self._group.rank
-        heads = [(str(k), int(n), float(lr)) for k, n, lr in heads]
-        if not heads:
-            raise ValueError("no heads")
-        if len({k for k, _, _ in heads}) != len(heads):
-            raise ValueError("head keys must be unique")
-        self.n_max = max(n for _, n, _ in heads)
-        init = {}
-        for key, n, _ in heads:
-            if n < 1:
-                raise ValueError(f"{key}: use_n_blocks must be >= 1")
-            init[key] = (torch.empty(self.C, n * self.Dc).normal_(mean=0.0, std=0.01), torch.zeros(self.C))
-        # a group reads the last n blocks: the trailing n Dc columns of X_all
-        self.heads = HeadStore([(key, n, n * self.Dc, (self.n_max - n) * self.Dc, lr) for key, n, lr in heads], init, self.device, max_iter)
-        del init
-        self.groups, self.keys = self.heads.groups, self.heads.keys
-        self.steps = 0
-        self.head_chunk: Optional[int] = None  # heads per weight-step launch; None: as many as SGD_WORKSPACE_BOUND allows
-        self._ws_pix, self._ws_aux, self._ws_sgd = Workspace(self.device), Workspace(self.device), Workspace(self.device)
+        super().__init__(model, heads, n_bins, momentum, max_iter, group, cls_concat, embed_dim, device)
+        self.min_depth, self.max_depth, self.lam = float(min_depth), float(max_depth), float(lam)
+        self._ws_pix, self._ws_aux = Workspace(self.device), Workspace(self.device)
         self._stats = torch.zeros(len(self.keys), 4, device=self.device, dtype=torch.float64)  # (n, m1, m2, L) of the last call
         self._counts = torch.zeros(len(self.keys), 4, device=self.device, dtype=torch.int64)
         self._sums = torch.zeros(len(self.keys), 6, device=self.device, dtype=torch.float64)
 
-    # ------------------------------------------------------------------------------------------------ inputs
-    def features(self, images: torch.Tensor) -> torch.Tensor:
-        """X_all f32 [B h w, n_max Dc] with (h, w) = the image size over the patch size 16: the patch tokens of the last n_max
-        blocks, each through the trunk's final norm, in ascending block order; with cls_concat every patch token is followed by its
-        block's class token (patch then cls, Dc = 2 D)"""
-        if self.model is None:
-            raise RuntimeError("DepthProbe was built without a model: use the *_features methods")
-        outs = self.model.get_intermediate_layers_feature(images, n=self.n_max, norm=True, return_class_token=self.cls_concat)
-        cols = []
-        for o in outs:
-            patch, cls_t = o if self.cls_concat else (o, None)
-            B, T, D = patch.shape
-            cols.append(patch.reshape(B * T, D))
-            if cls_t is not None:
-                cols.append(cls_t[:, None, :].expand(B, T, D).reshape(B * T, D))
-        return torch.cat(cols, dim=1)
-
-    @staticmethod
-    def _hw(images: torch.Tensor) -> Tuple[int, int]:
-        return images.shape[-2] // 16, images.shape[-1] // 16
-
-    def _features(self, x_all: torch.Tensor, hw, B: int):
-        h, w = int(hw[0]), int(hw[1])
-        x = x_all.detach().to(torch.float32)
-        if x.dim() != 2 or h < 1 or w < 1 or tuple(x.shape) != (B * h * w, self.n_max * self.Dc):
-            raise ValueError(f"features must be [B h w, n_max Dc] = [{B * h * w}, {self.n_max * self.Dc}], got {tuple(x_all.shape)}")
-        if x.stride(1) != 1 or x.stride(0) % 4 or x.data_ptr() % 16:
-            x = x.contiguous()
-        return x, (h, w)
-
-    def _inputs(self, x_all: torch.Tensor, hw, labels: torch.Tensor):
-        for name, t in (("features", x_all), ("labels", labels)):
-            if not isinstance(t, torch.Tensor) or not t.is_cuda:
-                raise ValueError(f"{name} must live on the MI355X (got a CPU tensor): there is no CPU path")
+    def _labels(self, labels: torch.Tensor) -> torch.Tensor:
         if not labels.is_floating_point() or labels.dim() != 3 or min(labels.shape) < 1:
             raise ValueError(f"labels must be floating-point depth [B, Hl, Wl], got {labels.dtype} {tuple(labels.shape)}")
-        x, hw = self._features(x_all, hw, labels.shape[0])
-        return x, hw, labels.detach().to(torch.float32).contiguous()
-
-    def _head_chunk(self, g: HeadGroup, M: int) -> int:
-        if self.head_chunk is not None:
-            return max(1, min(g.H, int(self.head_chunk)))
-        per_head = ops.depth_sgd_workspace_bytes(M, self.C, g.K)
-        return max(1, min(g.H, SGD_WORKSPACE_BOUND // per_head))
-
-    def _logits(self, g: HeadGroup, x: torch.Tensor, M: int) -> torch.Tensor:
-        z = torch.empty(M, g.H * self.C, device=self.device, dtype=torch.float32)
-        ops.probe_logits(x[:, g.col0:g.col0 + g.K], g.weight, g.bias, z, M, g.H * self.C, g.K)
-        return z
+        return labels.detach().to(torch.float32).contiguous()
 
     def _range(self):
         return self.min_depth, self.max_depth, self.lam
 
     # ------------------------------------------------------------------------------------------------ training
-    def learning_rates(self, step: Optional[int] = None) -> Dict[str, float]:
-        return self.heads.learning_rates(self.steps if step is None else step)
-
-    def step(self, images: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-        return self.step_features(self.features(images), self._hw(images), labels)
-
     def step_features(self, x_all: torch.Tensor, hw, labels: torch.Tensor) -> torch.Tensor:
         """one optimizer step of every head on X_all [B h w, n_max Dc] and labels [B, Hl, Wl]; returns the per-head losses (device
         f32, order of `keys`, no host sync).  Without a valid pixel the loss and the gradient are 0 and the momentum still decays."""
-        if self.world > 1:
-            raise NotImplementedError("Training is single-process in this pull request.")
+        self._single_process()
         x, (h, w), y = self._inputs(x_all, hw, labels)
         B, Hl, Wl = y.shape
         M, C = B * h * w, self.C
@@ -169,7 +90,6 @@ class DepthProbe:
         f = cosine_factor(self.steps, self.max_iter)
         for g in self.groups:
             self.heads.set_lr(g, f)
-            xs = x[:, g.col0:g.col0 + g.K]
             z = self._logits(g, x, M)
             grad = torch.empty(M, g.H * C, device=self.device, dtype=torch.float32)
             ws = self._ws_pix.at_least(ops.depth_pix_workspace_bytes(B, h, w, Hl, Wl, g.H, C))
@@ -177,19 +97,11 @@ class DepthProbe:
             stats = self._stats[g.off:g.off + g.H]
             ops.depth_pix(z, y, (h, w), g.H, C, *self._range(), aux=aux, loss=losses[g.off:g.off + g.H], stats=stats, workspace=ws)
             ops.depth_dlogits(z, (B, Hl, Wl), (h, w), g.H, C, *self._range(), aux, stats, grad)
-            step = self._head_chunk(g, M)
-            for lo in range(0, g.H, step):  # the chunking bounds the workspace and changes no bit of the result
-                n = min(step, g.H - lo)
-                ws = self._ws_sgd.at_least(ops.depth_sgd_workspace_bytes(M, n * C, g.K))
-                ops.depth_sgd(g.weight[lo:lo + n], g.bias[lo:lo + n], g.m_weight[lo:lo + n], g.m_bias[lo:lo + n], grad[:, lo * C:], xs,
-                              g.lr[lo:lo + n], M, n, C, g.K, self.momentum, ws)
+            self._weight_step(g, grad, x[:, g.col0:g.col0 + g.K], M)
         self.steps += 1
         return losses
 
     # ------------------------------------------------------------------------------------------------ evaluation
-    def evaluate(self, images: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-        return self.evaluate_features(self.features(images), self._hw(images), labels)
-
     def evaluate_features(self, x_all: torch.Tensor, hw, labels: torch.Tensor) -> torch.Tensor:
         """adds this batch to the evaluation counters (depth predicted at the labels' own size, invalid pixels skipped); returns its
         per-head losses (device f32, no host sync)"""
@@ -209,8 +121,7 @@ class DepthProbe:
 
     def predict_features(self, x_all: torch.Tensor, hw, out_hw) -> torch.Tensor:
         """f32 [heads, B, Ho, Wo]: the depth of every head (order of `keys`) at out_hw = (Ho, Wo), in [min_depth, max_depth]"""
-        if not isinstance(x_all, torch.Tensor) or not x_all.is_cuda:
-            raise ValueError("features must live on the MI355X (got a CPU tensor): there is no CPU path")
+        self._on_device(features=x_all)
         h, w = int(hw[0]), int(hw[1])
         Ho, Wo = int(out_hw[0]), int(out_hw[1])
         if h < 1 or w < 1 or Ho < 1 or Wo < 1 or x_all.dim() != 2 or x_all.shape[0] % (h * w):
@@ -244,23 +155,3 @@ class DepthProbe:
     def reset_eval(self) -> None:
         self._counts.zero_()
         self._sums.zero_()
-
-    # ------------------------------------------------------------------------------------------------ checkpoints
-    def state_dict(self) -> Dict[str, torch.Tensor]:
-        return {**{name: t.clone() for name, t in self._named()}, "steps": torch.tensor(self.steps, dtype=torch.int64)}
-
-    def _named(self):
-        """(checkpoint key, tensor view) per head: heads.<key>.weight, heads.<key>.bias, momentum.<key>.weight, momentum.<key>.bias"""
-        entries = list(self.heads.entries())
-        for (k, _, w, mw), (_, _, b, mb) in zip(entries[0::2], entries[1::2]):  # a head's weight entry, then its bias entry
-            yield from ((f"heads.{k}.weight", w), (f"heads.{k}.bias", b), (f"momentum.{k}.weight", mw), (f"momentum.{k}.bias", mb))
-
-    def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
-        want = {f"{p}.{k}.{q}" for k in self.keys for p in ("heads", "momentum") for q in ("weight", "bias")} | {"steps"}
-        if want != set(sd):
-            raise KeyError(f"load_state_dict: missing {sorted(want - set(sd))}, unexpected {sorted(set(sd) - want)}")
-        for name, dst in self._named():
-            if sd[name].shape != dst.shape:
-                raise ValueError(f"{name}: shape {tuple(sd[name].shape)}, expected {tuple(dst.shape)}")
-            dst.copy_(sd[name])
-        self.steps = int(sd["steps"])

@@ -611,6 +611,13 @@ def _size_or_raise(fn, *args):
     return n
 
 
+def _need_token_map(rows, cols, **tensors):
+    """z / g of the dense probes: [rows = B h w, >= cols = H C] with unit column stride (a column slice of a wider matrix is fine)"""
+    for name, t in tensors.items():
+        if t.dim() != 2 or t.shape[0] != rows or t.stride(1) != 1:
+            raise ValueError(f"{name} must be [{rows}, >= {cols}] with unit column stride, got {tuple(t.shape)}")
+
+
 def seg_ce_workspace_bytes(B, h, w, Hl, Wl, H, C):
     """bytes of workspace seg_ce needs; ValueError for arguments the kernel refuses or a workspace above 2 GiB"""
     return _size_or_raise(_lib_().vtp_seg_ce_workspace_bytes, B, h, w, Hl, Wl, H, C)
@@ -634,8 +641,7 @@ def seg_ce(z, labels, hw, H, C, ignore_index, loss, call_counts, workspace, lse=
     _need(workspace, "workspace", torch.uint8, dims=1)
     _need_f32(z=z)
     _need_gpu(labels=labels, loss=loss, call_counts=call_counts, lse=lse, conf=conf, totals=totals, workspace=workspace)
-    if z.dim() != 2 or z.shape[0] != B * h * w or z.stride(1) != 1:
-        raise ValueError(f"z must be [{B * h * w}, >= {H * C}] with unit column stride, got {tuple(z.shape)}")
+    _need_token_map(B * h * w, H * C, z=z)
     _lib.check(_lib_().vtp_seg_ce(_p(z), z.stride(0), _p(labels), B, h, w, Hl, Wl, H, C, ignore_index, _p(lse), _p(conf), _p(loss),
                                   _p(call_counts), _p(totals), _p(workspace), workspace.numel(), _s()), "vtp_seg_ce")
 
@@ -649,9 +655,7 @@ def seg_dlogits(z, labels, hw, H, C, ignore_index, lse, call_counts, g):
     _need(call_counts, "call_counts", torch.int32, (2,))
     _need_f32(z=z, g=g)
     _need_gpu(labels=labels, lse=lse, call_counts=call_counts)
-    for name, t in (("z", z), ("g", g)):
-        if t.dim() != 2 or t.shape[0] != B * h * w or t.stride(1) != 1:
-            raise ValueError(f"{name} must be [{B * h * w}, >= {H * C}] with unit column stride, got {tuple(t.shape)}")
+    _need_token_map(B * h * w, H * C, z=z, g=g)
     _lib.check(_lib_().vtp_seg_dlogits(_p(z), z.stride(0), _p(labels), _p(lse), _p(call_counts), _p(g), g.stride(0), B, h, w, Hl, Wl,
                                        H, C, ignore_index, _s()), "vtp_seg_dlogits")
 
@@ -661,24 +665,38 @@ def seg_sgd_slice():
     return _lib_().vtp_seg_sgd_slice()
 
 
+def _dense_sgd_workspace_bytes(name, M, N, K):
+    return _size_or_raise(getattr(_lib_(), name), M, N, K)
+
+
+def _dense_sgd(name, w, bias, mw, mb, g, x, lr, M, H, C, K, momentum, workspace):
+    _need(workspace, "workspace", torch.uint8, dims=1)
+    _need_f32(w=w, bias=bias, mw=mw, mb=mb, g=g, x=x, lr=lr)
+    _need_gpu(workspace=workspace)
+    _lib.check(getattr(_lib_(), name)(_p(w), _p(bias), _p(mw), _p(mb), _p(g), g.stride(0), _p(x), x.stride(0), _p(lr), M, H, C, K,
+                                      momentum, _p(workspace), workspace.numel(), _s()), name)
+
+
 def seg_sgd_workspace_bytes(M, N, K):
     """bytes of workspace seg_sgd needs for M token rows and N = H * C outputs; ValueError for refused arguments or above 2 GiB"""
-    return _size_or_raise(_lib_().vtp_seg_sgd_workspace_bytes, M, N, K)
+    return _dense_sgd_workspace_bytes("vtp_seg_sgd_workspace_bytes", M, N, K)
 
 
 def seg_sgd(w, bias, mw, mb, g, x, lr, M, H, C, K, momentum, workspace):
     """probe_sgd for M token rows, sliced over the rows and folded in slice order: w [H*C, K], bias [H*C] and their momentum buffers
     updated in place from g [M, >= H*C] and x [M, K] (a column slice); lr f32 [H] on the device"""
-    _need(workspace, "workspace", torch.uint8, dims=1)
-    _need_f32(w=w, bias=bias, mw=mw, mb=mb, g=g, x=x, lr=lr)
-    _need_gpu(workspace=workspace)
-    _lib.check(_lib_().vtp_seg_sgd(_p(w), _p(bias), _p(mw), _p(mb), _p(g), g.stride(0), _p(x), x.stride(0), _p(lr), M, H, C, K, momentum,
-                                   _p(workspace), workspace.numel(), _s()), "vtp_seg_sgd")
+    _dense_sgd("vtp_seg_sgd", w, bias, mw, mb, g, x, lr, M, H, C, K, momentum, workspace)
 
 
 def depth_pix_workspace_bytes(B, h, w, Hl, Wl, H, C, aux=False):
     """bytes of workspace depth_pix needs, or with aux=True bytes of its aux plane; ValueError for refused arguments or above 2 GiB"""
     return _size_or_raise(_lib_().vtp_depth_pix_workspace_bytes, B, h, w, Hl, Wl, H, C, int(bool(aux)))
+
+
+def _need_aux(aux, B, h, w, Hl, Wl, H, C):
+    _need(aux, "aux", torch.uint8, dims=1)
+    if aux.numel() < depth_pix_workspace_bytes(B, h, w, Hl, Wl, H, C, aux=True) or aux.data_ptr() % 4:
+        raise ValueError("aux is smaller than depth_pix_workspace_bytes(..., aux=True) or not 4-byte aligned")
 
 
 def depth_pix(z, gt, hw, H, C, min_depth, max_depth, lam, *, out_hw=None, dhat=None, aux=None, loss=None, stats=None, workspace=None,
@@ -701,17 +719,14 @@ def depth_pix(z, gt, hw, H, C, min_depth, max_depth, lam, *, out_hw=None, dhat=N
         _need(stats, "stats", torch.float64, (H, 4))
         _need(workspace, "workspace", torch.uint8, dims=1)
     if aux is not None:
-        _need(aux, "aux", torch.uint8, dims=1)
-        if aux.numel() < depth_pix_workspace_bytes(B, h, w, Hl, Wl, H, C, aux=True) or aux.data_ptr() % 4:
-            raise ValueError("aux is smaller than depth_pix_workspace_bytes(..., aux=True) or not 4-byte aligned")
+        _need_aux(aux, B, h, w, Hl, Wl, H, C)
     if eval_counts is not None:
         _need(eval_counts, "eval_counts", torch.int64, (H, 4))
     if eval_sums is not None:
         _need(eval_sums, "eval_sums", torch.float64, (H, 6))
     _need_f32(z=z)
     _need_gpu(gt=gt, dhat=dhat, aux=aux, loss=loss, stats=stats, workspace=workspace, eval_counts=eval_counts, eval_sums=eval_sums)
-    if z.dim() != 2 or z.shape[0] != B * h * w or z.stride(1) != 1:
-        raise ValueError(f"z must be [{B * h * w}, >= {H * C}] with unit column stride, got {tuple(z.shape)}")
+    _need_token_map(B * h * w, H * C, z=z)
     _lib.check(_lib_().vtp_depth_pix(_p(z), z.stride(0), _p(gt), B, h, w, Hl, Wl, H, C, min_depth, max_depth, lam, _p(dhat), _p(aux),
                                      _p(loss), _p(stats), _p(eval_counts), _p(eval_sums), _p(workspace),
                                      0 if workspace is None else workspace.numel(), _s()), "vtp_depth_pix")
@@ -721,31 +736,23 @@ def depth_dlogits(z, label_hw, hw, H, C, min_depth, max_depth, lam, aux, stats, 
     """cell pass: g f32 [B*h*w, >= H*C] = d L / d z, gathered per cell from aux and stats of depth_pix; label_hw = (B, Hl, Wl)"""
     h, w = hw
     B, Hl, Wl = label_hw
-    _need(aux, "aux", torch.uint8, dims=1)
+    _need_aux(aux, B, h, w, Hl, Wl, H, C)
     _need(stats, "stats", torch.float64, (H, 4))
-    if aux.numel() < depth_pix_workspace_bytes(B, h, w, Hl, Wl, H, C, aux=True) or aux.data_ptr() % 4:
-        raise ValueError("aux is smaller than depth_pix_workspace_bytes(..., aux=True) or not 4-byte aligned")
     _need_f32(z=z, g=g)
     _need_gpu(aux=aux, stats=stats)
-    for name, t in (("z", z), ("g", g)):
-        if t.dim() != 2 or t.shape[0] != B * h * w or t.stride(1) != 1:
-            raise ValueError(f"{name} must be [{B * h * w}, >= {H * C}] with unit column stride, got {tuple(t.shape)}")
+    _need_token_map(B * h * w, H * C, z=z, g=g)
     _lib.check(_lib_().vtp_depth_dlogits(_p(z), z.stride(0), _p(aux), _p(stats), _p(g), g.stride(0), B, h, w, Hl, Wl, H, C, min_depth,
                                          max_depth, lam, _s()), "vtp_depth_dlogits")
 
 
 def depth_sgd_workspace_bytes(M, N, K):
     """bytes of workspace depth_sgd needs for M token rows and N = H * C outputs; ValueError for refused arguments or above 2 GiB"""
-    return _size_or_raise(_lib_().vtp_depth_sgd_workspace_bytes, M, N, K)
+    return _dense_sgd_workspace_bytes("vtp_depth_sgd_workspace_bytes", M, N, K)
 
 
 def depth_sgd(w, bias, mw, mb, g, x, lr, M, H, C, K, momentum, workspace):
     """seg_sgd for up to 1024 outputs per head: the same kernels, the same bits"""
-    _need(workspace, "workspace", torch.uint8, dims=1)
-    _need_f32(w=w, bias=bias, mw=mw, mb=mb, g=g, x=x, lr=lr)
-    _need_gpu(workspace=workspace)
-    _lib.check(_lib_().vtp_depth_sgd(_p(w), _p(bias), _p(mw), _p(mb), _p(g), g.stride(0), _p(x), x.stride(0), _p(lr), M, H, C, K,
-                                     momentum, _p(workspace), workspace.numel(), _s()), "vtp_depth_sgd")
+    _dense_sgd("vtp_depth_sgd", w, bias, mw, mb, g, x, lr, M, H, C, K, momentum, workspace)
 
 
 def zs_class_mean(feat, wt, C, T, D, eps=1e-12):
